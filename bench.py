@@ -3,6 +3,8 @@
 
     python bench.py --gpus N --steps K --warmup W            (N = 1: run directly)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py ... --dump-outputs DIR                   (+ the last timed step's outputs as DIR/<name>.npy)
+    python bench.py ... --full                               (+ roofline, PCIe-inclusive rate, CPU baseline, other configs)
 
 A "step" is one pass of the hot path over one batch of synthetic patches already resident in HBM:
 VQAE.forward = conv encoder -> p=4 vector quantiser -> conv decoder (reference vq_ae/model.py:41-48)
@@ -10,6 +12,10 @@ on BASELINE.json configs[1]: batch 256 of 256x256x3 fp32 patches -> 32x32 codes,
 codebook (SURVEY.md §8 "cfg B"), per GPU.  With N > 1 the patch batch is sharded (weak scaling:
 256 patches per rank) and each step ends with the path's only collective, an RCCL all-gather of the
 uint8 code grids.  Rank 0 prints ONE JSON line.
+
+A plain run only sets up, warms up, times the K steps, writes the outputs (--dump-outputs) and prints the line.  Everything
+else the line can carry -- the `roofline` of the dominant kernel (HIP events on its launches), `value_with_h2d`, the CPU
+baseline with its parity sample, and the `other_configs` legs -- is measured only with --full.
 """
 import argparse
 import ctypes
@@ -108,6 +114,24 @@ def synth_weights(spec_name):
     return O.make_params(O.SPECS[spec_name], 0)
 
 
+DUMP_RECON_SAMPLE = 1 << 22       # elements of the reconstruction written by --dump-outputs (16 MB of float32)
+
+
+def dump_outputs(path, out, idx, loss):
+    """What the timed path handed its caller in the last timed step, as float32 / float64 .npy files: the code grids
+    (exact as float32), the VQ loss and a fixed, seeded sample of the reconstruction (the whole of it is 200 MB at cfg B)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"codes": idx.float().cpu().numpy(), "vq_loss": loss.double().cpu().numpy()}
+    if out is not None:
+        flat = out.reshape(-1)
+        n = min(flat.numel(), DUMP_RECON_SAMPLE)
+        sel = np.sort(np.random.Generator(np.random.PCG64(7)).integers(0, flat.numel(), n))  # same positions every run
+        arrays["recon_sample"] = flat[torch.from_numpy(sel).to(flat.device)].float().cpu().numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"outputs written to {path}: " + ", ".join(f"{k} {tuple(a.shape)} {a.dtype}" for k, a in arrays.items()))
+
+
 def cpu_baseline(spec_name, size, params, embed, sample_batch, iters):
     """The CPU oracle (PyTorch-CPU fp32 restatement of the reference path) timed on this box's host
     cores, on a bounded sample of the same workload."""
@@ -178,7 +202,7 @@ def run_leg(args, ctx, headline):
     # timed region; the dominant kernel class is timed with HIP events on the launch stream
     lib = L.lib()
     n_launch_max = args.steps * 256
-    prof_on = rank == 0 and args.prof_class > 0
+    prof_on = rank == 0 and args.full and args.prof_class > 0
     if prof_on:
         L.check(lib.vqae_prof_begin(args.prof_class, n_launch_max))
     barrier()
@@ -198,10 +222,12 @@ def run_leg(args, ctx, headline):
         dt = float(t.item())
         if rank == 0:          # the gathered grids hold every rank's tiles in rank order
             assert torch.equal(gathered[:B], idx)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, gathered if use_dist else idx, loss)
 
     # ---- the same steps with the batch coming from pinned host memory each step (PCIe-inclusive rate; never `value`) ----
     h2d_value = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         host = x.cpu().pin_memory()
         xd = torch.empty_like(x)
         n_h2d = max(2, min(args.steps, 5))
@@ -237,8 +263,9 @@ def run_leg(args, ctx, headline):
             "conv_tflops_direct_equivalent": round(value * flops_patch / 1e12, 2),
             "recon_mse_vs_input": float(((out - x) ** 2).mean()) if out is not None else None,
             "vq_loss": float(loss),
-            "value_with_h2d": round(h2d_value, 2) if h2d_value else None,
         }
+        if args.full:
+            res["value_with_h2d"] = round(h2d_value, 2) if h2d_value else None
         # ---- roofline of the dominant kernel ---------------------------------------------------
         if prof_on and k_n.value > 0:
             avg_ms = k_ms.value / k_n.value
@@ -309,7 +336,7 @@ def run_leg(args, ctx, headline):
                                    "valu_frac_of_78.6Tops": round(alg / (avg_ms * 1e-3) / 78.6e12, 4)}
             res["roofline"]["frac"] = round(res["roofline"]["achieved"] / res["roofline"]["peak"], 4)
         # ---- CPU baseline beside it (rank 0, N = 1 only) -----------------------------------------
-        if world == 1 and not args.no_cpu_baseline and args.dtype == "f32":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.dtype == "f32":
             sb = 16 if size == 256 else 4                  # ~10-20 s of CPU work on the box's 16-core share
             log("cpu baseline ...")
             cb, cx, cout, cidx = cpu_baseline(args.config, size, params, embed, sb, 4)
@@ -329,20 +356,29 @@ def run_leg(args, ctx, headline):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="B", choices=["A", "B", "C", "BM"])
     ap.add_argument("--batch", type=int, default=256, help="patches per GPU per step")
     ap.add_argument("--mode", default="full", choices=["full", "encode"])
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16", "f16"],
                     help="compute dtype of the convolutions (16-bit = torch.autocast semantics); headline: f32")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--prof-class", type=int, default=1, help="kernel class timed for `roofline` (1 = trunk 3x3 conv)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (codes, vq_loss, a seeded sample of the reconstruction) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline of the dominant kernel, the PCIe-inclusive rate, the CPU baseline "
+                         "and the other configurations (`other_configs`); off: only the timed steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--prof-class", type=int, default=1,
+                    help="kernel class timed for `roofline` under --full (1 = trunk 3x3 conv)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short legs of the other BASELINE configs that the default N = 1 line carries")
+                    help="skip the short legs of the other BASELINE configs that the default N = 1 --full line carries")
     ap.add_argument("--no-slide-leg", action="store_true", help="skip the whole-slide extraction leg of other_configs")
     ap.add_argument("--other-steps", type=int, default=5)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -374,14 +410,14 @@ def main():
 
     # ---- the other BASELINE.json configs that fit one GPU, as short legs of the same (driver-timed) process -------
     # `metric` / `value` / `config` stay the headline's; the legs land under "other_configs".  N = 1 and the default
-    # headline only; each leg frees its handle and workspace before the next one starts.
-    if rank == 0 and world == 1 and not args.no_other_configs and \
+    # headline only, under --full; each leg frees its handle and workspace before the next one starts.
+    if args.full and rank == 0 and world == 1 and not args.no_other_configs and \
             (args.config, args.dtype, args.batch, args.mode, args.prof_class) == ("B", "f32", 256, "full", 1):
         other = {}
         for key, cfgname, dt, mode, pclass in OTHER_LEGS:
             leg = argparse.Namespace(**vars(args))
             leg.config, leg.dtype, leg.mode, leg.prof_class = cfgname, dt, mode, pclass
-            leg.steps, leg.warmup, leg.no_cpu_baseline = args.other_steps, 2, True
+            leg.steps, leg.warmup, leg.no_cpu_baseline, leg.dump_outputs = args.other_steps, 2, True, None
             log(f"other_configs leg {key}: cfg {cfgname} {dt} {mode}")
             try:
                 r = run_leg(leg, ctx, headline=False)

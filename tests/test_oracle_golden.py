@@ -9,6 +9,17 @@ import torch
 from conftest import load_golden, tap_sample
 
 
+@pytest.fixture(autouse=True)
+def recording_threads():
+    """The fixtures were recorded with torch on 8 CPU threads.  torch's CPU reductions split their work by the thread
+    count, so the bit-exact comparisons below hold at that count whatever the machine's core count or OMP_NUM_THREADS
+    (1, 2 and 4 threads round some sums differently)."""
+    n = torch.get_num_threads()
+    torch.set_num_threads(8)
+    yield
+    torch.set_num_threads(n)
+
+
 @pytest.mark.parametrize("D,K", [(8, 256), (128, 256), (256, 1024), (32, 16)])
 def test_vq_oracle_matches_reference_fixture(oracle, D, K):
     g = load_golden(f"vq_D{D}_K{K}")
