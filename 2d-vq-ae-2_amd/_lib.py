@@ -21,6 +21,8 @@ ACT_NONE, ACT_ELU, ACT_SILU = 0, 1, 2
 DW_SAME, DW_DOWN, DW_UP = 0, 1, 2
 BLOCK_FIXUP, BLOCK_MBCONV = 0, 1
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
+# VQAE_METRIC_*: columns of the vqae_recon_metrics_f32 output rows
+METRIC_NAMES = ("mse", "huber", "psnr", "ssim", "pred_min", "pred_max", "target_min", "target_max")
 DTYPES = {"f32": DT_F32, "fp32": DT_F32, "float32": DT_F32, "bf16": DT_BF16, "bfloat16": DT_BF16,
           "f16": DT_F16, "fp16": DT_F16, "float16": DT_F16, "half": DT_F16}
 
@@ -116,6 +118,9 @@ SYMBOLS = {
     "vqae_block_count": (c_int, [c_void_p, c_int]),
     "vqae_run_blocks": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, POINTER(c_int),
                                 POINTER(c_int), c_void_p]),
+    "vqae_recon_metrics_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "vqae_recon_metrics_f32": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_float), POINTER(c_float), c_int, c_int, c_int,
+                                       c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     "vqae_flops_per_patch": (c_double, [c_void_p, c_int, c_int, c_int, c_int]),
     "vqae_prof_begin": (c_int, [c_int, c_int]),
     "vqae_prof_end": (c_int, [POINTER(c_double), POINTER(c_int), POINTER(c_double)]),
@@ -153,4 +158,6 @@ def check(rc: int):
         raise KeyError(msg)                       # missing state-dict entry
     if rc == -4:
         raise MemoryError(msg)
+    if rc == -6:
+        raise ValueError(msg)                     # reference: torchmetrics' ValueError
     raise VqaeHipError(f"libvqae_hip error {rc}: {msg}")

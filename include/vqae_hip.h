@@ -35,7 +35,8 @@ typedef enum vqae_status {
     VQAE_ERR_UNSUPPORTED = -2,    /* reference: NotImplementedError (vq.py:100-104) */
     VQAE_ERR_HIP = -3,            /* HIP runtime failure */
     VQAE_ERR_NOMEM = -4,
-    VQAE_ERR_NOT_FOUND = -5       /* missing tensor name in a weight set (reference: KeyError in load_state_dict) */
+    VQAE_ERR_NOT_FOUND = -5,      /* missing tensor name in a weight set (reference: KeyError in load_state_dict) */
+    VQAE_ERR_VALUE = -6           /* reference: ValueError (torchmetrics SSIM on an image smaller than its window) */
 } vqae_status;
 
 enum { VQAE_LAYOUT_NHWC = 0, VQAE_LAYOUT_NCHW = 1 };
@@ -310,7 +311,40 @@ int vqae_run_blocks(vqae_handle* h, int side, int first, int count, const float*
 double vqae_flops_per_patch(const vqae_handle* h, int in_h, int in_w, int encoder, int decoder);
 
 /* ---------------------------------------------------------------------------------------------
- * 4. Measurement hook (bench.py `roofline`): time every launch of one kernel class with HIP events
+ * 4. Reconstruction metrics -- replaces the validation scoring of the reference: VQAE.shared_step
+ *    (vq_ae/model.py:82-93: `val_recon_loss` = loss_f(out, x) with loss_f/huber.yaml, and the torchmetrics
+ *    collection of conf/model/metrics/{mse,psnr,ssim}.yaml, torchmetrics 0.8.2), which
+ *    scripts/extract_validation_metrics/eval.py:13-45 runs over a checkpoint with batch size 1.
+ *    Per image i (p, t = prediction, target [C][H][W], N = C*H*W, d = p - t):
+ *      mse   = sum d^2 / N;   huber = sum h(d) / N,  h(d) = 0.5 d^2 if |d| < delta else delta (|d| - 0.5 delta);
+ *      psnr  = 10 log10((max t - min t)^2 / mse)       (PeakSignalNoiseRatio, data_range=None; mse = 0 -> +inf);
+ *      ssim  = mean over C x (H-10) x (W-10) valid window centres of the Gaussian(11, 1.5) SSIM map with
+ *              r = max(max p - min p, max t - min t), c1 = (0.01 r)^2, c2 = (0.03 r)^2, un-centred moments
+ *              (StructuralSimilarityIndexMeasure: reflect pad + conv + crop keeps only the valid centres);
+ *      and the min / max of p and of t.
+ *    Evaluated in fp32 with fp64 sums; per-workgroup partials are reduced in a fixed order (no atomics), and the
+ *    partition depends on (channels, h, w) only: an image's results are bit-identical run to run and in any batch.
+ * ------------------------------------------------------------------------------------------- */
+enum { VQAE_METRIC_MSE = 0, VQAE_METRIC_HUBER = 1, VQAE_METRIC_PSNR = 2, VQAE_METRIC_SSIM = 3, VQAE_METRIC_PRED_MIN = 4,
+       VQAE_METRIC_PRED_MAX = 5, VQAE_METRIC_TARGET_MIN = 6, VQAE_METRIC_TARGET_MAX = 7, VQAE_METRICS_K = 8 };
+/* Bytes of scratch vqae_recon_metrics_f32 needs (0 for an empty batch or an image under 11 x 11). */
+size_t vqae_recon_metrics_workspace_bytes(int batch, int channels, int h, int w);
+/*   pred_dev      [B][C][H][W] (layout VQAE_LAYOUT_NCHW) or [B][H][W][C] (VQAE_LAYOUT_NHWC), fp32
+ *   target_dev    fp32 in the same layout, or NULL;
+ *   target_u8_dev uint8 NHWC [B][H][W][3] normalised on the fly, (u - mean255[c]) * inv_std255[c] as
+ *                 vqae_conv3x3_direct_f32 does (host arrays of 3; NULL -> 0 / 1), or NULL -- exactly one of the two;
+ *   huber_delta   HuberLoss delta (loss_f/huber.yaml: 1.0);
+ *   out_dev       double [B][VQAE_METRICS_K], indexed by VQAE_METRIC_*;
+ *   workspace_dev vqae_recon_metrics_workspace_bytes(B, C, H, W) bytes.
+ * Errors: null pointers / both or neither target / bad layout / delta <= 0 -> VQAE_ERR_INVALID; H < 11 or W < 11 ->
+ * VQAE_ERR_VALUE; a uint8 target with C != 3, B > 65535 -> VQAE_ERR_UNSUPPORTED.  Both targets constant (r = 0):
+ * c1 = c2 = 0 and SSIM is 0/0, as in torchmetrics. */
+int vqae_recon_metrics_f32(const float* pred_dev, const float* target_dev, const uint8_t* target_u8_dev,
+                           const float* mean255, const float* inv_std255, int batch, int channels, int h, int w,
+                           int layout, float huber_delta, double* out_dev, void* workspace_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * 5. Measurement hook (bench.py `roofline`): time every launch of one kernel class with HIP events
  *    recorded on the launch stream.  kernel_class: 1 = trunk 3x3 circular conv (MFMA, cin >= 128; incl. its fused conv3/conv1 tail),
  *    2 = trunk 1x1 conv, 3 = VQ tier-1 argmin.  Not thread-safe; off by default.
  * ------------------------------------------------------------------------------------------- */
