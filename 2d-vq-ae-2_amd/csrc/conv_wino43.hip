@@ -23,6 +23,8 @@
 // d4 + c1 d1 + c2 d2 + c3 d3 and folds Y_a += a_a Z differ in coefficients only); xi = 0 and 5 are specialised (three rows, one Y row).
 // Tails: output rows {0, 1} of every tile (image rows {0, 1, 4, 5} of the 8) form the first 128-pixel half, rows {2, 3} the second;
 // each half is t2 -> LDS [128 px][132], conv3, epilogue, next conv1 exactly as in wino_trunk_kernel.
+// Split form (SPLIT, the default at C = 128; VQAE_W43_SPLIT=0 keeps the above): the same walk with every GEMM on the bf16 MFMA, each fp32
+// operand as three bf16 pieces and six of their nine products.
 // The same kernel serves the levels above the trunk (C = 64 on the 64-wide grid: 2 slices x 2 tile groups; C = 32 on the 128-wide
 // grid: 1 slice x 4 tile groups) and C = 256 on the code grid (8 slices, 512 threads, one workgroup per CU).
 #include "common.h"
@@ -31,6 +33,8 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 using vqae::elu_act;
 using vqae::lds_barrier;
 
@@ -41,6 +45,10 @@ struct W43K {
     const float* __restrict__ w1n;       // same, the next block's conv1 (TAIL == 2)
     float* xio;                          // [M][C] residual stream, updated in place
     float* y2;                           // [M][C] next block's t1 (TAIL == 2)
+    // split form (SPLIT): the same weights as three bf16 planes, hi + mid + lo (wino43_split_weight_kernel / split_1x1_kernel)
+    const float* __restrict__ Us;        // [36 pos][C / 32 slices][C / 32 chunks][2 blocks][3 planes][64 lanes][8 bf16]
+    const float* __restrict__ w3s;       // [C / 32 blocks][C / 16 k-slices][3 planes][64 lanes][8 bf16]
+    const float* __restrict__ w1ns;      // same, the next block's conv1 (TAIL == 2)
     int H, M;
     int stag, first_gen;                 // developer experiment (VQAE_W43_STAG, default 0 = off): delay (x 1024 cycles) of the odd-slot workgroups among the first first_gen
     float act_a, act_b, t_scale, t_b4, n_b1a, n_b1b, n_b2a, n_b2b;
@@ -67,6 +75,10 @@ template <int C_> struct W43Cfg {
     static constexpr int MI = PXH / ((NWV / WN) * 32); //        32-pixel tiles per wave (MI * NI = 4 accumulators)
     static constexpr int V_BYTES = 6 * TILES * LDT * 4, T_BYTES = PXH * LDT * 4;
     static constexpr int LDS_BYTES = V_BYTES > T_BYTES ? V_BYTES : T_BYTES;
+    // split form: V_xi as three bf16 planes per tile row (plane p at p * C), 16 bytes of padding; the tails keep T in fp32
+    static constexpr int LDVB = 3 * C + 8, KC = C / 32, KS2 = C / 16;
+    static constexpr int VS_BYTES = 6 * TILES * LDVB * 2;
+    static constexpr int LDS_SPLIT = VS_BYTES > T_BYTES ? VS_BYTES : T_BYTES;
     static_assert(TILES == 2 * TC && RP == TC && PXH / RP == 16 && MI * NI == 4, "geometry");
 };
 #ifndef W43_RD
@@ -81,6 +93,18 @@ template <int C_> struct W43Cfg {
 constexpr int EARLY = W43_EARLY;                      // input batches of the next pass requested before the fold over xi (0, 1, 2)
 constexpr int RD = W43_RD;                                // weight-fragment ring depth (k-groups of 8 MFMAs = 256 MFMA cycles each)
 constexpr int RT = 3;                                // tails: ring depth in k-slices (16 MFMAs = 1024 cycles each)
+
+// v = h0 + h1 + h2 + O(2^-24 |v|): each piece rounded to bf16 (RNE, v_cvt_pk_bf16_f32), the residuals exact in fp32.
+// bf16 x bf16 products are exact in fp32, so of the nine piece products the six of order >= 2^-18 carry the fp32 product
+// (Henry, Tang & Heinecke, ARITH 2019: "bf16x6").
+__device__ __forceinline__ void split3(const f32x4& v, bf16x4 (&h)[3]) {
+    h[0] = __builtin_convertvector(v, bf16x4);
+    const f32x4 r1 = v - __builtin_convertvector(h[0], f32x4);
+    h[1] = __builtin_convertvector(r1, bf16x4);
+    const f32x4 r2 = r1 - __builtin_convertvector(h[1], f32x4);
+    h[2] = __builtin_convertvector(r2, bf16x4);
+}
+__device__ __forceinline__ bf16x8 as_bf8(const f32x4& v) { return __builtin_bit_cast(bf16x8, v); }
 
 __device__ __forceinline__ f32x4 fma4(const f32x4& a, float s, const f32x4& c) {
     return __builtin_elementwise_fma(a, f32x4{s, s, s, s}, c);
@@ -102,12 +126,13 @@ __device__ unsigned long long* g_w43_trace = nullptr;
 
 template <int N> struct IC { static constexpr int value = N; };
 
-template <int C, int TAIL>
+template <int C, int TAIL, bool SPLIT>
 __global__ __launch_bounds__((W43Cfg<C>::NT), (W43Cfg<C>::NT == 512 ? 1 : 2))
 void wino43_trunk_kernel(const W43K p) {
     using K = W43Cfg<C>;
     constexpr int W = K::W, LDT = K::LDT, KG = K::KG, KS = K::KS, TILES = K::TILES, TC = K::TC, NS = K::NS, C4 = K::C4, RP = K::RP;
     constexpr int MI = K::MI, NI = K::NI, WN = K::WN;
+    constexpr int LDVB = K::LDVB, KC = K::KC, KS2 = K::KS2;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -182,18 +207,31 @@ void wino43_trunk_kernel(const W43K p) {
     };
     auto columns = [&](int s) __attribute__((always_inline)) {                                      // (w B)[nu] -> V[nu][tile][c]
         float* const dst = lds + (s * TC + tj) * LDT + 4 * cg;
+        __bf16* const dsb = reinterpret_cast<__bf16*>(lds) + (s * TC + tj) * LDVB + 4 * cg;
+        auto put = [&](int nu, const f32x4& v) __attribute__((always_inline)) {
+            if constexpr (SPLIT) {                                    // split once here, not after every wave's ds_read
+                bf16x4 h[3];
+                split3(v, h);
+#pragma unroll
+                for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<bf16x4*>(dsb + nu * TILES * LDVB + pl * C) = h[pl];
+            } else {
+                *reinterpret_cast<f32x4*>(dst + nu * TILES * LDT) = v;
+            }
+        };
         const f32x4 t1 = fma4(w[2], -4.f, w[4]), t2 = fma4(w[1], -4.f, w[3]);
         const f32x4 t3 = w[4] - w[2], t4 = w[3] - w[1];
-        *reinterpret_cast<f32x4*>(dst + 0 * TILES * LDT) = fma4(w[0], 4.f, fma4(w[2], -5.f, w[4]));
-        *reinterpret_cast<f32x4*>(dst + 1 * TILES * LDT) = t1 + t2;
-        *reinterpret_cast<f32x4*>(dst + 2 * TILES * LDT) = t1 - t2;
-        *reinterpret_cast<f32x4*>(dst + 3 * TILES * LDT) = fma4(t4, 2.f, t3);
-        *reinterpret_cast<f32x4*>(dst + 4 * TILES * LDT) = fma4(t4, -2.f, t3);
-        *reinterpret_cast<f32x4*>(dst + 5 * TILES * LDT) = fma4(w[1], 4.f, fma4(w[3], -5.f, w[5]));
+        put(0, fma4(w[0], 4.f, fma4(w[2], -5.f, w[4])));
+        put(1, t1 + t2);
+        put(2, t1 - t2);
+        put(3, fma4(t4, 2.f, t3));
+        put(4, fma4(t4, -2.f, t3));
+        put(5, fma4(w[1], 4.f, fma4(w[3], -5.f, w[5])));
     };
 
     // weights: this wave's 16 KiB of a position are contiguous ([k-group][block][lane][4]); positions C * C floats apart
     const float* const ub = p.U + ns * (KG * 512);                   // uniform; + 16 lane bytes per lane
+    const float* const ubs = p.Us + ns * (KC * 1536);                // split form: this wave's 24 KiB of a position
+    const __bf16* const vbs = reinterpret_cast<const __bf16*>(lds) + (16 * tg + li) * LDVB + 8 * q;   // split V fragment base
     const unsigned wl = 16u * lane;
     const float* const bfrag = lds + (16 * tg + li) * LDT + 4 * q;  // V fragment base, + nu * TILES * LDT + 16 kg
 
@@ -234,56 +272,10 @@ void wino43_trunk_kernel(const W43K p) {
         }
 #endif
         __builtin_amdgcn_sched_barrier(0);                            // (the weight loads below must not rise into the transform: registers)
-        int64_t uoff = (int64_t)xi * 6 * (C * C);
-        asm volatile("" : "+s"(uoff));                                // opaque per pass: keeps hipcc from hoisting one address pair per load out of the xi loop
-        const float* const ux = ub + uoff;
-#define WB(s) (((s) / KG) * (C * C) + 512 * ((s) % KG))
-        f32x4 wq[RD][2];
-#pragma unroll
-        for (int s = 0; s < RD; ++s) {                               // first weight fragments: in flight across the barrier
-            wq[s][0] = ldg(ux + WB(s), wl);
-            wq[s][1] = ldg(ux + WB(s) + 256, wl);
-        }
-        STAMP(1 + 5 * xi);
-#if defined(W43_PRIO) && W43_PRIO == 1
-        __builtin_amdgcn_s_setprio(0);
-#elif defined(W43_PRIO) && W43_PRIO == 2
-        __builtin_amdgcn_s_setprio(3);                               // experiment: the MFMA phase first
-#endif
-        lds_barrier();                                               // V complete
-        STAMP(2 + 5 * xi);
         f32x4 Z[4][2];
-#pragma unroll
-        for (int b = 0; b < 4; ++b) { Z[b][0] = f32x4{0.f, 0.f, 0.f, 0.f}; Z[b][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
         f32x4 acc[2][2];
-        f32x4 bq[2];
-        bq[0] = *reinterpret_cast<const f32x4*>(bfrag);
-#pragma unroll
-        for (int nu = 0; nu < 6; ++nu) {
-            const int st = nu & 1;
-            acc[st][0] = f32x4{0.f, 0.f, 0.f, 0.f};
-            acc[st][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kg = 0; kg < KG; ++kg) {
-                const int s = KG * nu + kg;
-                if (s + 1 < 6 * KG)
-                    bq[(s + 1) & 1] = *reinterpret_cast<const f32x4*>(bfrag + ((s + 1) / KG) * TILES * LDT + 16 * ((s + 1) % KG));
-                const f32x4 wa = wq[s % RD][0], wb = wq[s % RD][1];
-                if (s + RD < 6 * KG) {
-                    wq[s % RD][0] = ldg(ux + WB(s + RD), wl);
-                    wq[s % RD][1] = ldg(ux + WB(s + RD) + 256, wl);
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    acc[st][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[j], bq[s & 1][j], acc[st][0], 0, 0, 0);   // D[channel][tile]
-                    acc[st][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wb[j], bq[s & 1][j], acc[st][1], 0, 0, 0);
-#ifdef W43_ALT
-                    __builtin_amdgcn_sched_barrier(0);                // keep the two accumulators alternating: hipcc otherwise queues 4 dependent MFMAs
-#endif
-                }
-                __builtin_amdgcn_sched_barrier(0);                    // keep the prefetch distances as written
-            }
-            // fold over nu: Z[b] += A^T[b][nu] acc,  A^T = [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1]
+        // fold over nu: Z[b] += A^T[b][nu] acc,  A^T = [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1]
+        auto fold_nu = [&](int nu) __attribute__((always_inline)) {
 #pragma unroll
             for (int bl = 0; bl < 2; ++bl) {
                 if (nu == 0) Z[0][bl] = Z[0][bl] + acc[0][bl];
@@ -301,8 +293,111 @@ void wino43_trunk_kernel(const W43K p) {
             }
             if (nu == 0 || nu == 2 || nu == 4)
                 asm volatile("" : "+v"(Z[0][0]), "+v"(Z[0][1]), "+v"(Z[1][0]), "+v"(Z[1][1]), "+v"(Z[2][0]), "+v"(Z[2][1]), "+v"(Z[3][0]), "+v"(Z[3][1]));
-        }
+        };
+        if constexpr (SPLIT) {
+            // Split form: per 32-channel chunk, six v_mfma_f32_16x16x32_bf16 per block (96 cycles) replace 16 v_mfma_f32_16x16x4_f32
+            // (256 cycles).  Registers allow 32 for weights (Y, Z and the accumulators hold 176): the hi plane is double-buffered, mid and
+            // lo are used first in each chunk and re-requested for the next one right after their last use; the V planes likewise.
+            int64_t uoff = (int64_t)xi * 6 * (3 * C * C / 2);
+            asm volatile("" : "+s"(uoff));
+            const float* const ux = ubs + uoff;
+#define WS(s, bl, pl) (((s) / KC) * (3 * C * C / 2) + 1536 * ((s) % KC) + 256 * (3 * (bl) + (pl)))
+#define VB(s, pl) (*reinterpret_cast<const bf16x8*>(vbs + ((s) / KC) * TILES * LDVB + (pl) * C + 32 * ((s) % KC)))
+            f32x4 w0[2][2], w1[2], w2[2];                                // [slot][block] hi plane, [block] mid / lo planes
+#pragma unroll
+            for (int bl = 0; bl < 2; ++bl) {
+                w0[0][bl] = ldg(ux + WS(0, bl, 0), wl);
+                w1[bl] = ldg(ux + WS(0, bl, 1), wl);
+                w2[bl] = ldg(ux + WS(0, bl, 2), wl);
+                w0[1][bl] = ldg(ux + WS(1, bl, 0), wl);
+            }
+            STAMP(1 + 5 * xi);
+            lds_barrier();                                               // V complete
+            STAMP(2 + 5 * xi);
+#pragma unroll
+            for (int b = 0; b < 4; ++b) { Z[b][0] = f32x4{0.f, 0.f, 0.f, 0.f}; Z[b][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+            bf16x8 vb0 = VB(0, 0), vb1 = VB(0, 1), vb2 = VB(0, 2);
+#pragma unroll
+            for (int nu = 0; nu < 6; ++nu) {
+                const int st = nu & 1;
+                acc[st][0] = f32x4{0.f, 0.f, 0.f, 0.f};
+                acc[st][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int kc = 0; kc < KC; ++kc) {
+                    const int s = KC * nu + kc, sl = s & 1;
+                    const bool nxt = s + 1 < 6 * KC;
+#define MM(wa, vb) for (int bl = 0; bl < 2; ++bl) acc[st][bl] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf8(wa[bl]), vb, acc[st][bl], 0, 0, 0)
+                    MM(w1, vb1);                                         // a1 b1
+                    MM(w1, vb0);                                         // a1 b0
+                    if (nxt) for (int bl = 0; bl < 2; ++bl) w1[bl] = ldg(ux + WS(s + 1, bl, 1), wl);
+                    MM(w2, vb0);                                         // a2 b0
+                    if (nxt) for (int bl = 0; bl < 2; ++bl) w2[bl] = ldg(ux + WS(s + 1, bl, 2), wl);
+                    MM(w0[sl], vb2);                                     // a0 b2
+                    if (nxt) vb2 = VB(s + 1, 2);
+                    MM(w0[sl], vb1);                                     // a0 b1
+                    if (nxt) vb1 = VB(s + 1, 1);
+                    MM(w0[sl], vb0);                                     // a0 b0
+                    if (s + 2 < 6 * KC) for (int bl = 0; bl < 2; ++bl) w0[sl][bl] = ldg(ux + WS(s + 2, bl, 0), wl);
+                    if (nxt) vb0 = VB(s + 1, 0);
+#undef MM
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                fold_nu(nu);
+            }
+#undef WS
+#undef VB
+        } else {
+            int64_t uoff = (int64_t)xi * 6 * (C * C);
+            asm volatile("" : "+s"(uoff));                                // opaque per pass: keeps hipcc from hoisting one address pair per load out of the xi loop
+            const float* const ux = ub + uoff;
+#define WB(s) (((s) / KG) * (C * C) + 512 * ((s) % KG))
+            f32x4 wq[RD][2];
+#pragma unroll
+            for (int s = 0; s < RD; ++s) {                               // first weight fragments: in flight across the barrier
+                wq[s][0] = ldg(ux + WB(s), wl);
+                wq[s][1] = ldg(ux + WB(s) + 256, wl);
+            }
+            STAMP(1 + 5 * xi);
+#if defined(W43_PRIO) && W43_PRIO == 1
+            __builtin_amdgcn_s_setprio(0);
+#elif defined(W43_PRIO) && W43_PRIO == 2
+            __builtin_amdgcn_s_setprio(3);                               // experiment: the MFMA phase first
+#endif
+            lds_barrier();                                               // V complete
+            STAMP(2 + 5 * xi);
+#pragma unroll
+            for (int b = 0; b < 4; ++b) { Z[b][0] = f32x4{0.f, 0.f, 0.f, 0.f}; Z[b][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+            f32x4 bq[2];
+            bq[0] = *reinterpret_cast<const f32x4*>(bfrag);
+#pragma unroll
+            for (int nu = 0; nu < 6; ++nu) {
+                const int st = nu & 1;
+                acc[st][0] = f32x4{0.f, 0.f, 0.f, 0.f};
+                acc[st][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int kg = 0; kg < KG; ++kg) {
+                    const int s = KG * nu + kg;
+                    if (s + 1 < 6 * KG)
+                        bq[(s + 1) & 1] = *reinterpret_cast<const f32x4*>(bfrag + ((s + 1) / KG) * TILES * LDT + 16 * ((s + 1) % KG));
+                    const f32x4 wa = wq[s % RD][0], wb = wq[s % RD][1];
+                    if (s + RD < 6 * KG) {
+                        wq[s % RD][0] = ldg(ux + WB(s + RD), wl);
+                        wq[s % RD][1] = ldg(ux + WB(s + RD) + 256, wl);
+                    }
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        acc[st][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[j], bq[s & 1][j], acc[st][0], 0, 0, 0);   // D[channel][tile]
+                        acc[st][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wb[j], bq[s & 1][j], acc[st][1], 0, 0, 0);
+#ifdef W43_ALT
+                        __builtin_amdgcn_sched_barrier(0);                // keep the two accumulators alternating: hipcc otherwise queues 4 dependent MFMAs
+#endif
+                    }
+                    __builtin_amdgcn_sched_barrier(0);                    // keep the prefetch distances as written
+                }
+                fold_nu(nu);
+            }
 #undef WB
+        }
         STAMP(3 + 5 * xi);
         // the next pass's first input batches go out before the fold over xi and the barrier
         __builtin_amdgcn_sched_barrier(0);
@@ -366,7 +461,19 @@ void wino43_trunk_kernel(const W43K p) {
     float* const trow = T + tj0 * LDT + 4 * cg;
     const int ty = (16 * tg + li) / TC, tx = (16 * tg + li) % TC;
     f32x4 bt[RT][NI];
+    f32x4 bs0[2][NI], bs1[NI], bs2[NI];                              // split form: the hi plane of two k-slices, mid / lo of one
     auto tail_prefetch = [&](const float* __restrict__ wsrc) __attribute__((always_inline)) {
+        if constexpr (SPLIT) {
+            const float* b0 = wsrc + (wn * NI) * (KS2 * 768);
+#pragma unroll
+            for (int ni = 0; ni < NI; ++ni) {
+                bs0[0][ni] = ldg(b0 + ni * (KS2 * 768), wl);
+                bs1[ni] = ldg(b0 + ni * (KS2 * 768) + 256, wl);
+                bs2[ni] = ldg(b0 + ni * (KS2 * 768) + 512, wl);
+                bs0[1][ni] = ldg(b0 + ni * (KS2 * 768) + 768, wl);
+            }
+            return;
+        }
         const float* b0 = wsrc + (wn * NI) * (KS * 256);
 #pragma unroll
         for (int u = 0; u < RT; ++u)
@@ -374,6 +481,41 @@ void wino43_trunk_kernel(const W43K p) {
             for (int ni = 0; ni < NI; ++ni) bt[u][ni] = ldg(b0 + ni * (KS * 256) + 256 * u, wl);
     };
     f32x16 acc[MI][NI];
+    // Split form of gemm_tail: per 16-channel k-slice, each lane reads its 8 fp32 values of T per 32-pixel tile and splits them
+    // (the WN waves along the channels repeat this); six v_mfma_f32_32x32x16_bf16 per tile pair (192 cycles) replace
+    // 8 v_mfma_f32_32x32x2_f32 (512 cycles), in the order and weight ring of the main phase.  The output layout is that of the fp32 form.
+    auto gemm_tail_split = [&](const float* __restrict__ wsrc) __attribute__((always_inline)) {
+        const float* a0 = T + (wm * MI * 32 + li32) * LDT + 8 * hh;
+        const float* b0 = wsrc + (wn * NI) * (KS2 * 768);
+#pragma unroll
+        for (int ks = 0; ks < KS2; ++ks) {
+            const int sl = ks & 1;
+            bf16x8 x[MI][3];
+#pragma unroll
+            for (int mi = 0; mi < MI; ++mi) {
+                bf16x4 lo[3], hi[3];
+                split3(*reinterpret_cast<const f32x4*>(a0 + mi * 32 * LDT + 16 * ks), lo);
+                split3(*reinterpret_cast<const f32x4*>(a0 + mi * 32 * LDT + 16 * ks + 4), hi);
+#pragma unroll
+                for (int pl = 0; pl < 3; ++pl) x[mi][pl] = __builtin_shufflevector(lo[pl], hi[pl], 0, 1, 2, 3, 4, 5, 6, 7);
+            }
+#define MM(wa, pb) for (int mi = 0; mi < MI; ++mi) for (int ni = 0; ni < NI; ++ni) \
+                acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf8(wa[ni]), x[mi][pb], acc[mi][ni], 0, 0, 0)
+#define RELOAD(dst, k, pl) for (int ni = 0; ni < NI; ++ni) dst[ni] = ldg(b0 + ni * (KS2 * 768) + 768 * (k) + 256 * (pl), wl)
+            MM(bs1, 1);
+            MM(bs1, 0);
+            if (ks + 1 < KS2) RELOAD(bs1, ks + 1, 1);
+            MM(bs2, 0);
+            if (ks + 1 < KS2) RELOAD(bs2, ks + 1, 2);
+            MM(bs0[sl], 2);
+            MM(bs0[sl], 1);
+            MM(bs0[sl], 0);
+            if (ks + 2 < KS2) RELOAD(bs0[sl], ks + 2, 0);
+#undef MM
+#undef RELOAD
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
     auto gemm_tail = [&](const float* __restrict__ wsrc) __attribute__((always_inline)) {
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi)
@@ -381,6 +523,10 @@ void wino43_trunk_kernel(const W43K p) {
             for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+        if constexpr (SPLIT) {
+            gemm_tail_split(wsrc);
+            return;
+        }
         const float* a0 = T + (wm * MI * 32 + li32) * LDT + 4 * hh;
         const float* b0 = wsrc + (wn * NI) * (KS * 256);
         f32x4 a[2][MI];
@@ -437,7 +583,7 @@ void wino43_trunk_kernel(const W43K p) {
                     for (int e = 0; e < 4; ++e) o[e] = elu_act(Y[2 * hf + a2][b][bl][e] + p.act_a) + p.act_b;
                     *reinterpret_cast<f32x4*>(T + ((2 * ty + a2) * W + 4 * tx + b) * LDT + 32 * ns + 16 * bl + 4 * q) = o;
                 }
-        tail_prefetch(p.w3);
+        tail_prefetch(SPLIT ? p.w3s : p.w3);
         const int64_t pixb = ((int64_t)img * p.H + row0 + 2 * hf) * W + tj0;
         float* xr[4];
 #pragma unroll
@@ -450,13 +596,13 @@ void wino43_trunk_kernel(const W43K p) {
         STAMP(31 + 8 * hf);
         lds_barrier();                                               // t2 complete
         STAMP(32 + 8 * hf);
-        gemm_tail(p.w3);                                             // conv3
+        gemm_tail(SPLIT ? p.w3s : p.w3);                             // conv3
         STAMP(33 + 8 * hf);
         if (hf == 0) {
 #pragma unroll
             for (int i = NRES0; i < 16; ++i) res[i] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(xr[(RP * i) / W] + ((RP * i) % W) * C));
         }
-        if (TAIL == 2) tail_prefetch(p.w1n);
+        if (TAIL == 2) tail_prefetch(SPLIT ? p.w1ns : p.w1n);
         lds_barrier();                                               // every wave is done reading t2
         acc_to_lds();
         lds_barrier();
@@ -478,7 +624,7 @@ void wino43_trunk_kernel(const W43K p) {
         STAMP(35 + 8 * hf);
         if constexpr (TAIL == 2) {
             lds_barrier();
-            gemm_tail(p.w1n);                                        // next block's conv1
+            gemm_tail(SPLIT ? p.w1ns : p.w1n);                       // next block's conv1
             STAMP(36 + 8 * hf);
             lds_barrier();                                           // every wave is done reading T
             acc_to_lds();
@@ -499,25 +645,68 @@ void wino43_trunk_kernel(const W43K p) {
     }
 }
 
-// U[pos = 6 xi + nu] = (G g G^T)[xi][nu] for g = w[n][k][3][3], evaluated in fp64 and rounded once;
+// U[pos = 6 xi + nu] = (G g G^T)[xi][nu] for g = w[n][k][3][3], evaluated in fp64;
 // G = [1/4 0 0; -1/6 -1/6 -1/6; -1/6 1/6 -1/6; 1/24 1/12 1/6; 1/24 -1/12 1/6; 0 0 1]
-// -> [pos][n >> 5][k >> 4][(n >> 4) & 1][lane = ((k >> 2) & 3) * 16 + (n & 15)][k & 3]: what lane (li, q) feeds to MFMA k & 3 of the k-group.
-__global__ void wino43_weight_kernel(const float* __restrict__ w, int c, float* __restrict__ U) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;              // over n * c + k
-    if (i >= c * c) return;
+__device__ void wino43_u(const float* __restrict__ w, int64_t i, double (&u)[36]) {
     const double G[6][3] = {{0.25, 0, 0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
                             {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
     double g[3][3], t[6][3];
     for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) g[a][b] = (double)w[(int64_t)i * 9 + a * 3 + b];
+        for (int b = 0; b < 3; ++b) g[a][b] = (double)w[i * 9 + a * 3 + b];
     for (int x = 0; x < 6; ++x)
         for (int b = 0; b < 3; ++b) t[x][b] = G[x][0] * g[0][b] + G[x][1] * g[1][b] + G[x][2] * g[2][b];
+    for (int x = 0; x < 6; ++x)
+        for (int y = 0; y < 6; ++y) u[x * 6 + y] = t[x][0] * G[y][0] + t[x][1] * G[y][1] + t[x][2] * G[y][2];
+}
+
+// rounded once -> [pos][n >> 5][k >> 4][(n >> 4) & 1][lane = ((k >> 2) & 3) * 16 + (n & 15)][k & 3]: what lane (li, q) feeds to MFMA k & 3
+// of the k-group.
+__global__ void wino43_weight_kernel(const float* __restrict__ w, int c, float* __restrict__ U) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;              // over n * c + k
+    if (i >= c * c) return;
+    double u[36];
+    wino43_u(w, i, u);
     const int n = i / c, k = i % c;
     const int64_t fo = ((((int64_t)(n >> 5) * (c / 16) + (k >> 4)) * 2 + ((n >> 4) & 1)) * 64 + ((k >> 2) & 3) * 16 + (n & 15)) * 4 + (k & 3);
     const int64_t cc = (int64_t)c * c;
-    for (int x = 0; x < 6; ++x)
-        for (int y = 0; y < 6; ++y)
-            U[(x * 6 + y) * cc + fo] = (float)(t[x][0] * G[y][0] + t[x][1] * G[y][1] + t[x][2] * G[y][2]);
+    for (int x = 0; x < 36; ++x) U[x * cc + fo] = (float)u[x];
+}
+
+// v = h0 + h1 + h2 + O(2^-25 |v|), each piece bf16 (RNE), the residuals taken in fp64
+__device__ void split3_f64(double v, __bf16 (&h)[3]) {
+    for (int pl = 0; pl < 3; ++pl) {
+        h[pl] = (__bf16)(float)v;
+        v -= (double)(float)h[pl];
+    }
+}
+
+// split form: U split from the fp64 value -> [pos][n >> 5][k >> 5][(n >> 4) & 1][plane][lane = ((k >> 3) & 3) * 16 + (n & 15)][k & 7],
+// the A fragment of v_mfma_f32_16x16x32_bf16 (lane (li, q) holds row li, k = 8 q .. 8 q + 7 of the 32-channel chunk)
+__global__ void wino43_split_weight_kernel(const float* __restrict__ w, int c, __bf16* __restrict__ U) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= c * c) return;
+    double u[36];
+    wino43_u(w, i, u);
+    const int n = i / c, k = i % c;
+    const int64_t fo = (((int64_t)(n >> 5) * (c / 32) + (k >> 5)) * 2 + ((n >> 4) & 1)) * 3 * 512 + (((k >> 3) & 3) * 16 + (n & 15)) * 8 + (k & 7);
+    const int64_t cc = (int64_t)c * c;
+    for (int x = 0; x < 36; ++x) {
+        __bf16 h[3];
+        split3_f64(u[x], h);
+        for (int pl = 0; pl < 3; ++pl) U[x * 3 * cc + fo + pl * 512] = h[pl];
+    }
+}
+
+// split form of a 1x1 tail weight, packed [n][k] -> [n >> 5][k >> 4][plane][lane = ((k >> 3) & 1) * 32 + (n & 31)][k & 7]:
+// the A fragment of v_mfma_f32_32x32x16_bf16
+__global__ void split_1x1_kernel(const float* __restrict__ w, int c, __bf16* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= c * c) return;
+    const int n = i / c, k = i % c;
+    __bf16 h[3];
+    split3_f64((double)w[i], h);
+    const int64_t fo = ((int64_t)(n >> 5) * (c / 16) + (k >> 4)) * 3 * 512 + (((k >> 3) & 1) * 32 + (n & 31)) * 8 + (k & 7);
+    for (int pl = 0; pl < 3; ++pl) out[fo + pl * 512] = h[pl];
 }
 
 }  // namespace
@@ -539,6 +728,27 @@ bool wino43_enabled() {
 
 size_t wino43_weight_floats(int c) { return (size_t)36 * c * c; }
 
+// The split (bf16x6) form serves C = 128 only: C = 64 and 256 keep the fp32 matrix instruction.
+// VQAE_W43_SPLIT=0 (read once per handle) keeps it at C = 128 too.
+bool wino43_split_supported(int c) { return c == 128; }
+size_t wino43_split_weight_bytes(int c) { return (size_t)36 * c * c * 3 * 2; }
+size_t split_1x1_bytes(int c) { return (size_t)c * c * 3 * 2; }
+
+int wino43_split_weight(const float* w_oihw_dev, int c, void* U_dev, hipStream_t stream) {
+    VQAE_REQUIRE(wino43_split_supported(c), VQAE_ERR_UNSUPPORTED, "wino43_split_weight: C = %d", c);
+    wino43_split_weight_kernel<<<(unsigned)ceil_div(c * c, 256), 256, 0, stream>>>(w_oihw_dev, c, (__bf16*)U_dev);
+    VQAE_LAUNCH_CHECK();
+    return VQAE_OK;
+}
+
+// packed [c][c] 1x1 weights (device, vqae_conv_pack_weight_f32) -> the split tail fragments
+int split_1x1_weight(const float* w_packed_dev, int c, void* out_dev, hipStream_t stream) {
+    VQAE_REQUIRE(wino43_split_supported(c), VQAE_ERR_UNSUPPORTED, "split_1x1_weight: C = %d", c);
+    split_1x1_kernel<<<(unsigned)ceil_div(c * c, 256), 256, 0, stream>>>(w_packed_dev, c, (__bf16*)out_dev);
+    VQAE_LAUNCH_CHECK();
+    return VQAE_OK;
+}
+
 // w_oihw_dev [c][c][3][3] (PyTorch layout, device) -> U_dev [36][c][c] (fragment order above)
 int wino43_transform_weight(const float* w_oihw_dev, int c, float* U_dev, hipStream_t stream) {
     VQAE_REQUIRE(c == 256 || c == 128 || c == 64 || c == 32, VQAE_ERR_UNSUPPORTED, "wino43_transform_weight: C = %d", c);
@@ -547,34 +757,41 @@ int wino43_transform_weight(const float* w_oihw_dev, int c, float* U_dev, hipStr
     return VQAE_OK;
 }
 
-template <int C>
+// The dynamic-LDS limit is a per-device attribute of the function: set once per device and instantiation.
+template <int C, bool SPLIT>
 static int launch_w43(W43K& k, int64_t M, bool chain, hipStream_t stream) {
     using K = W43Cfg<C>;
-    static bool attr_set = false;
+    constexpr int lds = SPLIT ? K::LDS_SPLIT : K::LDS_BYTES;
+    static bool attr_set[64] = {};
     static int pad = 0;
-    if (!attr_set) {
+    int dev = 0;
+    VQAE_HIP_CHECK(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
 #ifdef W43_TRACE
         pad = getenv("VQAE_W43_LDS_PAD") ? atoi(getenv("VQAE_W43_LDS_PAD")) : 0;      // experiment: one workgroup per CU
 #endif
-        VQAE_HIP_CHECK(hipFuncSetAttribute((const void*)wino43_trunk_kernel<C, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS_BYTES + pad));
-        VQAE_HIP_CHECK(hipFuncSetAttribute((const void*)wino43_trunk_kernel<C, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS_BYTES + pad));
-        attr_set = true;
+        VQAE_HIP_CHECK(hipFuncSetAttribute((const void*)wino43_trunk_kernel<C, 1, SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds + pad));
+        VQAE_HIP_CHECK(hipFuncSetAttribute((const void*)wino43_trunk_kernel<C, 2, SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds + pad));
+        if (dev >= 0 && dev < 64) attr_set[dev] = true;
     }
     const unsigned grid = (unsigned)(M / (8 * K::W));
-    // executed matrix work: 36 GEMMs of K = C per 16 output pixels (K_eff = 2.25 C per pixel) + the 1x1 tails
+    // executed matrix work: 36 GEMMs of K = C per 16 output pixels (K_eff = 2.25 C per pixel) + the 1x1 tails, priced as fp32 work
+    // in both forms (the split form executes 3x these products on the bf16 pipe)
     const double flops = 2.0 * (double)M * C * (2.25 * C + C + (chain ? C : 0));
     ProfScope prof(C >= 128 ? PROF_CONV3X3_TRUNK : PROF_NONE, stream, flops);
-    if (chain) wino43_trunk_kernel<C, 2><<<grid, K::NT, K::LDS_BYTES + pad, stream>>>(k);
-    else wino43_trunk_kernel<C, 1><<<grid, K::NT, K::LDS_BYTES + pad, stream>>>(k);
+    if (chain) wino43_trunk_kernel<C, 2, SPLIT><<<grid, K::NT, lds + pad, stream>>>(k);
+    else wino43_trunk_kernel<C, 1, SPLIT><<<grid, K::NT, lds + pad, stream>>>(k);
     prof.done();
     VQAE_LAUNCH_CHECK();
     return VQAE_OK;
 }
 
 // Same contract as wino_trunk_tail (conv_wino.hip): t1 -> xio in place (+ t1_next); w3 / w1n in that file's fragment order (k-slice 8).
+// Us / w3s / w1ns non-null (all three, w1ns only when chained): the split form with those weights (wino43_split_weight, split_1x1_weight).
 int wino43_trunk_tail(const float* t1, const float* U, const float* w3, float act_a, float act_b, float t_scale, float t_b4,
                       float* xio, const float* w1n, float n_b1a, float n_b1b, float n_b2a, float n_b2b, float* t1_next,
-                      int batch, int h, int w, int c, hipStream_t stream) {
+                      int batch, int h, int w, int c, hipStream_t stream,
+                      const void* Us, const void* w3s, const void* w1ns) {
     if (batch == 0) return VQAE_OK;
     VQAE_REQUIRE(t1 && U && w3 && xio && (!w1n || t1_next), VQAE_ERR_INVALID, "wino43_trunk_tail: null pointer");
     VQAE_REQUIRE(wino43_supported(c, h, w, VQAE_DT_F32), VQAE_ERR_UNSUPPORTED, "wino43_trunk_tail: C = %d, H = %d, W = %d", c, h, w);
@@ -588,11 +805,16 @@ int wino43_trunk_tail(const float* t1, const float* U, const float* w3, float ac
     k.n_b1a = n_b1a; k.n_b1b = n_b1b; k.n_b2a = n_b2a; k.n_b2b = n_b2b;
     static const int stag = getenv("VQAE_W43_STAG") ? atoi(getenv("VQAE_W43_STAG")) : 0;
     k.stag = stag; k.first_gen = 512;
+    if (Us) {
+        VQAE_REQUIRE(wino43_split_supported(c) && w3s && (!w1n || w1ns), VQAE_ERR_INVALID, "wino43_trunk_tail: split form needs C = 128 and its three weights");
+        k.Us = (const float*)Us; k.w3s = (const float*)w3s; k.w1ns = (const float*)w1ns;
+        return launch_w43<128, true>(k, M, w1n != nullptr, stream);
+    }
     switch (c) {
-        case 256: return launch_w43<256>(k, M, w1n != nullptr, stream);
-        case 128: return launch_w43<128>(k, M, w1n != nullptr, stream);
-        case 64: return launch_w43<64>(k, M, w1n != nullptr, stream);
-        default: return launch_w43<32>(k, M, w1n != nullptr, stream);
+        case 256: return launch_w43<256, false>(k, M, w1n != nullptr, stream);
+        case 128: return launch_w43<128, false>(k, M, w1n != nullptr, stream);
+        case 64: return launch_w43<64, false>(k, M, w1n != nullptr, stream);
+        default: return launch_w43<32, false>(k, M, w1n != nullptr, stream);
     }
 }
 

@@ -30,9 +30,15 @@ bool wino43_supported(int c, int h, int w, int dtype);
 bool wino43_enabled();
 size_t wino43_weight_floats(int c);
 int wino43_transform_weight(const float* w_oihw_dev, int c, float* U_dev, hipStream_t stream);
+bool wino43_split_supported(int c);
+size_t wino43_split_weight_bytes(int c);
+size_t split_1x1_bytes(int c);
+int wino43_split_weight(const float* w_oihw_dev, int c, void* U_dev, hipStream_t stream);
+int split_1x1_weight(const float* w_packed_dev, int c, void* out_dev, hipStream_t stream);
 int wino43_trunk_tail(const float* t1, const float* U, const float* w3, float act_a, float act_b, float t_scale, float t_b4,
                       float* xio, const float* w1n, float n_b1a, float n_b1b, float n_b2a, float n_b2b, float* t1_next,
-                      int batch, int h, int w, int c, hipStream_t stream);
+                      int batch, int h, int w, int c, hipStream_t stream,
+                      const void* Us, const void* w3s, const void* w1ns);
 int wino_trunk_tail(const float* t1, const float* U, const float* w3, float act_a, float act_b, float t_scale, float t_b4,
                     float* xio, const float* w1n, float n_b1a, float n_b1b, float n_b2a, float n_b2b, float* t1_next,
                     int batch, int h, int w, int c, int dtype, hipStream_t stream);
@@ -137,6 +143,7 @@ struct Block {
     float b1a, b1b, b2a, b2b, b3a, b3b, b4, scale, b1c, b1d;
     float *w1, *w2, *w3, *wskip;          // packed, device
     float* wU43 = nullptr;                // F(4x4, 3x3)-domain conv2 weights [36][C][C] (fp32, C = 128, conv_wino43.hip)
+    void *wU43s = nullptr, *w1s = nullptr, *w3s = nullptr;   // the same and conv1 / conv3 as three bf16 planes (split form, C = 128)
     float* wU = nullptr;                  // Winograd-domain conv2 weights [16][C][C] (fp32 trunk blocks, C = 64 / 128, conv_wino.hip)
     float *w1f = nullptr, *w3f = nullptr; // conv1 / conv3 weights in MFMA fragment order for the fused tails (both trunk kernels)
     float *w2f = nullptr, *wskf = nullptr;// 'down' blocks: conv2 / skip_conv in fragment order too (down_fused.hip)
@@ -184,6 +191,7 @@ struct vqae_handle {
     bool fuse_up16 = true;                 // 'up' blocks in the autocast modes: head16 + one launch (up16.hip)
     bool fuse_up_tail = true;              // fp32 up blocks at the stem-side levels: resize + ELU + conv3 + skip in one launch
     bool use_wino = true;                  // fp32 trunk blocks (C = 128 on a 32-wide grid, C = 64 on a 64-wide one): Winograd F(2x2,3x3) conv2
+    bool w43_split = true;                 // F(4x4,3x3) trunk at C = 128: GEMMs on the bf16 MFMA with 3-way split operands (conv_wino43.hip)
     void* idx_scratch = nullptr;           // indices nobody asked for (vqae_forward with idx == NULL)
     size_t idx_scratch_bytes = 0;
     float* se_ws = nullptr;                // MBConv: SE partial sums, then the gate [B][E]
@@ -257,19 +265,20 @@ int upload_wino(vqae_handle* h, const float* host, int c, float** out) {
     return rc;
 }
 
-// conv2 weights [c][c][3][3] (host, PyTorch layout) -> F(4x4, 3x3) domain on the device (conv_wino43.hip)
-int upload_wino43(vqae_handle* h, const float* host, int c, float** out) {
+// conv2 weights [c][c][3][3] (host, PyTorch layout) -> F(4x4, 3x3) domain on the device (conv_wino43.hip); split: as three bf16 planes
+int upload_wino43(vqae_handle* h, const float* host, int c, bool split, void** out) {
     void* tmp = nullptr;
     const size_t raw = (size_t)c * c * 9 * 4;
     if (hipMalloc(&tmp, raw) != hipSuccess) return vqae::fail(VQAE_ERR_NOMEM, "hipMalloc failed");
     hipError_t e = hipMemcpy(tmp, host, raw, hipMemcpyHostToDevice);
     void* U = nullptr;
-    int rc = (e == hipSuccess) ? dev_alloc(h, vqae::wino43_weight_floats(c) * 4, &U)
+    int rc = (e == hipSuccess) ? dev_alloc(h, split ? vqae::wino43_split_weight_bytes(c) : vqae::wino43_weight_floats(c) * 4, &U)
                                : vqae::fail(VQAE_ERR_HIP, "hipMemcpy failed: %s", hipGetErrorString(e));
-    if (rc == VQAE_OK) rc = vqae::wino43_transform_weight((const float*)tmp, c, (float*)U, nullptr);
+    if (rc == VQAE_OK) rc = split ? vqae::wino43_split_weight((const float*)tmp, c, U, nullptr)
+                                  : vqae::wino43_transform_weight((const float*)tmp, c, (float*)U, nullptr);
     if (rc == VQAE_OK && hipDeviceSynchronize() != hipSuccess) rc = vqae::fail(VQAE_ERR_HIP, "winograd weight transform failed");
     (void)hipFree(tmp);
-    *out = (float*)U;
+    *out = U;
     return rc;
 }
 
@@ -296,13 +305,16 @@ int load_block(vqae_handle* h, const TensorMap& tm, const std::string& pre, int 
     if ((rc = find(tm, pre + ".branch_conv2.weight", (int64_t)b->br * b->br * k2 * k2, &p))) return rc;
     if ((rc = upload_packed(h, p, b->br, b->br, k2, &b->w2))) return rc;
     b->wU = b->wU43 = b->w1f = b->w3f = nullptr;
+    b->wU43s = b->w1s = b->w3s = nullptr;
     const bool wino = mode == MODE_SAME && cout == cin && h->use_wino &&       // conv_wino.hip: fp32 C = 32/64/128; 16-bit C = 32
                       (h->cfg.compute_dtype == VQAE_DT_F32 ? (cin == 256 || cin == 128 || cin == 64 || cin == 32) : cin == 32);
     if (wino && (rc = upload_wino(h, p, cin, &b->wU))) return rc;
     // F(4x4, 3x3) form (C = 256 / 128 on the 32-wide code grid, 64 on the 64-wide, 32 on the 128-wide level; the grid is not known
     // here, vqae::wino43_supported decides per launch and the F(2x2, 3x3) weights stay for the other grids)
     if (wino && h->cfg.compute_dtype == VQAE_DT_F32 && vqae::wino43_enabled() && vqae::wino43_supported(cin, 8, cin >= 128 ? 32 : (cin == 64 ? 64 : 128), VQAE_DT_F32) &&
-        (rc = upload_wino43(h, p, cin, &b->wU43))) return rc;
+        (rc = upload_wino43(h, p, cin, false, (void**)&b->wU43))) return rc;
+    const bool split = b->wU43 && h->w43_split && vqae::wino43_split_supported(cin);
+    if (split && (rc = upload_wino43(h, p, cin, true, &b->wU43s))) return rc;
     if ((rc = find(tm, pre + ".branch_conv3.weight", (int64_t)cout * b->br, &p))) return rc;
     if ((rc = upload_packed(h, p, cout, b->br, 1, &b->w3))) return rc;
     if (wino || (mode == MODE_SAME && (cin == 128 || cin == 64) && cout == cin)) {      // blocks that run a fused-tail kernel
@@ -311,6 +323,10 @@ int load_block(vqae_handle* h, const TensorMap& tm, const std::string& pre, int 
         if ((rc = dev_alloc(h, (size_t)cin * cin * 4, &f1)) || (rc = dev_alloc(h, (size_t)cin * cin * 4, &f3))) return rc;
         b->w1f = (float*)f1; b->w3f = (float*)f3;
         if ((rc = vqae::wino_frag_weight(b->w1, cin, sk, b->w1f, nullptr)) || (rc = vqae::wino_frag_weight(b->w3, cin, sk, b->w3f, nullptr))) return rc;
+        if (split) {
+            if ((rc = dev_alloc(h, vqae::split_1x1_bytes(cin), &b->w1s)) || (rc = dev_alloc(h, vqae::split_1x1_bytes(cin), &b->w3s))) return rc;
+            if ((rc = vqae::split_1x1_weight(b->w1, cin, b->w1s, nullptr)) || (rc = vqae::split_1x1_weight(b->w3, cin, b->w3s, nullptr))) return rc;
+        }
         VQAE_HIP_CHECK(hipDeviceSynchronize());
     }
     b->w1h = b->w2h = b->w3h = nullptr;
@@ -549,9 +565,11 @@ int run_block(vqae_handle* h, const Block& b, const Block* next, int B, int& H, 
         }
         const bool chain = next && next->mode == MODE_SAME && next->cin == b.cin && next->cout == b.cin && (!wino || next->w1f);
         if (wino && b.wU43 && vqae::wino43_supported(b.cin, H, W, g_dt)) {
+            const bool split = b.wU43s && (!chain || next->w1s);
             if ((rc = vqae::wino43_trunk_tail(P, b.wU43, b.w3f, b.b3a, b.b3b, b.scale, b.b4, X, chain ? next->w1f : nullptr,
                                               chain ? next->b1a : 0.f, chain ? next->b1b : 0.f, chain ? next->b2a : 0.f,
-                                              chain ? next->b2b : 0.f, chain ? Q : nullptr, B, H, W, b.cin, st))) return rc;
+                                              chain ? next->b2b : 0.f, chain ? Q : nullptr, B, H, W, b.cin, st,
+                                              split ? b.wU43s : nullptr, b.w3s, chain ? next->w1s : nullptr))) return rc;
             if (chain) std::swap(h->buf[1], h->buf[2]);
             h->t1_ready = chain;
             return VQAE_OK;
@@ -875,6 +893,7 @@ extern "C" int vqae_create(const vqae_config* cfg, const vqae_tensor* tensors, i
     h->fuse_trunk = !(getenv("VQAE_NO_TRUNK_FUSION") && atoi(getenv("VQAE_NO_TRUNK_FUSION")));
     h->up_conv_first = !(getenv("VQAE_NO_UP_REORDER") && atoi(getenv("VQAE_NO_UP_REORDER")));
     h->use_wino = !(getenv("VQAE_NO_WINOGRAD") && atoi(getenv("VQAE_NO_WINOGRAD")));
+    h->w43_split = !(getenv("VQAE_W43_SPLIT") && !atoi(getenv("VQAE_W43_SPLIT")));
     h->fuse_up_tail = !(getenv("VQAE_NO_UP_TAIL_FUSION") && atoi(getenv("VQAE_NO_UP_TAIL_FUSION")));
     h->fuse_down = !(getenv("VQAE_NO_DOWN_FUSION") && atoi(getenv("VQAE_NO_DOWN_FUSION")));
     h->fuse_down16 = !(getenv("VQAE_NO_DOWN16") && atoi(getenv("VQAE_NO_DOWN16")));
