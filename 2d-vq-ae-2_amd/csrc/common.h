@@ -76,24 +76,7 @@ __device__ __forceinline__ float round_dt(float v, int dt) {
 // matrix-pipe time; the previous range-reduced expm1 polynomial (19 instructions, <= 1.5 ulp relative) cost 2x more.
 // Absolute error <= ~1.2e-7 (one ulp of 1.0) -- the size of the fp32 rounding of the O(1) activations around it;
 // relative error near v -> 0- is not preserved, which no consumer of this path needs (the next op adds an O(0.05) bias).
-// VQAE_ELU_POLY=1 at compile time restores the polynomial.
 __device__ __forceinline__ float elu_act(float v) {
-#ifdef VQAE_ELU_POLY
-    const float x = fmaxf(fminf(v, 0.f), -88.f);
-    const float k = __builtin_rintf(x * 1.44269504088896341f);
-    float r = __builtin_fmaf(k, -0.693145751953125f, x);
-    r = __builtin_fmaf(k, -1.42860682030941723e-06f, r);
-    float p = 1.98412698e-04f;
-    p = __builtin_fmaf(p, r, 1.38888889e-03f);
-    p = __builtin_fmaf(p, r, 8.33333333e-03f);
-    p = __builtin_fmaf(p, r, 4.16666667e-02f);
-    p = __builtin_fmaf(p, r, 1.66666667e-01f);
-    p = __builtin_fmaf(p, r, 0.5f);
-    const float em = __builtin_fmaf(p * r, r, r);
-    const float sc = __builtin_ldexpf(1.0f, (int)k);
-    const float e = __builtin_fmaf(sc, em, sc - 1.0f);
-    return v > 0.f ? v : e;
-#else
     // ELU(v) = median(v, e^v - 1, 0): in exact arithmetic 0 <= v <= e^v - 1 for v >= 0 and v < e^v - 1 < 0 for v < 0.  Four
     // instructions (v_mul, v_exp, v_add, v_med3) instead of five for the select form.  In fp32 `e - 1` is a multiple of
     // ulp(1) = 1.19e-7, so for 0 < v < ~3.5e-4 it can round BELOW v and the median returns it instead of v (e.g.
@@ -103,7 +86,6 @@ __device__ __forceinline__ float elu_act(float v) {
     // (PMC: vector issue), hence the shorter form.
     const float e = __builtin_amdgcn_exp2f(v * 1.44269504088896341f);
     return __builtin_amdgcn_fmed3f(v, e - 1.0f, 0.0f);
-#endif
 }
 
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains the vector-memory counter
@@ -118,5 +100,11 @@ __device__ __forceinline__ void lds_barrier() {
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int64_t round_up(int64_t a, int64_t b) { return ceil_div(a, b) * b; }
+
+// hipFuncSetAttribute(kernel, MaxDynamicSharedMemorySize, bytes) on the current device, once per (kernel, device): the limit
+// is a per-device attribute of the function, and a launch with more than 64 KB of dynamic LDS fails where it was not set.
+int set_max_dynamic_lds(const void* kernel, int bytes);
+// Multiprocessor count of the current device, queried once per device (256 if the query fails).
+int cu_count();
 
 }  // namespace vqae

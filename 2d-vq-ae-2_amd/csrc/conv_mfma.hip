@@ -564,12 +564,7 @@ int launch_r(const ConvK& k, hipStream_t stream) {
     const int npad = (int)vqae::round_up(k.Cout, 32);
     dim3 grid((unsigned)vqae::ceil_div(k.M, 128), (unsigned)vqae::ceil_div(npad, NT));
     constexpr int lds_bytes = 2 * (128 + NT) * (KC + P::PAD) * (int)sizeof(typename P::elem);
-    static bool attr_set = false;
-    if (!attr_set) {
-        VQAE_HIP_CHECK(hipFuncSetAttribute((const void*)conv_mfma_kernel<NT, KC, PRE, PADZ, TAIL, DT, M16>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        attr_set = true;
-    }
+    if (int rc = vqae::set_max_dynamic_lds((const void*)conv_mfma_kernel<NT, KC, PRE, PADZ, TAIL, DT, M16>, lds_bytes)) return rc;
     const int cls = (NT == 128 && KC == 32 && k.Cin >= 128) ? (k.ks == 3 ? vqae::PROF_CONV3X3_TRUNK : (k.ks == 1 ? vqae::PROF_CONV1X1_TRUNK : 0)) : 0;
     const double flops = 2.0 * k.M * (double)k.Cout * ((double)k.Ktot + (TAIL >= 1 ? (double)k.Cout : 0.0) + (TAIL == 2 ? (double)k.Cout : 0.0));
     vqae::ProfScope prof(cls, stream, flops);

@@ -25,10 +25,11 @@
 // transforms, the other one's MFMAs run.  Then t2 = ELU(Y + b3a) + b3b goes to LDS as the [128 px][132] A operand of
 // the conv3 / next-conv1 tails.
 //
-// Measured (cfg B, batch 256, `-DVQAE_WINO_TRACE` stamps): a tile costs a wave ~98 k cycles of MFMA issue, ~10 k of VALU
-// (fold 576, ELU 1150, transforms 512 instructions ...; fp32 MFMA and VALU do not co-execute) and ~20 k of exposed
-// waits across its 14 barrier-separated phases; a lone workgroup per CU takes 154 k cycles per tile, two take 260 k for
-// two.  DESIGN.md section 4 has the roofline numbers, section 8 what would move them.
+// Measured (cfg B, batch 256, per-phase s_memtime stamps of a developer build, removed after f2b9d9d): a tile costs a wave
+// ~98 k cycles of MFMA issue, ~10 k of VALU (fold 576, ELU 1150, transforms 512 instructions ...; fp32 MFMA and VALU do not
+// co-execute) and ~20 k of exposed waits across its 14 barrier-separated phases; a lone workgroup per CU takes 154 k cycles
+// per tile, two take 260 k for two.  The same stamps placed the cost of this kernel's first version in the L1 tag pipe
+// (row-major weight fragments), not in HBM or the MFMAs.  DESIGN.md section 4 has the roofline numbers, section 8 what would move them.
 #include "common.h"
 
 namespace {
@@ -46,29 +47,13 @@ struct WinoK {
     float* y2;                           // [M][C] next block's t1 (TAIL == 2)
     int H, Wimg, M;                      // image rows / columns (Wimg a multiple of the workgroup's column span); M = B * H * Wimg
     float act_a, act_b, t_scale, t_b4, n_b1a, n_b1b, n_b2a, n_b2b;
-#ifdef VQAE_WINO_TRACE
-    unsigned long long* trace;           // [wg][4 waves][32] s_memtime stamps (developer build only)
-#endif
 };
-
-// Developer aid (off by default): per-phase s_memtime stamps of every wave -> gpurun_out/wino_trace.bin.  It showed that
-// the cost of this kernel's first version sat in the L1 tag pipe (row-major weight fragments), not in HBM or the MFMAs.
-#ifdef VQAE_WINO_TRACE
-#define STAMP(i) do { if (lane == 0 && p.trace && wave < 4) p.trace[((int64_t)blockIdx.x * 4 + wave) * 32 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define STAMP(i) do {} while (0)
-#endif
 
 constexpr int BPF = 6;                   // weight-fragment prefetch distance (k-slices)
 
 template <int C> struct WinoCfg {
-#ifdef VQAE_WINO_SMALL_WG                               // experiment: half-size workgroups (2 waves), 4 per CU, at C = 32 / 64
-    static constexpr int W = C >= 128 ? 32 : (C == 64 ? 32 : 64);
-    static constexpr int NT = C == 256 ? 512 : (C >= 128 ? 256 : 128);
-#else
     static constexpr int W = C >= 128 ? 32 : (C == 64 ? 64 : 128);   // columns a workgroup spans (the image may be k times wider)
     static constexpr int NT = C == 256 ? 512 : 256;    // threads: at C = 256 eight waves (one per 32-channel slice), one workgroup per CU
-#endif
     static constexpr int NW = NT / 64;
     static constexpr int PX = 4 * W;                   // output pixels per workgroup (4 image rows)
     static constexpr int TILES = PX / 4;               // 2x2 output tiles per workgroup
@@ -82,14 +67,10 @@ template <int C> struct WinoCfg {
     static constexpr int WN = C / (32 * NI);           //        waves along the channels, NW / WN along the pixels
     static constexpr int MI = PX / ((NW / WN) * 32);   //        32-pixel tiles per wave (MI * NI = 4 accumulators)
     static constexpr int LDS_BYTES = PX * LDT * 4;     // V[4][TILES][LDT] and T[PX][LDT] overlay each other
-#ifdef VQAE_WINO_PREF_ALL
-    static constexpr int PREF = 1;
-#else
     // C <= 64: the first half of the NEXT pass's input rows is requested before this pass's MFMAs (64 registers in flight).  These
     // levels move as many bytes per tile as C = 128 with 1/4 (C = 32) or 1/2 (C = 64) of the matrix work, and without it a tile
     // takes HBM time PLUS matrix time (round 3).  At C = 128 the same prefetch measured slower (section 4, negative results).
     static constexpr int PREF = C <= 64 ? 1 : 0;
-#endif
 };
 
 // Fragment order of a [C n][C k] matrix: element (n, k) of the 32-row tile n >> 5 and 8-wide k-slice k >> 3 goes to
@@ -216,7 +197,6 @@ void wino_trunk_kernel(const WinoK p) {
             for (int ni = 0; ni < NI; ++ni) bt[0][u][ni] = *reinterpret_cast<const f32x4*>(b0 + ni * (KS * 256) + 256 * u);
     };
 
-    STAMP(0);
     f32x16 y00, y01, y10, y11;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { y00[r] = 0.f; y01[r] = 0.f; y10[r] = 0.f; y11[r] = 0.f; }
@@ -243,7 +223,6 @@ void wino_trunk_kernel(const WinoK p) {
         for (int s = 0; s < BPF; ++s)                                  // first B fragments: in flight across the barrier
             bq[s] = *reinterpret_cast<const f32x4*>(ux + WB(s));
         __syncthreads();
-        STAMP(14 + 4 * xi);
         if (PREF && xi < 3) tr_load(xi + 1, 0);                     // in flight under this pass's MFMAs (v is dead until then)
         f32x4 aq[2];
         aq[0] = *reinterpret_cast<const f32x4*>(af);
@@ -284,7 +263,6 @@ void wino_trunk_kernel(const WinoK p) {
             // pin the fold here: left to itself the compiler defers these adds to the end of the kernel and spills
             // every (xi, nu) accumulator to scratch meanwhile
             asm volatile("" : "+v"(y00), "+v"(y01), "+v"(y10), "+v"(y11));
-            if (nu < 3) STAMP(15 + 4 * xi + nu);
         }
 #undef WB
         // Next pass's input rows are requested only now.  Requesting them under this pass's MFMAs measured SLOWER
@@ -295,7 +273,6 @@ void wino_trunk_kernel(const WinoK p) {
             if (!PREF) tr_load(xi + 1, 0);
             tr_combine(xi + 1, 0); tr_load(xi + 1, 1); tr_combine(xi + 1, 1);
         }
-        STAMP(1 + xi);
     }
 
     // ---- t2 = ELU(conv2 + b3a) + b3b -> T[pixel][channel].  The MFMAs ran with the weights as the row operand, so a
@@ -323,9 +300,7 @@ void wino_trunk_kernel(const WinoK p) {
             *reinterpret_cast<f32x4*>(d + 8 * g + (W + 1) * LDT) = o11;
         }
     }
-    STAMP(5);
     __syncthreads();
-    STAMP(6);
 
     // ---- tails: 64 px x 64 ch per wave over the PX x C tile, weight fragments straight from L2, D[channel][pixel] ------
     f32x16 acc[MI][NI];
@@ -384,12 +359,10 @@ void wino_trunk_kernel(const WinoK p) {
     float* const trow = T + tj0 * LDT + 4 * cg;                       // row-coalesced view: + (RP i) rows
 
     gemm_tail(p.w3);                                                  // conv3
-    STAMP(7);
     if (TAIL == 2) tail_prefetch(p.w1n);                              // ahead of the epilogue's stores
     __syncthreads();                                                  // every wave is done reading t2
     acc_to_lds();
     __syncthreads();
-    STAMP(8);
     // out = conv3 * scale + bias4 + x, in place over the residual stream, whole pixel rows per RP-th of a workgroup
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
@@ -404,16 +377,12 @@ void wino_trunk_kernel(const WinoK p) {
             *reinterpret_cast<f32x4*>(trow + RP * i * LDT) = t;
         }
     }
-    STAMP(9);
     if constexpr (TAIL == 2) {
         __syncthreads();
-        STAMP(10);
         gemm_tail(p.w1n);                                             // next block's conv1
-        STAMP(11);
         __syncthreads();                                              // every wave is done reading T
         acc_to_lds();
         __syncthreads();
-        STAMP(12);
         float* yr[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) yr[r] = p.y2 + (pix0 + (int64_t)r * Wimg) * C + 4 * cg;
@@ -424,7 +393,6 @@ void wino_trunk_kernel(const WinoK p) {
             for (int e = 0; e < 4; ++e) t[e] = elu_act(rnd(t[e]) + p.n_b2a) + p.n_b2b;   // next conv1 output cast
             __builtin_nontemporal_store(t, reinterpret_cast<f32x4*>(yr[(RP * i) / W] + ((RP * i) % W) * C));
         }
-        STAMP(13);
     }
 }
 
@@ -647,12 +615,8 @@ __global__ void frag_weight_kernel(const float* __restrict__ w, int c, int sk, f
 template <int C, int DT, bool WIDE>
 int launch_wino_w(const WinoK& k, bool chain, hipStream_t stream) {
     using K = WinoCfg<C>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        VQAE_HIP_CHECK(hipFuncSetAttribute((const void*)wino_trunk_kernel<C, 1, DT, WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS_BYTES));
-        VQAE_HIP_CHECK(hipFuncSetAttribute((const void*)wino_trunk_kernel<C, 2, DT, WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS_BYTES));
-        attr_set = true;
-    }
+    if (int rc = vqae::set_max_dynamic_lds((const void*)wino_trunk_kernel<C, 1, DT, WIDE>, K::LDS_BYTES)) return rc;
+    if (int rc = vqae::set_max_dynamic_lds((const void*)wino_trunk_kernel<C, 2, DT, WIDE>, K::LDS_BYTES)) return rc;
     const unsigned grid = (unsigned)(k.M / K::PX);
     // executed matrix work: 16 GEMMs of K = C per 4 output pixels (K_eff = 4 C per pixel) + the 1x1 tails
     const double flops = 2.0 * (double)k.M * C * (4.0 * C + C + (chain ? C : 0));
@@ -701,22 +665,9 @@ template <int C>
 static int launch_conv1(const float* x, const float* w1f, float pa, float pb, float aa, float ab, float* y, int64_t m,
                         hipStream_t stream) {
     using K = WinoCfg<C>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        VQAE_HIP_CHECK(hipFuncSetAttribute((const void*)fixup_conv1_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS_BYTES));
-        attr_set = true;
-    }
-    static bool attr_p = false;
-    static int n_cu = 256;
-    if (!attr_p) {
-        VQAE_HIP_CHECK(hipFuncSetAttribute((const void*)fixup_conv1p_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS_BYTES));
-        int dev = 0;
-        hipDeviceProp_t prop;
-        VQAE_HIP_CHECK(hipGetDevice(&dev));
-        VQAE_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-        if (prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
-        attr_p = true;
-    }
+    if (int rc = set_max_dynamic_lds((const void*)fixup_conv1_kernel<C>, K::LDS_BYTES)) return rc;
+    if (int rc = set_max_dynamic_lds((const void*)fixup_conv1p_kernel<C>, K::LDS_BYTES)) return rc;
+    const int n_cu = cu_count();
     // read per call (a chain head: a handful of launches per forward pass) so that tests can switch forms inside one process
     const char* e1 = getenv("VQAE_CONV1_ONESHOT");
     const char* e2 = getenv("VQAE_CONV1_PERSIST_MIN_TILES");
@@ -768,28 +719,11 @@ int wino_trunk_tail(const float* t1, const float* U, const float* w3, float act_
     k.H = h; k.Wimg = w; k.M = (int)M;
     k.act_a = act_a; k.act_b = act_b; k.t_scale = t_scale; k.t_b4 = t_b4;
     k.n_b1a = n_b1a; k.n_b1b = n_b1b; k.n_b2a = n_b2a; k.n_b2b = n_b2b;
-#ifdef VQAE_WINO_TRACE
-    static unsigned long long* trace = nullptr;
-    if (!trace) (void)hipMalloc((void**)&trace, (size_t)4096 * 128 * 8);
-    k.trace = (c == 128 && M / 128 <= 4096) ? trace : nullptr;
-#endif
-    const int rc = dtype == VQAE_DT_BF16 ? launch_wino<32, VQAE_DT_BF16>(k, w1n != nullptr, stream)
-                 : dtype == VQAE_DT_F16 ? launch_wino<32, VQAE_DT_F16>(k, w1n != nullptr, stream)
-                 : c == 256 ? launch_wino<256>(k, w1n != nullptr, stream)
-                 : c == 128 ? launch_wino<128>(k, w1n != nullptr, stream)
-                 : (c == 64 ? launch_wino<64>(k, w1n != nullptr, stream) : launch_wino<32>(k, w1n != nullptr, stream));
-#ifdef VQAE_WINO_TRACE
-    static int launches = 0;
-    if (rc == VQAE_OK && c == 128 && w1n && M / 128 == 2048 && ++launches == 200) {   // one steady-state launch of the B = 256 bench
-        (void)hipStreamSynchronize(stream);
-        unsigned long long* host = new unsigned long long[(size_t)2048 * 128];
-        (void)hipMemcpy(host, trace, (size_t)2048 * 128 * 8, hipMemcpyDeviceToHost);
-        FILE* f = fopen("gpurun_out/wino_trace.bin", "wb");
-        if (f) { fwrite(host, 8, (size_t)2048 * 128, f); fclose(f); }
-        delete[] host;
-    }
-#endif
-    return rc;
+    return dtype == VQAE_DT_BF16 ? launch_wino<32, VQAE_DT_BF16>(k, w1n != nullptr, stream)
+         : dtype == VQAE_DT_F16 ? launch_wino<32, VQAE_DT_F16>(k, w1n != nullptr, stream)
+         : c == 256 ? launch_wino<256>(k, w1n != nullptr, stream)
+         : c == 128 ? launch_wino<128>(k, w1n != nullptr, stream)
+         : (c == 64 ? launch_wino<64>(k, w1n != nullptr, stream) : launch_wino<32>(k, w1n != nullptr, stream));
 }
 
 }  // namespace vqae

@@ -25,8 +25,8 @@
 // each half is t2 -> LDS [128 px][132], conv3, epilogue, next conv1 exactly as in wino_trunk_kernel.
 // Split form (SPLIT, the default at C = 128; VQAE_W43_SPLIT=0 keeps the above): the same walk with every GEMM on the bf16 MFMA, each fp32
 // operand as three bf16 pieces and six of their nine products.
-// The same kernel serves the levels above the trunk (C = 64 on the 64-wide grid: 2 slices x 2 tile groups; C = 32 on the 128-wide
-// grid: 1 slice x 4 tile groups) and C = 256 on the code grid (8 slices, 512 threads, one workgroup per CU).
+// The same kernel serves the level above the trunk (C = 64 on the 64-wide grid: 2 slices x 2 tile groups) and C = 256 on the code
+// grid (8 slices, 512 threads, one workgroup per CU).
 #include "common.h"
 
 namespace {
@@ -50,14 +50,13 @@ struct W43K {
     const float* __restrict__ w3s;       // [C / 32 blocks][C / 16 k-slices][3 planes][64 lanes][8 bf16]
     const float* __restrict__ w1ns;      // same, the next block's conv1 (TAIL == 2)
     int H, M;
-    int stag, first_gen;                 // developer experiment (VQAE_W43_STAG, default 0 = off): delay (x 1024 cycles) of the odd-slot workgroups among the first first_gen
     float act_a, act_b, t_scale, t_b4, n_b1a, n_b1b, n_b2a, n_b2b;
 };
 
-// (C, grid width): (256, 32) [512 threads, one workgroup per CU], (128, 32), (64, 64), (32, 128): 8 image rows x the whole grid width
+// (C, grid width): (256, 32) [512 threads, one workgroup per CU], (128, 32), (64, 64): 8 image rows x the whole grid width
 template <int C_> struct W43Cfg {
     static constexpr int C = C_;
-    static constexpr int W = C >= 128 ? 32 : (C == 64 ? 64 : 128);
+    static constexpr int W = C >= 128 ? 32 : 64;
     static constexpr int NT = C == 256 ? 512 : 256;
     static constexpr int NWV = NT / 64;
     static constexpr int NS = C / 32;                  // 32-channel slices
@@ -70,7 +69,7 @@ template <int C_> struct W43Cfg {
     static constexpr int LDT = C + 4;
     static constexpr int KG = C / 16;                  // k-groups (16 channels = 4 MFMAs per block) per position
     static constexpr int KS = C / 8;                   // tails: k-slices
-    static constexpr int NI = C >= 64 ? 2 : 1;         // tails: 32-channel tiles per wave
+    static constexpr int NI = 2;                       // tails: 32-channel tiles per wave
     static constexpr int WN = C / (32 * NI);           //        waves along the channels
     static constexpr int MI = PXH / ((NWV / WN) * 32); //        32-pixel tiles per wave (MI * NI = 4 accumulators)
     static constexpr int V_BYTES = 6 * TILES * LDT * 4, T_BYTES = PXH * LDT * 4;
@@ -81,17 +80,9 @@ template <int C_> struct W43Cfg {
     static constexpr int LDS_SPLIT = VS_BYTES > T_BYTES ? VS_BYTES : T_BYTES;
     static_assert(TILES == 2 * TC && RP == TC && PXH / RP == 16 && MI * NI == 4, "geometry");
 };
-#ifndef W43_RD
-#define W43_RD 4
-#endif
-#ifndef W43_NRES0
-#define W43_NRES0 4
-#endif
-#ifndef W43_EARLY
-#define W43_EARLY 1
-#endif
-constexpr int EARLY = W43_EARLY;                      // input batches of the next pass requested before the fold over xi (0, 1, 2)
-constexpr int RD = W43_RD;                                // weight-fragment ring depth (k-groups of 8 MFMAs = 256 MFMA cycles each)
+constexpr int EARLY = 1;                             // input batches of the next pass requested before the fold over xi (0, 1, 2)
+constexpr int RD = 4;                                // weight-fragment ring depth (k-groups of 8 MFMAs = 256 MFMA cycles each)
+constexpr int NRES0 = 4;                             // tails: residual rows requested ahead of the first half's conv3
 constexpr int RT = 3;                                // tails: ring depth in k-slices (16 MFMAs = 1024 cycles each)
 
 // v = h0 + h1 + h2 + O(2^-24 |v|): each piece rounded to bf16 (RNE, v_cvt_pk_bf16_f32), the residuals exact in fp32.
@@ -116,14 +107,6 @@ __device__ __forceinline__ f32x4 ldg(const float* sbase, unsigned voff_bytes) {
     return *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(sbase) + voff_bytes);
 }
 
-// Developer aid (off by default; tools/dbg/w43_trace.py): per-phase s_memtime stamps of every wave of the chained (TAIL == 2) launches.
-#ifdef W43_TRACE
-__device__ unsigned long long* g_w43_trace = nullptr;
-#define STAMP(i) do { if (TAIL == 2 && lane == 0 && g_w43_trace) g_w43_trace[((int64_t)blockIdx.x * 8 + wave) * 64 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define STAMP(i) do {} while (0)
-#endif
-
 template <int N> struct IC { static constexpr int value = N; };
 
 template <int C, int TAIL, bool SPLIT>
@@ -140,18 +123,6 @@ void wino43_trunk_kernel(const W43K p) {
     const int li = lane & 15, q = lane >> 4;                         // main phase: tile of the group, channel quad of the 16-channel block
     const int ns = wave % NS, tg = wave / NS;                        // main phase: 32-channel slice, 16-tile group
 
-    if (p.stag > 0 && (int)blockIdx.x < p.first_gen) {
-        const unsigned slot = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 4);       // HW_ID.wave_id
-        if (slot & 1) for (int i = 0; i < p.stag; ++i) __builtin_amdgcn_s_sleep(16);
-    }
-#ifdef W43_TRACE
-    if (TAIL == 2 && lane == 0 && g_w43_trace) {
-        const unsigned hw = __builtin_amdgcn_s_getreg((15 << 11) | (0 << 6) | 4);           // HW_ID[15:0]
-        const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20);          // XCC_ID[3:0]
-        g_w43_trace[((int64_t)blockIdx.x * 8 + wave) * 64 + 63] = ((unsigned long long)xcc << 32) | hw;
-    }
-#endif
-    STAMP(0);
     int tile_m;                                                      // XCD-contiguous order (conv_wino.hip)
     {
         const int nwg = gridDim.x, bid = blockIdx.x;
@@ -188,12 +159,7 @@ void wino43_trunk_kernel(const W43K p) {
         for (int i = 0; i < (KIND == 1 ? 4 : 3); ++i) {
             const int row = KIND == 0 ? 2 * i : (KIND == 5 ? 2 * i + 1 : i + 1);
 #pragma unroll
-            for (int jj = 0; jj < 2; ++jj)
-#ifdef W43_DBG_NOLOAD
-                d[bf][i][jj] = f32x4{1.f, 2.f, (float)i, (float)tid};
-#else
-                d[bf][i][jj] = ldg(xim + roff[s][row], coff[2 * cp + jj]);
-#endif
+            for (int jj = 0; jj < 2; ++jj) d[bf][i][jj] = ldg(xim + roff[s][row], coff[2 * cp + jj]);
         }
     };
     auto combine = [&](auto kind_c, int k, float c1, float c2, float c3) __attribute__((always_inline)) {
@@ -246,23 +212,9 @@ void wino43_trunk_kernel(const W43K p) {
         constexpr int KIND = decltype(kind_c)::value;
         constexpr int NEXT = decltype(next_c)::value;                // kind of the following pass (-1: none)
         __builtin_amdgcn_sched_barrier(0);
-#if defined(W43_PRIO) && W43_PRIO == 1
-        __builtin_amdgcn_s_setprio(3);                               // experiment: the short load / vector phases ahead of the partner's MFMA stream
-#elif defined(W43_PRIO) && W43_PRIO == 2
-        __builtin_amdgcn_s_setprio(0);
-#endif
 #pragma unroll
         for (int j = 0; j < 6; ++j) asm volatile("" : "+v"(coff[j]));    // opaque per pass (as uoff below): no hoisted 64-bit address per (row, column)
         if (EARLY < 1) issue(kind_c, 0);                             // (EARLY batches of this pass went out before the previous pass's fold)
-#ifdef W43_SERIAL
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            if (k > 0) issue(kind_c, k);
-            combine(kind_c, k, c1, c2, c3);
-            if (k % 3 == 2) columns(k / 3);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#else
         if (EARLY < 2) issue(kind_c, 1);
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
@@ -270,7 +222,6 @@ void wino43_trunk_kernel(const W43K p) {
             if (k % 3 == 2) columns(k / 3);                          // before the next request: w, the column temporaries and TWO batches in flight do not fit
             if (k + 2 < 6) issue(kind_c, k + 2);
         }
-#endif
         __builtin_amdgcn_sched_barrier(0);                            // (the weight loads below must not rise into the transform: registers)
         f32x4 Z[4][2];
         f32x4 acc[2][2];
@@ -311,9 +262,7 @@ void wino43_trunk_kernel(const W43K p) {
                 w2[bl] = ldg(ux + WS(0, bl, 2), wl);
                 w0[1][bl] = ldg(ux + WS(1, bl, 0), wl);
             }
-            STAMP(1 + 5 * xi);
             lds_barrier();                                               // V complete
-            STAMP(2 + 5 * xi);
 #pragma unroll
             for (int b = 0; b < 4; ++b) { Z[b][0] = f32x4{0.f, 0.f, 0.f, 0.f}; Z[b][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
             bf16x8 vb0 = VB(0, 0), vb1 = VB(0, 1), vb2 = VB(0, 2);
@@ -357,14 +306,7 @@ void wino43_trunk_kernel(const W43K p) {
                 wq[s][0] = ldg(ux + WB(s), wl);
                 wq[s][1] = ldg(ux + WB(s) + 256, wl);
             }
-            STAMP(1 + 5 * xi);
-#if defined(W43_PRIO) && W43_PRIO == 1
-            __builtin_amdgcn_s_setprio(0);
-#elif defined(W43_PRIO) && W43_PRIO == 2
-            __builtin_amdgcn_s_setprio(3);                               // experiment: the MFMA phase first
-#endif
             lds_barrier();                                               // V complete
-            STAMP(2 + 5 * xi);
 #pragma unroll
             for (int b = 0; b < 4; ++b) { Z[b][0] = f32x4{0.f, 0.f, 0.f, 0.f}; Z[b][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
             f32x4 bq[2];
@@ -388,9 +330,6 @@ void wino43_trunk_kernel(const W43K p) {
                     for (int j = 0; j < 4; ++j) {
                         acc[st][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[j], bq[s & 1][j], acc[st][0], 0, 0, 0);   // D[channel][tile]
                         acc[st][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wb[j], bq[s & 1][j], acc[st][1], 0, 0, 0);
-#ifdef W43_ALT
-                        __builtin_amdgcn_sched_barrier(0);                // keep the two accumulators alternating: hipcc otherwise queues 4 dependent MFMAs
-#endif
                     }
                     __builtin_amdgcn_sched_barrier(0);                    // keep the prefetch distances as written
                 }
@@ -398,7 +337,6 @@ void wino43_trunk_kernel(const W43K p) {
             }
 #undef WB
         }
-        STAMP(3 + 5 * xi);
         // the next pass's first input batches go out before the fold over xi and the barrier
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (NEXT == 9) {                                   // inside the xi = 1..4 loop: rows (1, 2, 3, 4) of pass xi + 1 <= 4, rows (1, 3, 5, -) of pass 5
@@ -428,15 +366,7 @@ void wino43_trunk_kernel(const W43K p) {
                     Y[3][b][bl] = fma4(Z[b][bl], a3, Y[3][b][bl]);
                 }
             }
-#ifdef W43_PIN_Y
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) asm volatile("" : "+v"(Y[a][b][0]), "+v"(Y[a][b][1]));
-#endif
-        STAMP(4 + 5 * xi);
         lds_barrier();                                               // every wave is done reading V of this pass
-        STAMP(5 + 5 * xi);
     };
 
     if (EARLY >= 1) issue(IC<0>{}, 0);
@@ -590,14 +520,10 @@ void wino43_trunk_kernel(const W43K p) {
         for (int r = 0; r < 4; ++r) xr[r] = p.xio + (pixb + (int64_t)(4 * (r >> 1) + (r & 1)) * W) * C + 4 * cg;
         // residual rows: requested ahead of conv3 -- in the first half only half of them (the second half's Y is still live: registers)
         f32x4 res[16];
-        constexpr int NRES0 = W43_NRES0;
 #pragma unroll
         for (int i = 0; i < (hf == 0 ? NRES0 : 16); ++i) res[i] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(xr[(RP * i) / W] + ((RP * i) % W) * C));
-        STAMP(31 + 8 * hf);
         lds_barrier();                                               // t2 complete
-        STAMP(32 + 8 * hf);
         gemm_tail(SPLIT ? p.w3s : p.w3);                             // conv3
-        STAMP(33 + 8 * hf);
         if (hf == 0) {
 #pragma unroll
             for (int i = NRES0; i < 16; ++i) res[i] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(xr[(RP * i) / W] + ((RP * i) % W) * C));
@@ -606,7 +532,6 @@ void wino43_trunk_kernel(const W43K p) {
         lds_barrier();                                               // every wave is done reading t2
         acc_to_lds();
         lds_barrier();
-        STAMP(34 + 8 * hf);
         // out = conv3 * scale + bias4 + x, in place over the residual stream, whole pixel rows per 8th of a workgroup
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -621,11 +546,9 @@ void wino43_trunk_kernel(const W43K p) {
                 *reinterpret_cast<f32x4*>(trow + RP * i * LDT) = t;
             }
         }
-        STAMP(35 + 8 * hf);
         if constexpr (TAIL == 2) {
             lds_barrier();
             gemm_tail(SPLIT ? p.w1ns : p.w1n);                       // next block's conv1
-            STAMP(36 + 8 * hf);
             lds_barrier();                                           // every wave is done reading T
             acc_to_lds();
             lds_barrier();
@@ -639,9 +562,7 @@ void wino43_trunk_kernel(const W43K p) {
                 __builtin_nontemporal_store(t, reinterpret_cast<f32x4*>(y0 + ((4 * (r >> 1) + (r & 1)) * W + (RP * i) % W) * C));
             }
         }
-        STAMP(37 + 8 * hf);
         if (hf == 0) lds_barrier();                                  // T is rewritten by the second half's t2
-        STAMP(38 + 8 * hf);
     }
 }
 
@@ -715,10 +636,9 @@ namespace vqae {
 
 // geometry only; whether a handle uses this form at all is decided when it is created (VQAE_WINO43=0: F(2x2, 3x3) everywhere)
 bool wino43_supported(int c, int h, int w, int dtype) {
-    // C = 32 on the 128-wide grid compiles and is correct (VQAE_WINO43_C32=1), but that level is bound by vector issue: the 30 % fewer
-    // MFMAs buy nothing there (675 us either way), so it keeps F(2x2, 3x3) and its smaller rounding error
-    static const bool c32 = getenv("VQAE_WINO43_C32") && atoi(getenv("VQAE_WINO43_C32"));
-    const bool cw = (c == 256 && w == 32) || (c == 128 && w == 32) || (c == 64 && w == 64) || (c32 && c == 32 && w == 128);
+    // C = 32 on the 128-wide grid keeps F(2x2, 3x3) and its smaller rounding error: that level is bound by HBM and vector issue,
+    // and the 30 % fewer MFMAs of F(4x4, 3x3) bought nothing there (675 us either way)
+    const bool cw = (c == 256 && w == 32) || (c == 128 && w == 32) || (c == 64 && w == 64);
     return dtype == VQAE_DT_F32 && cw && h >= 8 && h % 8 == 0;
 }
 bool wino43_enabled() {
@@ -751,36 +671,25 @@ int split_1x1_weight(const float* w_packed_dev, int c, void* out_dev, hipStream_
 
 // w_oihw_dev [c][c][3][3] (PyTorch layout, device) -> U_dev [36][c][c] (fragment order above)
 int wino43_transform_weight(const float* w_oihw_dev, int c, float* U_dev, hipStream_t stream) {
-    VQAE_REQUIRE(c == 256 || c == 128 || c == 64 || c == 32, VQAE_ERR_UNSUPPORTED, "wino43_transform_weight: C = %d", c);
+    VQAE_REQUIRE(c == 256 || c == 128 || c == 64, VQAE_ERR_UNSUPPORTED, "wino43_transform_weight: C = %d", c);
     wino43_weight_kernel<<<(unsigned)ceil_div(c * c, 256), 256, 0, stream>>>(w_oihw_dev, c, U_dev);
     VQAE_LAUNCH_CHECK();
     return VQAE_OK;
 }
 
-// The dynamic-LDS limit is a per-device attribute of the function: set once per device and instantiation.
 template <int C, bool SPLIT>
 static int launch_w43(W43K& k, int64_t M, bool chain, hipStream_t stream) {
     using K = W43Cfg<C>;
     constexpr int lds = SPLIT ? K::LDS_SPLIT : K::LDS_BYTES;
-    static bool attr_set[64] = {};
-    static int pad = 0;
-    int dev = 0;
-    VQAE_HIP_CHECK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-#ifdef W43_TRACE
-        pad = getenv("VQAE_W43_LDS_PAD") ? atoi(getenv("VQAE_W43_LDS_PAD")) : 0;      // experiment: one workgroup per CU
-#endif
-        VQAE_HIP_CHECK(hipFuncSetAttribute((const void*)wino43_trunk_kernel<C, 1, SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds + pad));
-        VQAE_HIP_CHECK(hipFuncSetAttribute((const void*)wino43_trunk_kernel<C, 2, SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds + pad));
-        if (dev >= 0 && dev < 64) attr_set[dev] = true;
-    }
+    if (int rc = set_max_dynamic_lds((const void*)wino43_trunk_kernel<C, 1, SPLIT>, lds)) return rc;
+    if (int rc = set_max_dynamic_lds((const void*)wino43_trunk_kernel<C, 2, SPLIT>, lds)) return rc;
     const unsigned grid = (unsigned)(M / (8 * K::W));
     // executed matrix work: 36 GEMMs of K = C per 16 output pixels (K_eff = 2.25 C per pixel) + the 1x1 tails, priced as fp32 work
     // in both forms (the split form executes 3x these products on the bf16 pipe)
     const double flops = 2.0 * (double)M * C * (2.25 * C + C + (chain ? C : 0));
     ProfScope prof(C >= 128 ? PROF_CONV3X3_TRUNK : PROF_NONE, stream, flops);
-    if (chain) wino43_trunk_kernel<C, 2, SPLIT><<<grid, K::NT, lds + pad, stream>>>(k);
-    else wino43_trunk_kernel<C, 1, SPLIT><<<grid, K::NT, lds + pad, stream>>>(k);
+    if (chain) wino43_trunk_kernel<C, 2, SPLIT><<<grid, K::NT, lds, stream>>>(k);
+    else wino43_trunk_kernel<C, 1, SPLIT><<<grid, K::NT, lds, stream>>>(k);
     prof.done();
     VQAE_LAUNCH_CHECK();
     return VQAE_OK;
@@ -803,8 +712,6 @@ int wino43_trunk_tail(const float* t1, const float* U, const float* w3, float ac
     k.H = h; k.M = (int)M;
     k.act_a = act_a; k.act_b = act_b; k.t_scale = t_scale; k.t_b4 = t_b4;
     k.n_b1a = n_b1a; k.n_b1b = n_b1b; k.n_b2a = n_b2a; k.n_b2b = n_b2b;
-    static const int stag = getenv("VQAE_W43_STAG") ? atoi(getenv("VQAE_W43_STAG")) : 0;
-    k.stag = stag; k.first_gen = 512;
     if (Us) {
         VQAE_REQUIRE(wino43_split_supported(c) && w3s && (!w1n || w1ns), VQAE_ERR_INVALID, "wino43_trunk_tail: split form needs C = 128 and its three weights");
         k.Us = (const float*)Us; k.w3s = (const float*)w3s; k.w1ns = (const float*)w1ns;
@@ -813,15 +720,8 @@ int wino43_trunk_tail(const float* t1, const float* U, const float* w3, float ac
     switch (c) {
         case 256: return launch_w43<256, false>(k, M, w1n != nullptr, stream);
         case 128: return launch_w43<128, false>(k, M, w1n != nullptr, stream);
-        case 64: return launch_w43<64, false>(k, M, w1n != nullptr, stream);
-        default: return launch_w43<32, false>(k, M, w1n != nullptr, stream);
+        default: return launch_w43<64, false>(k, M, w1n != nullptr, stream);
     }
 }
 
 }  // namespace vqae
-
-#ifdef W43_TRACE
-extern "C" int vqae_debug_w43_trace(void* dev_buf) {
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_w43_trace), &dev_buf, sizeof(dev_buf)) == hipSuccess ? 0 : -3;
-}
-#endif

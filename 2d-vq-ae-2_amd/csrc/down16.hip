@@ -262,11 +262,7 @@ template <int CI, int DT>
 int launch_down16(const Down16K& k, int64_t n_tiles, hipStream_t stream) {
     constexpr int CO = 2 * CI, TPX = 4096 / (CO < 32 ? 32 : CO);
     constexpr int lds_bytes = TPX * ((4 * CO * 2 + 16) + (CO * 2 + 16));
-    static bool attr_set = false;
-    if (!attr_set) {
-        VQAE_HIP_CHECK(hipFuncSetAttribute((const void*)down16_kernel<CI, DT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        attr_set = true;
-    }
+    if (int rc = vqae::set_max_dynamic_lds((const void*)down16_kernel<CI, DT>, lds_bytes)) return rc;
     down16_kernel<CI, DT><<<(unsigned)n_tiles, 256, lds_bytes, stream>>>(k);
     VQAE_LAUNCH_CHECK();
     return VQAE_OK;

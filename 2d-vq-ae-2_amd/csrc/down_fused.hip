@@ -229,11 +229,7 @@ template <int CI, int DT>
 int launch_down_dt(const DownK& k, int64_t n_tiles, hipStream_t stream) {
     constexpr int CO = 2 * CI, TPX = 4096 / CO;
     constexpr int lds_bytes = TPX * (4 * CO + 4) * 4;
-    static bool attr_set = false;
-    if (!attr_set) {
-        VQAE_HIP_CHECK(hipFuncSetAttribute((const void*)down_block_kernel<CI, DT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        attr_set = true;
-    }
+    if (int rc = vqae::set_max_dynamic_lds((const void*)down_block_kernel<CI, DT>, lds_bytes)) return rc;
     down_block_kernel<CI, DT><<<(unsigned)n_tiles, 256, lds_bytes, stream>>>(k);
     VQAE_LAUNCH_CHECK();
     return VQAE_OK;

@@ -207,12 +207,7 @@ template <int C, int TH, bool R16>
 int launch_fused_r(FusedP& p, hipStream_t stream) {
     using K = FusedCfg<C, TH>;
     constexpr int lds_bytes = K::LDS_FLOATS * (int)sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-        VQAE_HIP_CHECK(hipFuncSetAttribute((const void*)fixup_same_small_kernel<C, TH, R16>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        attr_set = true;
-    }
+    if (int rc = vqae::set_max_dynamic_lds((const void*)fixup_same_small_kernel<C, TH, R16>, lds_bytes)) return rc;
     p.tiles_x = p.W / 32;
     p.tiles_y = p.H / TH;
     p.n_tiles = p.B * p.tiles_x * p.tiles_y;
@@ -229,7 +224,8 @@ int launch_fused_r(FusedP& p, hipStream_t stream) {
 // D: col = l&15, row = 4*(l>>4) + reg).  A 16-wide N tile wastes nothing at C = 16 (the 32x32x2 form
 // pads N to 32: half the matrix work and half of every epilogue lane were idle) and half at C = 8.
 // Lane (i, q) reads KQ = C/4 consecutive channels at KQ*q and feeds them to KQ MFMAs; the k-th
-// MFMA sums channels {KQ*q' + k : q' = 0..3}, identically permuted for A and B.
+// MFMA sums channels {KQ*q' + k : q' = 0..3}, identically permuted for A and B.  Launched at C = 16 (the 16-bit modes
+// and VQAE_NO_WINO16); C = 8 runs on the VALU kernel below, which measured faster.
 // ------------------------------------------------------------------------------------------------
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -389,12 +385,7 @@ template <int C, int TH, bool R16>
 int launch_tiny_r(FusedP& p, hipStream_t stream) {
     using K = FusedCfg<C, TH>;
     constexpr int lds_bytes = K::LDS_FLOATS_TINY * (int)sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-        VQAE_HIP_CHECK(hipFuncSetAttribute((const void*)fixup_same_tiny_kernel<C, TH, R16>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        attr_set = true;
-    }
+    if (int rc = vqae::set_max_dynamic_lds((const void*)fixup_same_tiny_kernel<C, TH, R16>, lds_bytes)) return rc;
     p.tiles_x = p.W / 32;
     p.tiles_y = p.H / TH;
     p.n_tiles = p.B * p.tiles_x * p.tiles_y;
@@ -600,21 +591,14 @@ template <int TH>
 int launch_wino16(FusedP& p, hipStream_t stream) {
     using K = FusedCfg<16, TH>;
     constexpr int lds_bytes = (2 * 16 * K::LDT + 16 * 256 + K::HP * K::LDT) * (int)sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-        VQAE_HIP_CHECK(hipFuncSetAttribute((const void*)fixup_same_wino16_kernel<TH, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        VQAE_HIP_CHECK(hipFuncSetAttribute((const void*)fixup_same_wino16_kernel<TH, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        attr_set = true;
-    }
+    if (int rc = vqae::set_max_dynamic_lds((const void*)fixup_same_wino16_kernel<TH, true>, lds_bytes)) return rc;
     p.tiles_x = p.W / 32;
     p.tiles_y = p.H / TH;
     p.n_tiles = p.B * p.tiles_x * p.tiles_y;
-    // the next tile's halo rows are requested under this tile's conv2 / conv3 (24 registers): 0.88 -> 0.82 ms; VQAE_WINO16_NO_PF=1: without
-    static const bool pf = !(getenv("VQAE_WINO16_NO_PF") && atoi(getenv("VQAE_WINO16_NO_PF")));
     int grid = 256 * 3;
     if (grid > p.n_tiles) grid = p.n_tiles;
-    if (pf) fixup_same_wino16_kernel<TH, true><<<grid, 256, lds_bytes, stream>>>(p);
-    else fixup_same_wino16_kernel<TH, false><<<grid, 256, lds_bytes, stream>>>(p);
+    // PF: the next tile's halo rows are requested under this tile's conv2 / conv3 (24 registers): 0.88 -> 0.82 ms
+    fixup_same_wino16_kernel<TH, true><<<grid, 256, lds_bytes, stream>>>(p);
     VQAE_LAUNCH_CHECK();
     return VQAE_OK;
 }
@@ -765,13 +749,11 @@ extern "C" int vqae_fixup_same_block_f32(const float* x, float* y, const float* 
     p.b3a = scalars8[4]; p.b3b = scalars8[5]; p.b4 = scalars8[6]; p.scale = scalars8[7];
     VQAE_REQUIRE(dtype >= VQAE_DT_F32 && dtype <= VQAE_DT_F16, VQAE_ERR_INVALID, "fixup_same_block: dtype %d", dtype);
     p.dt = dtype;
-    static const bool use32 = getenv("VQAE_FUSED_32X32") && atoi(getenv("VQAE_FUSED_32X32"));
-    static const bool mfma8 = getenv("VQAE_C8_MFMA") && atoi(getenv("VQAE_C8_MFMA"));
-    if (c == 8) return use32 ? launch_fused<8, 8>(p, stream) : (mfma8 ? launch_tiny<8, 8>(p, stream) : launch_c8(p, stream));
+    if (c == 8) return launch_c8(p, stream);
     // fp32, C = 16: conv2 as Winograd F(2x2, 3x3) from registers (fixup_same_wino16_kernel); read per call so that tests can compare
     // the forms inside one process
     const char* nw = getenv("VQAE_NO_WINO16");
-    if (c == 16 && dtype == VQAE_DT_F32 && !use32 && !(nw && atoi(nw))) return launch_wino16<8>(p, stream);
-    if (c == 16) return use32 ? launch_fused<16, 8>(p, stream) : launch_tiny<16, 8>(p, stream);
+    if (c == 16 && dtype == VQAE_DT_F32 && !(nw && atoi(nw))) return launch_wino16<8>(p, stream);
+    if (c == 16) return launch_tiny<16, 8>(p, stream);
     return launch_fused<32, 4>(p, stream);
 }

@@ -9,8 +9,12 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <map>
+#include <mutex>
+#include <set>
 #include <string>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 namespace vqae {
@@ -92,6 +96,32 @@ namespace vqae {
 ProfState& prof_state() {
     static ProfState p;
     return p;
+}
+
+int set_max_dynamic_lds(const void* kernel, int bytes) {
+    static std::mutex mu;
+    static std::set<std::pair<const void*, int>> done;
+    int dev = 0;
+    VQAE_HIP_CHECK(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(mu);
+    if (done.count({kernel, dev})) return VQAE_OK;
+    VQAE_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    done.insert({kernel, dev});
+    return VQAE_OK;
+}
+
+int cu_count() {
+    static std::mutex mu;
+    static std::map<int, int> count;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 256;
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = count.find(dev);
+    if (it != count.end()) return it->second;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, dev) != hipSuccess || prop.multiProcessorCount <= 0) return 256;
+    count[dev] = prop.multiProcessorCount;
+    return prop.multiProcessorCount;
 }
 }  // namespace vqae
 

@@ -178,9 +178,6 @@ void same8_16_kernel(const S8K p) {
 //   P1  a wave per 32 halo pixels: lane (pixel, hh) loads channels 8 hh .. + 7, pre-activation, one MFMA, lane holds channels
 //       {4 hh .. + 3, 8 + 4 hh .. + 3} -> activation -> t1 (32 B per pixel) in LDS
 //   P2  as the C = 8 form with one tap per k-step (9 steps), two register quads per lane, the lane halves swap one quad each.
-#ifndef SS16_RES_UP
-#define SS16_RES_UP 1
-#endif
 struct S16K {
     const float* __restrict__ x;         // [B][H][W][C] fp32
     float* __restrict__ y;
@@ -275,17 +272,14 @@ void same_small16_kernel(const S16K p) {
         lds_barrier();
         // ---- P2: conv2 + conv3 per 32-pixel row segment ------------------------------------------------------------------------------
         // the residual rows of all four segments are requested up front (L2 hits: P1 just read them): one latency instead of four
-        constexpr bool RES_UP = SS16_RES_UP;
-        f32x4 res_all[RES_UP ? 4 : 1][NQ];
-        if (RES_UP) {
+        f32x4 res_all[4][NQ];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int mt = wave * 4 + i;
-                const int py = mt >> 1, px = (mt & 1) * 32 + li;
-                const int64_t o = (((int64_t)b * p.H + ty0 + py) * p.W + tx0 + px) * C + 4 * hh;
+        for (int i = 0; i < 4; ++i) {
+            const int mt = wave * 4 + i;
+            const int py = mt >> 1, px = (mt & 1) * 32 + li;
+            const int64_t o = (((int64_t)b * p.H + ty0 + py) * p.W + tx0 + px) * C + 4 * hh;
 #pragma unroll
-                for (int q = 0; q < NQ; ++q) res_all[i][q] = *reinterpret_cast<const f32x4*>(p.x + o + 8 * q);
-            }
+            for (int q = 0; q < NQ; ++q) res_all[i][q] = *reinterpret_cast<const f32x4*>(p.x + o + 8 * q);
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -294,7 +288,7 @@ void same_small16_kernel(const S16K p) {
             const int64_t o = (((int64_t)b * p.H + ty0 + py) * p.W + tx0 + px) * C + 4 * hh;
             f32x4 res[NQ];
 #pragma unroll
-            for (int q = 0; q < NQ; ++q) res[q] = RES_UP ? res_all[i][q] : *reinterpret_cast<const f32x4*>(p.x + o + 8 * q);
+            for (int q = 0; q < NQ; ++q) res[q] = res_all[i][q];
             f32x16 acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;

@@ -89,17 +89,6 @@ template <int C, int W, int MT> struct T16Cfg {
     static constexpr int LDS_BYTES = IMG_BYTES + NW * WM * EPI_BYTES;
 };
 
-// Developer aid (off by default; tools/t16_trace.py): per-phase s_memtime stamps of every wave.
-#ifdef VQAE_T16_TRACE
-__device__ unsigned long long* g_t16_trace = nullptr;
-__device__ int g_t16_dbg = 0;         // experiments: 1 skip the staging loads, 2 skip the residual loads, 4 skip the stores
-#define DBG(bit) (g_t16_dbg & (bit))
-#define STAMP(i) do { if (lane == 0 && g_t16_trace) g_t16_trace[((int64_t)blockIdx.x * 8 + wv) * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define STAMP(i) do {} while (0)
-#define DBG(bit) false
-#endif
-
 constexpr int NB_MAX = 8;                             // weight-fragment ring depth (k-steps in flight per wave): 8, or 6 at C = 64
 
 template <int C, int W, int MT, int DT, bool NEXT>
@@ -122,13 +111,6 @@ void trunk16_kernel(const T16K p) {
     const int m0 = (wv / NW) * MTW;                                 // first of this wave's MTW m-tiles
     const int x = lane & 31, h = lane >> 5;
 
-#ifdef VQAE_T16_TRACE
-    if (!NEXT && lane == 0 && g_t16_trace) {                        // slot 6 (unused without NEXT): where this workgroup ran
-        const unsigned hw = __builtin_amdgcn_s_getreg((15 << 11) | (0 << 6) | 4);           // HW_ID[15:0] (cu_id, sh_id, se_id in 15:8)
-        const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20);          // XCC_ID[3:0]
-        g_t16_trace[((int64_t)blockIdx.x * 8 + wv) * 8 + 6] = ((unsigned long long)xcc << 32) | hw;
-    }
-#endif
     // XCD-contiguous tile order: neighbouring row groups of an image (shared halo rows) meet in one L2 (speed only)
     int tile;
     {
@@ -142,7 +124,6 @@ void trunk16_kernel(const T16K p) {
     const int y0 = (t_in / CB) * R, x0 = (t_in % CB) * TW;
     const int64_t pix0 = ((int64_t)img * p.H + y0) * W + x0;        // first output pixel of this tile (NHWC pixel index)
     auto moff = [&](int mi) { const int g = m0 + mi; return (g / SEG) * W + (g % SEG) * 32; };   // pixel offset of the wave's m-tile mi from pix0
-    STAMP(0);
 
     // first ring of conv2 weight fragments (L2), requested ahead of the input rows
     // ---- conv2: acc[mi] (32 channels x 32 pixels) += W2[tap] (row operand, from L2) x A[tap-shifted pixels] (LDS) --------
@@ -170,8 +151,7 @@ void trunk16_kernel(const T16K p) {
                     int iy = y0 - 1 + br;
                     iy = iy < 0 ? iy + p.H : (iy >= p.H ? iy - p.H : iy);
                     const int gx = (x0 + lx - 1) & (W - 1);
-                    if (!DBG(1)) v[i] = *reinterpret_cast<const u32x4*>(src + ((int64_t)(iy * W + gx) * C * 2 + part * 16));
-                    else v[i] = u32x4{0x3c003c00u + (unsigned)c, 0x3c003c00u, 0x3c003c00u, 0x3c003c00u};
+                    v[i] = *reinterpret_cast<const u32x4*>(src + ((int64_t)(iy * W + gx) * C * 2 + part * 16));
                 }
             }
 #pragma unroll
@@ -198,7 +178,6 @@ void trunk16_kernel(const T16K p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[mi][r] = 0.f;
     lds_barrier();
-    STAMP(1);
     static_assert((3 * KS) % NB == 0, "ring depth must divide a tap row's k-steps");
     // one tap row (dy) per trip of a real loop, its 3 * KS k-steps unrolled: keeps the scheduling window (and the
     // registers the compiler spends on hoisted LDS reads) bounded.  The ring runs NB steps ahead across trips; the
@@ -246,7 +225,6 @@ void trunk16_kernel(const T16K p) {
             for (int mi = 0; mi < MTW; ++mi) acc[mi] = E::mma(wc, af[g & 1][mi], acc[mi]);
         }
     }
-    STAMP(2);
 
     // result layout: lane = pixel x of m-tile mi, register r = channel 32 wave + (r & 3) + 8 (r >> 2) + 4 h
     const int cbase = wave * 32 + 4 * h;                            // + 8 q + {0..3}
@@ -319,13 +297,10 @@ void trunk16_kernel(const T16K p) {
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
             if constexpr (EPI) xr[mi][q] = *reinterpret_cast<const f32x4*>(xlin + ((int64_t)moff(mi) + 8 * q) * (C * 4));
-            else if (!DBG(2)) xr[mi][q] = *reinterpret_cast<const f32x4*>(xrow + (int64_t)moff(mi) * C + 8 * q);
-            else xr[mi][q] = f32x4{1.f, 2.f, 3.f, (float)lane};
+            else xr[mi][q] = *reinterpret_cast<const f32x4*>(xrow + (int64_t)moff(mi) * C + 8 * q);
         }
 
-    STAMP(3);
     gemm1x1(wp3);                                                   // conv3
-    STAMP(4);
     const char* wp1 = nullptr;
     if (NEXT) wp1 = w_prefetch(p.w1nf);
 
@@ -352,7 +327,7 @@ void trunk16_kernel(const T16K p) {
                 u[e] = elu_act(v + p.n_b1a) + p.n_b1b;
             }
             if constexpr (EPI) *reinterpret_cast<f32x4*>(s_mma + 32 * q) = t;
-            else if (!DBG(4) || t[0] == 12345.f) *reinterpret_cast<f32x4*>(xrow + (int64_t)moff(mi) * C + 8 * q) = t;
+            else *reinterpret_cast<f32x4*>(xrow + (int64_t)moff(mi) * C + 8 * q) = t;
             if (NEXT) to_T(u, mi, q);
         }
         if constexpr (EPI) {
@@ -363,10 +338,8 @@ void trunk16_kernel(const T16K p) {
     };
 #pragma unroll
     for (int mi = 0; mi < MTW; ++mi) finish(mi, xr[mi]);
-    STAMP(5);
     if constexpr (NEXT) {
         gemm1x1(wp1);                                               // the next block's conv1
-        STAMP(6);
         typename E::elem* const trow = (typename E::elem*)p.t1n + (pix0 + x) * C + cbase;
         // EPI form: 16-bit rows of this wave are 64 bytes: instruction i covers pixels 16 i .. 16 i + 15 (lane L: pixel 16 i + L / 4, chunk L % 4)
         char* const tlin = (char*)((typename E::elem*)p.t1n + pix0 * C) + ((lane >> 2) * C + wave * 32) * 2 + (lane & 3) * 16;
@@ -380,7 +353,7 @@ void trunk16_kernel(const T16K p) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = elu_act(E::rnd(acc[mi][4 * q + e]) + p.n_b2a) + p.n_b2b;
                 if constexpr (EPI) *reinterpret_cast<x4*>(s_tm + 16 * q) = __builtin_convertvector(v, x4);
-                else if (!DBG(4) || v[0] == 12345.f) *reinterpret_cast<x4*>(trow + (int64_t)moff(mi) * C + 8 * q) = __builtin_convertvector(v, x4);
+                else *reinterpret_cast<x4*>(trow + (int64_t)moff(mi) * C + 8 * q) = __builtin_convertvector(v, x4);
             }
             if constexpr (EPI) {
 #pragma unroll
@@ -389,7 +362,6 @@ void trunk16_kernel(const T16K p) {
             }
         }
     }
-    STAMP(7);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -508,20 +480,12 @@ __global__ void round_pack16_kernel(const float* __restrict__ src, EL* __restric
 template <int C, int W, int MT, int DT>
 int launch_t16(const T16K& k, bool next, int64_t n_px, hipStream_t stream) {
     using K = T16Cfg<C, W, MT>;
-    static bool attr_set = false;
-    static int pad = 0;
-    if (!attr_set) {
-#ifdef VQAE_T16_TRACE
-        pad = getenv("VQAE_T16_LDS_PAD") ? atoi(getenv("VQAE_T16_LDS_PAD")) : 0;      // experiment: fewer workgroups per CU
-#endif
-        VQAE_HIP_CHECK(hipFuncSetAttribute((const void*)trunk16_kernel<C, W, MT, DT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS_BYTES + pad));
-        VQAE_HIP_CHECK(hipFuncSetAttribute((const void*)trunk16_kernel<C, W, MT, DT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS_BYTES + pad));
-        attr_set = true;
-    }
+    if (int rc = vqae::set_max_dynamic_lds((const void*)trunk16_kernel<C, W, MT, DT, false>, K::LDS_BYTES)) return rc;
+    if (int rc = vqae::set_max_dynamic_lds((const void*)trunk16_kernel<C, W, MT, DT, true>, K::LDS_BYTES)) return rc;
     const int n_tiles = (int)(n_px / (32 * MT));
     vqae::ProfScope prof(C >= 128 && W == 32 ? vqae::PROF_CONV3X3_TRUNK : 0, stream, 2.0 * (double)n_px * C * (9.0 * C + C + (next ? C : 0)));
-    if (next) trunk16_kernel<C, W, MT, DT, true><<<n_tiles, K::NT, K::LDS_BYTES + pad, stream>>>(k);
-    else trunk16_kernel<C, W, MT, DT, false><<<n_tiles, K::NT, K::LDS_BYTES + pad, stream>>>(k);
+    if (next) trunk16_kernel<C, W, MT, DT, true><<<n_tiles, K::NT, K::LDS_BYTES, stream>>>(k);
+    else trunk16_kernel<C, W, MT, DT, false><<<n_tiles, K::NT, K::LDS_BYTES, stream>>>(k);
     prof.done();
     VQAE_LAUNCH_CHECK();
     return VQAE_OK;
@@ -539,19 +503,12 @@ int launch_t16_cw(const T16K& k, bool next, int c, int w, int64_t n_px, hipStrea
     if (c == 64 && w == 128) return launch_t16<64, 128, 4, DT>(k, next, n_px, stream);
     // C <= 32: 16 m-tiles (512 pixels, 4 per wave) per workgroup where the rows allow it -- these levels are bound by the
     // latency chain of a tile (stage -> conv2 -> conv3 -> conv1'), so more pixels per wave in flight is what pays
-    // (cfg A bf16 +3.3 %, cfg B f16 encode +2.9 % over 4 m-tiles; 8: +2.2 %).  VQAE_T16_MT = 4 / 8 / 16 overrides.
-    static const int mt_small = getenv("VQAE_T16_MT") ? atoi(getenv("VQAE_T16_MT")) : 16;
-    if (mt_small == 16 && h_rows % 4 == 0) {
+    // (cfg A bf16 +3.3 %, cfg B f16 encode +2.9 % over 4 m-tiles; 8: +2.2 %).  4 m-tiles where the rows do not divide.
+    if (h_rows % 4 == 0) {
         if (c == 32 && w == 128) return launch_t16<32, 128, 16, DT>(k, next, n_px, stream);
         if (c == 32 && w == 256) return launch_t16<32, 256, 16, DT>(k, next, n_px, stream);
         if (c == 16 && w == 128) return launch_t16<16, 128, 16, DT>(k, next, n_px, stream);
         if (c == 16 && w == 256) return launch_t16<16, 256, 16, DT>(k, next, n_px, stream);
-    }
-    if (mt_small == 8 && h_rows % 2 == 0) {
-        if (c == 32 && w == 128) return launch_t16<32, 128, 8, DT>(k, next, n_px, stream);
-        if (c == 32 && w == 256) return launch_t16<32, 256, 8, DT>(k, next, n_px, stream);
-        if (c == 16 && w == 128) return launch_t16<16, 128, 8, DT>(k, next, n_px, stream);
-        if (c == 16 && w == 256) return launch_t16<16, 256, 8, DT>(k, next, n_px, stream);
     }
     if (c == 32 && w == 128) return launch_t16<32, 128, 4, DT>(k, next, n_px, stream);
     if (c == 32 && w == 256) return launch_t16<32, 256, 4, DT>(k, next, n_px, stream);
@@ -651,12 +608,3 @@ int trunk16_block(const void* t1, const void* w2f, const void* w3f, float act_a,
 }
 
 }  // namespace vqae
-
-#ifdef VQAE_T16_TRACE
-extern "C" int vqae_debug_t16_dbg(int bits) {
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_t16_dbg), &bits, sizeof(bits)) == hipSuccess ? 0 : -3;
-}
-extern "C" int vqae_debug_t16_trace(void* dev_buf) {
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_t16_trace), &dev_buf, sizeof(dev_buf)) == hipSuccess ? 0 : -3;
-}
-#endif

@@ -233,11 +233,7 @@ void up16_kernel(const Up16K p) {
 template <int C, int DT, int ROWS>
 int launch_up16(const Up16K& k, int64_t n_tiles, hipStream_t stream) {
     constexpr int lds_bytes = (ROWS / 2 + 4) * 20 * (C * 4 + 16) + 2 * 32 * ROWS * (C * 2 + 16);
-    static bool attr_set = false;
-    if (!attr_set) {
-        VQAE_HIP_CHECK(hipFuncSetAttribute((const void*)up16_kernel<C, DT, ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        attr_set = true;
-    }
+    if (int rc = vqae::set_max_dynamic_lds((const void*)up16_kernel<C, DT, ROWS>, lds_bytes)) return rc;
     up16_kernel<C, DT, ROWS><<<(unsigned)n_tiles, 256, lds_bytes, stream>>>(k);
     VQAE_LAUNCH_CHECK();
     return VQAE_OK;

@@ -359,11 +359,7 @@ template <int D, int RT>
 int launch_vqf(const VqfK& k, hipStream_t stream) {
     constexpr int XS = (3 * D + 16) * 2 + 16;
     constexpr int lds_bytes = RT * XS + RT * 4 * 2 + 4 * RT * 4 + RT * 4 * 2 + RT * 8 * 2 + VF_PCAP * 4 * 2 + 16;
-    static bool attr_set = false;
-    if (!attr_set) {
-        VQAE_HIP_CHECK(hipFuncSetAttribute((const void*)vqf_main_kernel<D, RT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        attr_set = true;
-    }
+    if (int rc = vqae::set_max_dynamic_lds((const void*)vqf_main_kernel<D, RT>, lds_bytes)) return rc;
     const unsigned grid = (unsigned)(k.n_tiles < 256 ? k.n_tiles : 256);
     vqf_main_kernel<D, RT><<<grid, 256, lds_bytes, stream>>>(k);
     VQAE_LAUNCH_CHECK();

@@ -505,15 +505,11 @@ extern "C" int vqae_vq_forward_p_f32(const float* z, const float* embed, int64_t
         VQAE_LAUNCH_CHECK();
     }
     {
-        static bool attr_set = false;
         const int td = D < VQ_TD ? D : VQ_TD;
         const size_t lds_bytes = (size_t)td * VQ_TK * sizeof(float);
-        if (!attr_set) {
-            VQAE_HIP_CHECK(hipFuncSetAttribute((const void*)vq_tier1_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, VQ_TD * VQ_TK * (int)sizeof(float)));
-            VQAE_HIP_CHECK(hipFuncSetAttribute((const void*)vq_tier1_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, VQ_TD * VQ_TK * (int)sizeof(float)));
-            VQAE_HIP_CHECK(hipFuncSetAttribute((const void*)vq_tier1_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, VQ_TD * VQ_TK * (int)sizeof(float)));
-            attr_set = true;
-        }
+        if (int rc = vqae::set_max_dynamic_lds((const void*)vq_tier1_kernel<3>, VQ_TD * VQ_TK * (int)sizeof(float))) return rc;
+        if (int rc = vqae::set_max_dynamic_lds((const void*)vq_tier1_kernel<4>, VQ_TD * VQ_TK * (int)sizeof(float))) return rc;
+        if (int rc = vqae::set_max_dynamic_lds((const void*)vq_tier1_kernel<5>, VQ_TD * VQ_TK * (int)sizeof(float))) return rc;
         // evaluation-noise bound between tier-1 sums and the reference recipe's sums; p = 5 has one more rounded product
         const float thr = ((float)(p_norm > 4 ? p_norm : 4) * (float)D + 16.0f) * 5.9604645e-8f;
         // wide codebooks: the matrix-pipe filter + exact evaluation of the survivors (vq_filter.hip); it leaves flag_count[1] != 0

@@ -221,7 +221,8 @@ void vq_proj_fused_kernel(const VqProjK p) {
 //             not a multiple of 16, or a codebook with NaN / Inf: the wave step scans every code exactly (the loop below).
 //   proj_out  out^T[16 ch][16 rows] = W_out[16 x 8] . q^T[8 x 16] per 16-channel block, bias as the accumulator's start:
 //             lane (g, r) holds 4 consecutive channels of row r -> one 16-byte store, 64 contiguous bytes per row
-// and a wave loops over steps (persistent grid) with the NEXT step's x already requested (32 registers).
+// and a wave loops over steps (persistent grid).  PF requests the NEXT step's x during the current one (32 registers); the
+// launched form (4 waves per SIMD, 512-thread workgroups) leaves it off for the more resident waves.
 constexpr int VP16_CAP = 128;                                                 // (row, code) pairs per wave step
 
 template <int C, int DT, int WPS, bool PF, int NWV>
@@ -537,26 +538,14 @@ int launch_vq_proj16(const VqProjK& k, hipStream_t stream) {
     const int n_units = (int)vqae::ceil_div(k.N, 16);
     static const bool nofilter = getenv("VQAE_VQ16_NOFILTER") && atoi(getenv("VQAE_VQ16_NOFILTER"));
     const int use_filter = !nofilter && !k.margin && k.K <= 256 && (k.K & 15) == 0;   // the margin output wants the true second best
-    // VQAE_VQ16_WPS: waves per SIMD the kernel is compiled and launched for.  3 keeps the register prefetch of the next step's
-    // rows (256-thread workgroups, 3 per CU); 4 drops it for more resident waves (512-thread workgroups, 2 per CU)
-    static const int wps = getenv("VQAE_VQ16_WPS") ? atoi(getenv("VQAE_VQ16_WPS")) : 4;
-    const int nwv = wps >= 5 ? 10 : (wps == 4 ? 8 : 4);
+    // 4 waves per SIMD: 512-thread workgroups, 2 per CU, without the register prefetch of the next step's rows
+    constexpr int nwv = 8;
     const size_t lds_bytes = ((size_t)((k.K + 3) & ~3) * PD + (size_t)C * 17 + C + 16 + 16 + (size_t)C * 9) * sizeof(float)
                              + (size_t)nwv * (16 * PD * 4 + 16 * 8 * 2 + VP16_CAP * 4 + 16) + (use_filter ? (size_t)(k.K / 16) * 1024 : 0);
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        VQAE_HIP_CHECK(hipGetDevice(&dev));
-        VQAE_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-        n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    const int wg_per_cu = std::max(1, std::min(wps >= 4 ? 2 : 3, (int)(160 * 1024 / (lds_bytes + 256))));
-    const unsigned grid = (unsigned)std::min<int64_t>(vqae::ceil_div(n_units, nwv), (int64_t)n_cu * wg_per_cu);
+    const int wg_per_cu = std::max(1, std::min(2, (int)(160 * 1024 / (lds_bytes + 256))));
+    const unsigned grid = (unsigned)std::min<int64_t>(vqae::ceil_div(n_units, nwv), (int64_t)vqae::cu_count() * wg_per_cu);
     vqae::ProfScope prof(vqae::PROF_VQ_TIER1, stream, (double)k.N * (29.0 * k.K + 4.0 * PD * k.C));
-    if (wps >= 5) vq_proj16_kernel<C, DT, 5, false, 10><<<grid, 640, lds_bytes, stream>>>(k, n_units, use_filter);
-    else if (wps == 4) vq_proj16_kernel<C, DT, 4, false, 8><<<grid, 512, lds_bytes, stream>>>(k, n_units, use_filter);
-    else vq_proj16_kernel<C, DT, 3, true, 4><<<grid, 256, lds_bytes, stream>>>(k, n_units, use_filter);
+    vq_proj16_kernel<C, DT, 4, false, nwv><<<grid, 64 * nwv, lds_bytes, stream>>>(k, n_units, use_filter);
     prof.done();
     VQAE_LAUNCH_CHECK();
     return VQAE_OK;

@@ -217,8 +217,8 @@ def test_wino43_trunk_equals_f23_and_direct(amd, oracle, monkeypatch):
     multiple of 8 rows; VQAE_WINO43=0 keeps F(2x2, 3x3), VQAE_NO_WINOGRAD=1 the direct implicit GEMM.  Same function, different fp32
     rounding -- F(4x4, 3x3)'s transforms carry entries up to 8, so its distance to the direct form is a few times F(2x2, 3x3)'s
     (DESIGN.md section 2): pre-VQ features agree to <= 1e-4 of their range after 68 blocks, indices on every row outside the rounding
-    band, the decoder output to <= 1e-6 MSE.  cfg B runs it at three levels (C = 32 on the 128-wide grid, 64 on the 64-wide, 128 on the
-    32-wide code grid); image heights 512 / 256 / 128 / 64 / 32 give grids of 64 ... 4 rows (8 rows: every row wraps; 4 rows at the code
+    band, the decoder output to <= 1e-6 MSE.  cfg B runs it at two levels (C = 64 on the 64-wide grid, 128 on the 32-wide code grid;
+    C = 32 on the 128-wide grid keeps F(2x2, 3x3)); image heights 512 / 256 / 128 / 64 / 32 give grids of 64 ... 4 rows (8 rows: every row wraps; 4 rows at the code
     grid: that level falls back to F(2x2, 3x3)), odd batches."""
     g = load_golden("model_B")
     spec, p = golden_params(oracle, "B", g)
