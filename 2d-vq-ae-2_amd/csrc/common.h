@@ -4,6 +4,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 
 #include "../../include/vqae_hip.h"
@@ -96,6 +97,14 @@ __device__ __forceinline__ void lds_barrier() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+// Environment switches (DESIGN.md lists them): the integer value of `name`, `dflt` where it is unset.  A VQAE_NO_* switch is
+// `env_int(name, 0) != 0` (off unless set non-zero); VQAE_WINO43 / VQAE_W43_SPLIT are `env_int(name, 1) != 0` (on unless =0).
+// When a switch is read -- per handle, per process (`static const`) or per call -- is the caller's choice and part of its contract.
+inline int64_t env_int(const char* name, int64_t dflt) {
+    const char* e = getenv(name);
+    return e ? atoll(e) : dflt;
 }
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }

@@ -17,14 +17,7 @@
 // ds_read_b128 fragment reads conflict-free (MI355X_MICROARCH.md §LDS).  Lane (i = l&31, h = l>>5)
 // reads 4 consecutive k at 8u + 4h and feeds them to 4 consecutive MFMAs; A and B use the same k
 // permutation, which the sum over k does not see.
-#include "common.h"
-#include <cstdlib>
-
-namespace vqae {
-bool conv_small_k_supported(const vqae_conv_args* a);
-int conv_small_k(const vqae_conv_args* a, const float* x, const float* w, const float* bias_vec, const float* residual,
-                 float* y, hipStream_t stream);
-}  // namespace vqae
+#include "kernels.h"
 
 namespace {
 
@@ -676,7 +669,7 @@ int fill_conv(const vqae_conv_args* a, const float* x, const float* w, const flo
     VQAE_REQUIRE(k.pad_mode == VQAE_PAD_ZEROS || k.pad_mode == VQAE_PAD_CIRCULAR, VQAE_ERR_INVALID,
                  "conv2d: pad_mode %d", a->pad_mode);
     k.M = (int)M; k.Ktot = a->ksize * a->ksize * a->cin;
-    static const bool no_m16 = getenv("VQAE_NO_MFMA16") && atoi(getenv("VQAE_NO_MFMA16"));
+    static const bool no_m16 = vqae::env_int("VQAE_NO_MFMA16", 0) != 0;
     const bool padz = a->pad > 0 && a->pad_mode == VQAE_PAD_ZEROS;
     k.m16 = (a->dtype != VQAE_DT_F32 && a->cin % 32 == 0 && !padz && !no_m16) ? 1 : 0;
     const int kc = k.m16 ? ((a->cin % 64 == 0) ? 64 : 32) : ((a->cin % 32 == 0) ? 32 : (a->cin % 16 == 0) ? 16 : 8);
@@ -702,7 +695,7 @@ static int conv2d_impl(const vqae_conv_args* a, const float* x, const float* gat
     int kc;
     const int rc = fill_conv(a, x, w, bias_vec, residual, y, &k, &kc);
     if (rc) return rc;
-    static const bool no_small = getenv("VQAE_NO_SMALL_K") && atoi(getenv("VQAE_NO_SMALL_K"));
+    static const bool no_small = vqae::env_int("VQAE_NO_SMALL_K", 0) != 0;
     if (!gate && !no_small && vqae::conv_small_k_supported(a))       // 8-channel level: VALU kernel at the HBM rate
         return vqae::conv_small_k(a, x, w, bias_vec, residual, y, stream);
     VQAE_REQUIRE((a->pre_mode == VQAE_PRE_CHANNEL_GATE) == (gate != nullptr), VQAE_ERR_INVALID,
@@ -725,21 +718,20 @@ extern "C" int vqae_conv2d_gated_f32(const vqae_conv_args* a, const float* x, co
 }
 
 namespace vqae {
-// k-slice width of the engine conv_trunk_tail will use for this dtype / channel count (8: fp32 MFMA, 16: 16-bit MFMA);
-// w3 / w1n must be in fragment order for that width
+bool conv_trunk_tail_channels(int c) { return c == 128 || c == 64; }
+
 int conv_tail_kslice(int dtype, int cin) {
-    static const bool no_m16 = getenv("VQAE_NO_MFMA16") && atoi(getenv("VQAE_NO_MFMA16"));
+    static const bool no_m16 = env_int("VQAE_NO_MFMA16", 0) != 0;
     return (dtype != VQAE_DT_F32 && cin % 32 == 0 && !no_m16) ? 16 : 8;
 }
 
-// Trunk Fixup block tail fusion (internal to the handle): conv2 (3x3 circular, C = 128, `a` carries its
-// geometry and its ELU epilogue) + conv3 (+ the next block's conv1 when w1n != null).
-//   t1 [M][128] -> xio [M][128] updated in place (block output) and, if w1n, t1_next [M][128].
-int conv_trunk_tail(const vqae_conv_args* a, const float* t1, const float* w2, const float* w3, float t_scale,
-                    float t_b4, float* xio, const float* w1n, float n_b1a, float n_b1b, float n_b2a, float n_b2b,
-                    float* t1_next, hipStream_t stream) {
+// Trunk Fixup block tail fusion (internal to the handle; contract in kernels.h)
+int conv_trunk_tail(const vqae_conv_args* a, const float* t1, const float* w2, const float* w3, float t_scale, float t_b4,
+                    float* xio, const NextConv1& next, hipStream_t stream) {
     if (a->batch == 0) return VQAE_OK;
-    VQAE_REQUIRE((a->cin == 128 || a->cin == 64) && a->cout == a->cin && a->ksize == 3 && a->has_act && a->pre_mode == VQAE_PRE_NONE &&
+    const float* w1n = (const float*)next.w1;
+    float* t1_next = (float*)next.t1_next;
+    VQAE_REQUIRE(conv_trunk_tail_channels(a->cin) && a->cout == a->cin && a->ksize == 3 && a->has_act && a->pre_mode == VQAE_PRE_NONE &&
                  a->pad == 1 && a->pad_mode == VQAE_PAD_CIRCULAR, VQAE_ERR_UNSUPPORTED, "conv_trunk_tail: not a trunk conv2");
     VQAE_REQUIRE(w3 && xio && (!w1n || t1_next), VQAE_ERR_INVALID, "conv_trunk_tail: null pointer");
     ConvK k;
@@ -747,7 +739,7 @@ int conv_trunk_tail(const vqae_conv_args* a, const float* t1, const float* w2, c
     const int rc = fill_conv(a, t1, w2, nullptr, xio, xio, &k, &kc);
     if (rc) return rc;
     k.w3 = w3; k.w1n = w1n; k.y2 = t1_next;
-    k.t_scale = t_scale; k.t_b4 = t_b4; k.n_b1a = n_b1a; k.n_b1b = n_b1b; k.n_b2a = n_b2a; k.n_b2b = n_b2b;
+    k.t_scale = t_scale; k.t_b4 = t_b4; k.n_b1a = next.b1a; k.n_b1b = next.b1b; k.n_b2a = next.b2a; k.n_b2b = next.b2b;
     if (a->cin == 64) {
         if (kc == 64) return w1n ? launch<64, 64, VQAE_PRE_NONE, false, 2>(k, stream) : launch<64, 64, VQAE_PRE_NONE, false, 1>(k, stream);
         return w1n ? launch<64, 32, VQAE_PRE_NONE, false, 2>(k, stream) : launch<64, 32, VQAE_PRE_NONE, false, 1>(k, stream);

@@ -30,7 +30,7 @@
 // co-execute) and ~20 k of exposed waits across its 14 barrier-separated phases; a lone workgroup per CU takes 154 k cycles
 // per tile, two take 260 k for two.  The same stamps placed the cost of this kernel's first version in the L1 tag pipe
 // (row-major weight fragments), not in HBM or the MFMAs.  DESIGN.md section 4 has the roofline numbers, section 8 what would move them.
-#include "common.h"
+#include "kernels.h"
 
 namespace {
 
@@ -637,24 +637,24 @@ int launch_wino(const WinoK& k, bool chain, hipStream_t stream) {
 
 namespace vqae {
 
-// fp32: C in {256, 128, 64, 32} on a grid whose width is a multiple of the workgroup's column span (32, 64, 128); 16-bit autocast
-// modes: C = 32 only (the wider levels have a 16-bit MFMA kernel with fused tails, conv_mfma.hip)
+// 16-bit autocast modes: C = 32 only (the wider levels have a 16-bit MFMA kernel with fused tails, trunk16.hip)
+bool wino_trunk_channels(int c, int dtype) { return dtype == VQAE_DT_F32 ? (c == 256 || c == 128 || c == 64 || c == 32) : c == 32; }
+
 bool wino_trunk_supported(int c, int h, int w, int dtype) {
-    const int span = (c == 256 || c == 128) ? 32 : (c == 64 ? WinoCfg<64>::W : (c == 32 ? WinoCfg<32>::W : 0));
-    if (span == 0 || (dtype != VQAE_DT_F32 && c != 32)) return false;
+    if (!wino_trunk_channels(c, dtype)) return false;
+    const int span = c >= 128 ? 32 : (c == 64 ? WinoCfg<64>::W : WinoCfg<32>::W);
     return w >= span && w % span == 0 && h >= 4 && h % 4 == 0;
 }
 
 size_t wino_weight_floats(int c) { return (size_t)16 * c * c; }
 
-// w_oihw_dev [c][c][3][3] (PyTorch layout, device) -> U_dev [16][c][c] (fragment order)
 int wino_transform_weight(const float* w_oihw_dev, int c, int dtype, float* U_dev, hipStream_t stream) {
     wino_weight_kernel<<<(unsigned)ceil_div(c * c, 256), 256, 0, stream>>>(w_oihw_dev, c, dtype, U_dev);
     VQAE_LAUNCH_CHECK();
     return VQAE_OK;
 }
 
-// chain-head conv1 (fixup_conv1_kernel): fp32, C in {128, 64, 32}, M a multiple of the kernel's pixel tile
+// chain-head conv1 (fixup_conv1_kernel / fixup_conv1p_kernel)
 bool fixup_conv1_supported(int c, int64_t m) {
     if (c != 256 && c != 128 && c != 64 && c != 32) return false;
     const int px = c >= 128 ? 128 : (c == 64 ? WinoCfg<64>::PX : WinoCfg<32>::PX);
@@ -669,12 +669,10 @@ static int launch_conv1(const float* x, const float* w1f, float pa, float pb, fl
     if (int rc = set_max_dynamic_lds((const void*)fixup_conv1p_kernel<C>, K::LDS_BYTES)) return rc;
     const int n_cu = cu_count();
     // read per call (a chain head: a handful of launches per forward pass) so that tests can switch forms inside one process
-    const char* e1 = getenv("VQAE_CONV1_ONESHOT");
-    const char* e2 = getenv("VQAE_CONV1_PERSIST_MIN_TILES");
-    const bool oneshot = e1 && atoi(e1);
+    const bool oneshot = env_int("VQAE_CONV1_ONESHOT", 0) != 0;
     const int64_t n_tiles = m / K::PX;
     const int wgs = (int)std::min<int64_t>((K::LDS_BYTES * 2 <= 160 * 1024 ? 2 : 1) * n_cu, n_tiles);   // resident workgroups
-    const int64_t min_tiles = e2 ? atoll(e2) : 4ll * n_cu;          // below ~2 tiles per workgroup the loop has nothing to overlap
+    const int64_t min_tiles = env_int("VQAE_CONV1_PERSIST_MIN_TILES", 4ll * n_cu);   // below ~2 tiles per workgroup the loop has nothing to overlap
     ProfScope prof(C >= 128 ? PROF_CONV1X1_TRUNK : PROF_NONE, stream, 2.0 * (double)m * C * C);
     if (oneshot || C > 128 || n_tiles < min_tiles)
         fixup_conv1_kernel<C><<<(unsigned)n_tiles, K::NT, K::LDS_BYTES, stream>>>(x, w1f, pa, pb, aa, ab, y);
@@ -696,19 +694,17 @@ int fixup_conv1(const float* x, const float* w1f, float pa, float pb, float aa, 
     return launch_conv1<32>(x, w1f, pa, pb, aa, ab, y, m, stream);
 }
 
-// packed [c][c] 1x1 weights (device) -> fragment order (device); sk = 8 (fp32 MFMA k-slice) or 16 (16-bit MFMA)
 int wino_frag_weight(const float* w_packed_dev, int c, int sk, float* out_dev, hipStream_t stream) {
     frag_weight_kernel<<<(unsigned)ceil_div(c * c, 256), 256, 0, stream>>>(w_packed_dev, c, sk, out_dev);
     VQAE_LAUNCH_CHECK();
     return VQAE_OK;
 }
 
-// Same contract as conv_trunk_tail (conv_mfma.hip), fp32, (C, W) in {(128, 32), (64, 64), (32, 128)}: t1 -> xio in place (+ t1_next).
-// U, w3, w1n in fragment order.
 int wino_trunk_tail(const float* t1, const float* U, const float* w3, float act_a, float act_b, float t_scale, float t_b4,
-                    float* xio, const float* w1n, float n_b1a, float n_b1b, float n_b2a, float n_b2b, float* t1_next,
-                    int batch, int h, int w, int c, int dtype, hipStream_t stream) {
+                    float* xio, const NextConv1& next, int batch, int h, int w, int c, int dtype, hipStream_t stream) {
     if (batch == 0) return VQAE_OK;
+    const float* w1n = (const float*)next.w1;
+    float* t1_next = (float*)next.t1_next;
     VQAE_REQUIRE(t1 && U && w3 && xio && (!w1n || t1_next), VQAE_ERR_INVALID, "wino_trunk_tail: null pointer");
     VQAE_REQUIRE(wino_trunk_supported(c, h, w, dtype), VQAE_ERR_UNSUPPORTED, "wino_trunk_tail: C = %d, H = %d, W = %d, dtype %d", c, h, w, dtype);
     const int64_t M = (int64_t)batch * h * w;
@@ -718,7 +714,7 @@ int wino_trunk_tail(const float* t1, const float* U, const float* w3, float act_
     k.t1 = t1; k.U = U; k.w3 = w3; k.w1n = w1n; k.xio = xio; k.y2 = t1_next;
     k.H = h; k.Wimg = w; k.M = (int)M;
     k.act_a = act_a; k.act_b = act_b; k.t_scale = t_scale; k.t_b4 = t_b4;
-    k.n_b1a = n_b1a; k.n_b1b = n_b1b; k.n_b2a = n_b2a; k.n_b2b = n_b2b;
+    k.n_b1a = next.b1a; k.n_b1b = next.b1b; k.n_b2a = next.b2a; k.n_b2b = next.b2b;
     return dtype == VQAE_DT_BF16 ? launch_wino<32, VQAE_DT_BF16>(k, w1n != nullptr, stream)
          : dtype == VQAE_DT_F16 ? launch_wino<32, VQAE_DT_F16>(k, w1n != nullptr, stream)
          : c == 256 ? launch_wino<256>(k, w1n != nullptr, stream)

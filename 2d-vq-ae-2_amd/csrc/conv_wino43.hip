@@ -27,7 +27,7 @@
 // operand as three bf16 pieces and six of their nine products.
 // The same kernel serves the level above the trunk (C = 64 on the 64-wide grid: 2 slices x 2 tile groups) and C = 256 on the code
 // grid (8 slices, 512 threads, one workgroup per CU).
-#include "common.h"
+#include "kernels.h"
 
 namespace {
 
@@ -634,17 +634,15 @@ __global__ void split_1x1_kernel(const float* __restrict__ w, int c, __bf16* __r
 
 namespace vqae {
 
+// C = 32 on the 128-wide grid keeps F(2x2, 3x3) and its smaller rounding error: that level is bound by HBM and vector issue,
+// and the 30 % fewer MFMAs of F(4x4, 3x3) bought nothing there (675 us either way)
+bool wino43_channels(int c) { return c == 256 || c == 128 || c == 64; }
+
 // geometry only; whether a handle uses this form at all is decided when it is created (VQAE_WINO43=0: F(2x2, 3x3) everywhere)
 bool wino43_supported(int c, int h, int w, int dtype) {
-    // C = 32 on the 128-wide grid keeps F(2x2, 3x3) and its smaller rounding error: that level is bound by HBM and vector issue,
-    // and the 30 % fewer MFMAs of F(4x4, 3x3) bought nothing there (675 us either way)
-    const bool cw = (c == 256 && w == 32) || (c == 128 && w == 32) || (c == 64 && w == 64);
-    return dtype == VQAE_DT_F32 && cw && h >= 8 && h % 8 == 0;
+    return dtype == VQAE_DT_F32 && wino43_channels(c) && w == (c == 64 ? 64 : 32) && h >= 8 && h % 8 == 0;
 }
-bool wino43_enabled() {
-    const char* e = getenv("VQAE_WINO43");
-    return !(e && !atoi(e));
-}
+bool wino43_enabled() { return env_int("VQAE_WINO43", 1) != 0; }
 
 size_t wino43_weight_floats(int c) { return (size_t)36 * c * c; }
 
@@ -661,7 +659,6 @@ int wino43_split_weight(const float* w_oihw_dev, int c, void* U_dev, hipStream_t
     return VQAE_OK;
 }
 
-// packed [c][c] 1x1 weights (device, vqae_conv_pack_weight_f32) -> the split tail fragments
 int split_1x1_weight(const float* w_packed_dev, int c, void* out_dev, hipStream_t stream) {
     VQAE_REQUIRE(wino43_split_supported(c), VQAE_ERR_UNSUPPORTED, "split_1x1_weight: C = %d", c);
     split_1x1_kernel<<<(unsigned)ceil_div(c * c, 256), 256, 0, stream>>>(w_packed_dev, c, (__bf16*)out_dev);
@@ -669,9 +666,8 @@ int split_1x1_weight(const float* w_packed_dev, int c, void* out_dev, hipStream_
     return VQAE_OK;
 }
 
-// w_oihw_dev [c][c][3][3] (PyTorch layout, device) -> U_dev [36][c][c] (fragment order above)
 int wino43_transform_weight(const float* w_oihw_dev, int c, float* U_dev, hipStream_t stream) {
-    VQAE_REQUIRE(c == 256 || c == 128 || c == 64, VQAE_ERR_UNSUPPORTED, "wino43_transform_weight: C = %d", c);
+    VQAE_REQUIRE(wino43_channels(c), VQAE_ERR_UNSUPPORTED, "wino43_transform_weight: C = %d", c);
     wino43_weight_kernel<<<(unsigned)ceil_div(c * c, 256), 256, 0, stream>>>(w_oihw_dev, c, U_dev);
     VQAE_LAUNCH_CHECK();
     return VQAE_OK;
@@ -695,13 +691,12 @@ static int launch_w43(W43K& k, int64_t M, bool chain, hipStream_t stream) {
     return VQAE_OK;
 }
 
-// Same contract as wino_trunk_tail (conv_wino.hip): t1 -> xio in place (+ t1_next); w3 / w1n in that file's fragment order (k-slice 8).
-// Us / w3s / w1ns non-null (all three, w1ns only when chained): the split form with those weights (wino43_split_weight, split_1x1_weight).
 int wino43_trunk_tail(const float* t1, const float* U, const float* w3, float act_a, float act_b, float t_scale, float t_b4,
-                      float* xio, const float* w1n, float n_b1a, float n_b1b, float n_b2a, float n_b2b, float* t1_next,
-                      int batch, int h, int w, int c, hipStream_t stream,
-                      const void* Us, const void* w3s, const void* w1ns) {
+                      float* xio, const NextConv1& next, int batch, int h, int w, int c, hipStream_t stream,
+                      const void* Us, const void* w3s) {
     if (batch == 0) return VQAE_OK;
+    const float* w1n = (const float*)next.w1;
+    float* t1_next = (float*)next.t1_next;
     VQAE_REQUIRE(t1 && U && w3 && xio && (!w1n || t1_next), VQAE_ERR_INVALID, "wino43_trunk_tail: null pointer");
     VQAE_REQUIRE(wino43_supported(c, h, w, VQAE_DT_F32), VQAE_ERR_UNSUPPORTED, "wino43_trunk_tail: C = %d, H = %d, W = %d", c, h, w);
     const int64_t M = (int64_t)batch * h * w;
@@ -711,10 +706,10 @@ int wino43_trunk_tail(const float* t1, const float* U, const float* w3, float ac
     k.t1 = t1; k.U = U; k.w3 = w3; k.w1n = w1n; k.xio = xio; k.y2 = t1_next;
     k.H = h; k.M = (int)M;
     k.act_a = act_a; k.act_b = act_b; k.t_scale = t_scale; k.t_b4 = t_b4;
-    k.n_b1a = n_b1a; k.n_b1b = n_b1b; k.n_b2a = n_b2a; k.n_b2b = n_b2b;
+    k.n_b1a = next.b1a; k.n_b1b = next.b1b; k.n_b2a = next.b2a; k.n_b2b = next.b2b;
     if (Us) {
-        VQAE_REQUIRE(wino43_split_supported(c) && w3s && (!w1n || w1ns), VQAE_ERR_INVALID, "wino43_trunk_tail: split form needs C = 128 and its three weights");
-        k.Us = (const float*)Us; k.w3s = (const float*)w3s; k.w1ns = (const float*)w1ns;
+        VQAE_REQUIRE(wino43_split_supported(c) && w3s && (!w1n || next.w1s), VQAE_ERR_INVALID, "wino43_trunk_tail: split form needs C = 128 and its three weights");
+        k.Us = (const float*)Us; k.w3s = (const float*)w3s; k.w1ns = (const float*)next.w1s;
         return launch_w43<128, true>(k, M, w1n != nullptr, stream);
     }
     switch (c) {

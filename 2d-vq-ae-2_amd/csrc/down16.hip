@@ -18,7 +18,7 @@
 //            HBM read) -> T1[out pixel][tap * CO + c]
 //   phase 2  conv2 from T1 (K = 4 CO); skip_conv from global (L2 hits, requested before conv2) -> T2[out pixel][c]
 //   phase 3  conv3 from T2, epilogue, fp32 store.
-#include "common.h"
+#include "kernels.h"
 
 namespace {
 
@@ -272,9 +272,10 @@ int launch_down16(const Down16K& k, int64_t n_tiles, hipStream_t stream) {
 
 namespace vqae {
 
-// cin in {8, 16, 32, 64}; output width a multiple of 32, output height a multiple of the tile's rows (4, 4, 2, 1)
+bool down16_channels(int cin) { return cin == 8 || cin == 16 || cin == 32 || cin == 64; }
+
 bool down16_supported(int cin, int h, int w) {
-    if (cin != 8 && cin != 16 && cin != 32 && cin != 64) return false;
+    if (!down16_channels(cin)) return false;
     const int rows = (4096 / (2 * cin < 32 ? 32 : 2 * cin)) / 32;
     return h % 2 == 0 && w % 64 == 0 && (h / 2) % rows == 0;
 }
@@ -284,8 +285,6 @@ static int pad_k(int k) { return (k + 15) / 16 * 16; }
 
 size_t down16_weight_bytes(int n_rows, int K) { return (size_t)pad_rows(n_rows) * pad_k(K) * 2; }
 
-// packed [>= max(n_rows, 32)][K] fp32 (device; vqae_conv_pack_weight_f32 pads the rows to 128 with zeros) -> 16-bit fragment
-// order (device); n_rows % 32 == 0 or n_rows in {8, 16}; K % 8 == 0 (padded to 16 with zeros)
 int down16_pack_weight(const float* w_packed_dev, int n_rows, int K, int dtype, void* out_dev, hipStream_t stream) {
     VQAE_REQUIRE((n_rows % 32 == 0 || n_rows == 16 || n_rows == 8) && K % 8 == 0, VQAE_ERR_INVALID, "down16_pack_weight: %d x %d", n_rows, K);
     VQAE_REQUIRE(dtype == VQAE_DT_BF16 || dtype == VQAE_DT_F16, VQAE_ERR_INVALID, "down16_pack_weight: dtype %d", dtype);
@@ -297,21 +296,19 @@ int down16_pack_weight(const float* w_packed_dev, int n_rows, int K, int dtype, 
     return VQAE_OK;
 }
 
-// x [B][H][W][cin] fp32 -> y [B][H/2][W/2][2 cin] fp32; weights from down16_pack_weight; scalars10 =
-// {b1a, b1b, b2a, b2b, b3a, b3b, b4, scale, b1c, b1d}; dtype bf16 / f16
 int down16_block(const float* x, const void* w1h, const void* w2h, const void* w3h, const void* wskh, int B, int H, int W,
-                 int cin, const float* scalars10, int dtype, float* y, hipStream_t stream) {
+                 int cin, const FixupScalars& s, int dtype, float* y, hipStream_t stream) {
     if (B == 0) return VQAE_OK;
     VQAE_REQUIRE(dtype == VQAE_DT_BF16 || dtype == VQAE_DT_F16, VQAE_ERR_INVALID, "down16_block: dtype %d", dtype);
-    VQAE_REQUIRE(x && w1h && w2h && w3h && wskh && y && scalars10, VQAE_ERR_INVALID, "down16_block: null pointer");
+    VQAE_REQUIRE(x && w1h && w2h && w3h && wskh && y, VQAE_ERR_INVALID, "down16_block: null pointer");
     VQAE_REQUIRE(down16_supported(cin, H, W), VQAE_ERR_UNSUPPORTED, "down16_block: cin %d, %dx%d", cin, H, W);
     Down16K k;
     k.x = x; k.w1 = w1h; k.w2 = w2h; k.w3 = w3h; k.wsk = wskh; k.y = y;
     k.H = H; k.W = W;
     const int rows = (4096 / (2 * cin < 32 ? 32 : 2 * cin)) / 32;
     k.tiles_x = (W / 2) / 32; k.tiles_y = (H / 2) / rows;
-    k.b1a = scalars10[0]; k.b1b = scalars10[1]; k.b2a = scalars10[2]; k.b2b = scalars10[3]; k.b3a = scalars10[4];
-    k.b3b = scalars10[5]; k.b4 = scalars10[6]; k.scale = scalars10[7]; k.b1c = scalars10[8]; k.b1d = scalars10[9];
+    k.b1a = s.b1a; k.b1b = s.b1b; k.b2a = s.b2a; k.b2b = s.b2b; k.b3a = s.b3a;
+    k.b3b = s.b3b; k.b4 = s.b4; k.scale = s.scale; k.b1c = s.b1c; k.b1d = s.b1d;
     const int64_t n_tiles = (int64_t)B * k.tiles_x * k.tiles_y;
     VQAE_REQUIRE(n_tiles < (1ll << 31), VQAE_ERR_UNSUPPORTED, "down16_block: too many tiles");
 #define VQAE_D16(CI_) (dtype == VQAE_DT_BF16 ? launch_down16<CI_, VQAE_DT_BF16>(k, n_tiles, stream) : launch_down16<CI_, VQAE_DT_F16>(k, n_tiles, stream))

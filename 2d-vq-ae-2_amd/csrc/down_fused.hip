@@ -13,7 +13,7 @@
 //   phase 2  conv2 from T1 (K = 4 CO)                              -> t2 into LDS T2[out pixel][c] (over T1)
 //   phase 3  conv3 from T2 and skip_conv from global, epilogue, store.
 // Weight matrices are read from L2 in MFMA fragment order (contiguous wave-wide loads, see conv_wino.hip).
-#include "common.h"
+#include "kernels.h"
 
 namespace {
 
@@ -246,14 +246,14 @@ int launch_down(const DownK& k, int64_t n_tiles, int dtype, hipStream_t stream) 
 
 namespace vqae {
 
-// cin in {16, 32, 64}; output width a multiple of 32, output height a multiple of the tile's rows (4, 2, 1)
+bool down_block_channels(int cin) { return cin == 16 || cin == 32 || cin == 64; }
+
 bool down_block_supported(int cin, int h, int w) {
-    if (cin != 16 && cin != 32 && cin != 64) return false;
+    if (!down_block_channels(cin)) return false;
     const int rows = (4096 / (2 * cin)) / 32;
     return h % 2 == 0 && w % 64 == 0 && (h / 2) % rows == 0;
 }
 
-// packed [n_rows][K] -> fragment order (n_rows % 32 == 0, K % 8 == 0)
 int frag_weight_rect(const float* w_packed_dev, int n_rows, int K, float* out_dev, hipStream_t stream) {
     VQAE_REQUIRE(n_rows % 32 == 0 && K % 8 == 0, VQAE_ERR_INVALID, "frag_weight_rect: %d x %d", n_rows, K);
     frag_rect_kernel<<<(unsigned)ceil_div((int64_t)n_rows * K, 256), 256, 0, stream>>>(w_packed_dev, n_rows, K, out_dev);
@@ -261,21 +261,19 @@ int frag_weight_rect(const float* w_packed_dev, int n_rows, int K, float* out_de
     return VQAE_OK;
 }
 
-// x [B][H][W][cin] -> y [B][H/2][W/2][2 cin]; weights in fragment order (frag_weight_rect); scalars10 =
-// {b1a, b1b, b2a, b2b, b3a, b3b, b4, scale, b1c, b1d}
 int down_block(const float* x, const float* w1f, const float* w2f, const float* w3f, const float* wskf, int B, int H, int W,
-               int cin, const float* scalars10, int dtype, float* y, hipStream_t stream) {
+               int cin, const FixupScalars& s, int dtype, float* y, hipStream_t stream) {
     if (B == 0) return VQAE_OK;
     VQAE_REQUIRE(dtype >= VQAE_DT_F32 && dtype <= VQAE_DT_F16, VQAE_ERR_INVALID, "down_block: dtype %d", dtype);
-    VQAE_REQUIRE(x && w1f && w2f && w3f && wskf && y && scalars10, VQAE_ERR_INVALID, "down_block: null pointer");
+    VQAE_REQUIRE(x && w1f && w2f && w3f && wskf && y, VQAE_ERR_INVALID, "down_block: null pointer");
     VQAE_REQUIRE(down_block_supported(cin, H, W), VQAE_ERR_UNSUPPORTED, "down_block: cin %d, %dx%d", cin, H, W);
     DownK k;
     k.x = x; k.w1 = w1f; k.w2 = w2f; k.w3 = w3f; k.wsk = wskf; k.y = y;
     k.H = H; k.W = W;
     const int rows = (4096 / (2 * cin)) / 32;
     k.tiles_x = (W / 2) / 32; k.tiles_y = (H / 2) / rows;
-    k.b1a = scalars10[0]; k.b1b = scalars10[1]; k.b2a = scalars10[2]; k.b2b = scalars10[3]; k.b3a = scalars10[4];
-    k.b3b = scalars10[5]; k.b4 = scalars10[6]; k.scale = scalars10[7]; k.b1c = scalars10[8]; k.b1d = scalars10[9];
+    k.b1a = s.b1a; k.b1b = s.b1b; k.b2a = s.b2a; k.b2b = s.b2b; k.b3a = s.b3a;
+    k.b3b = s.b3b; k.b4 = s.b4; k.scale = s.scale; k.b1c = s.b1c; k.b1d = s.b1d;
     const int64_t n_tiles = (int64_t)B * k.tiles_x * k.tiles_y;
     VQAE_REQUIRE(n_tiles < (1ll << 31), VQAE_ERR_UNSUPPORTED, "down_block: too many tiles");
     if (cin == 16) return launch_down<16>(k, n_tiles, dtype, stream);

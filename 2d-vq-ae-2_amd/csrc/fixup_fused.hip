@@ -11,7 +11,6 @@
 // All three weight matrices stay resident in LDS ([n][k] rows, +4 float pad: conflict-free
 // ds_read_b128 fragments); workgroups are persistent and walk tiles in an XCD-contiguous order.
 #include "common.h"
-#include <cstdlib>
 
 namespace {
 
@@ -752,8 +751,7 @@ extern "C" int vqae_fixup_same_block_f32(const float* x, float* y, const float* 
     if (c == 8) return launch_c8(p, stream);
     // fp32, C = 16: conv2 as Winograd F(2x2, 3x3) from registers (fixup_same_wino16_kernel); read per call so that tests can compare
     // the forms inside one process
-    const char* nw = getenv("VQAE_NO_WINO16");
-    if (c == 16 && dtype == VQAE_DT_F32 && !(nw && atoi(nw))) return launch_wino16<8>(p, stream);
+    if (c == 16 && dtype == VQAE_DT_F32 && vqae::env_int("VQAE_NO_WINO16", 0) == 0) return launch_wino16<8>(p, stream);
     if (c == 16) return launch_tiny<16, 8>(p, stream);
     return launch_fused<32, 4>(p, stream);
 }

@@ -4,7 +4,7 @@
 // the reference's state-dict naming and are repacked once into the MFMA kernel's
 // [cout_pad][tap*cin] layout; activations stay NHWC fp32 in four rotating HBM buffers owned by the
 // handle (X = residual stream, P/Q/R = block temporaries).
-#include "common.h"
+#include "kernels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -22,77 +22,7 @@ char* last_error_buf() {
     static thread_local char buf[512] = {0};
     return buf;
 }
-int conv_trunk_tail(const vqae_conv_args* a, const float* t1, const float* w2, const float* w3, float t_scale,
-                    float t_b4, float* xio, const float* w1n, float n_b1a, float n_b1b, float n_b2a, float n_b2b,
-                    float* t1_next, hipStream_t stream);
-bool wino_trunk_supported(int c, int h, int w, int dtype);
-size_t wino_weight_floats(int c);
-int wino_transform_weight(const float* w_oihw_dev, int c, int dtype, float* U_dev, hipStream_t stream);
-int wino_frag_weight(const float* w_packed_dev, int c, int sk, float* out_dev, hipStream_t stream);
-int conv_tail_kslice(int dtype, int cin);
-bool wino43_supported(int c, int h, int w, int dtype);
-bool wino43_enabled();
-size_t wino43_weight_floats(int c);
-int wino43_transform_weight(const float* w_oihw_dev, int c, float* U_dev, hipStream_t stream);
-bool wino43_split_supported(int c);
-size_t wino43_split_weight_bytes(int c);
-size_t split_1x1_bytes(int c);
-int wino43_split_weight(const float* w_oihw_dev, int c, void* U_dev, hipStream_t stream);
-int split_1x1_weight(const float* w_packed_dev, int c, void* out_dev, hipStream_t stream);
-int wino43_trunk_tail(const float* t1, const float* U, const float* w3, float act_a, float act_b, float t_scale, float t_b4,
-                      float* xio, const float* w1n, float n_b1a, float n_b1b, float n_b2a, float n_b2b, float* t1_next,
-                      int batch, int h, int w, int c, hipStream_t stream,
-                      const void* Us, const void* w3s, const void* w1ns);
-int wino_trunk_tail(const float* t1, const float* U, const float* w3, float act_a, float act_b, float t_scale, float t_b4,
-                    float* xio, const float* w1n, float n_b1a, float n_b1b, float n_b2a, float n_b2b, float* t1_next,
-                    int batch, int h, int w, int c, int dtype, hipStream_t stream);
-bool trunk16_supported(int c, int h, int w, int dtype);
-size_t trunk16_weight_bytes(int c, int taps);
-int trunk16_pack_weight(const float* w_packed_dev, int c, int taps, int dtype, void* out_dev, hipStream_t stream);
-int trunk16_round_pack(const float* src, void* dst, int64_t n, int dtype, hipStream_t stream);
-bool trunk16_head_supported(int c, int64_t m, int dtype);
-int trunk16_head(const float* x, const void* w1f, float b1a, float b1b, float b2a, float b2b, void* t1, int64_t m, int c,
-                 int dtype, bool out32, hipStream_t stream);
-bool stem16_supported(int c0, int h, int w, int dtype);
-size_t stem16_weight_bytes(int cin);
-int stem16_pack_weight(const float* w_dev, int n_out, int cin, int dtype, void* out_dev, hipStream_t stream);
-int istem16(const void* x, int x_kind, const float* mean255, const float* inv_std255, const void* wf, const float* bias, int B,
-            int H, int W, int c0, float* y, int dtype, hipStream_t stream);
-int ostem16(const float* x, const void* wf, const float* bias, int B, int H, int W, int c, float* y, int y_nchw, int dtype,
-            hipStream_t stream);
-bool same8_16_supported(int c, int h, int w, int dtype);
-int same8_16_block(const float* x, float* y, const float* w1_packed, const void* w2h, const void* w3h, int B, int H, int W,
-                   const float* scalars8, int dtype, hipStream_t stream);
-bool same16_16_supported(int c, int h, int w, int dtype);
-int same16_16_block(const float* x, float* y, const void* w1h, const void* w2h, const void* w3h, int B, int H, int W, int c,
-                    const float* scalars8, int dtype, hipStream_t stream);
-bool up16_supported(int c, int h, int w, int dtype);
-int up16_block(const float* x, const float* t1, const void* w2h, const void* w3h, const void* wskh, int B, int H, int W, int c,
-               float b3a, float b3b, float scale, float b4, float b1c, float b1d, int dtype, float* y, hipStream_t stream);
-int trunk16_block(const void* t1, const void* w2f, const void* w3f, float act_a, float act_b, float t_scale, float t_b4,
-                  float* xio, const void* w1nf, float n_b1a, float n_b1b, float n_b2a, float n_b2b, void* t1_next,
-                  int batch, int h, int w, int c, int dtype, hipStream_t stream);
-bool fixup_conv1_supported(int c, int64_t m);
-int fixup_conv1(const float* x, const float* w1f, float pa, float pb, float aa, float ab, float* y, int64_t m, int c,
-                hipStream_t stream);
-bool down_block_supported(int cin, int h, int w);
-int frag_weight_rect(const float* w_packed_dev, int n_rows, int K, float* out_dev, hipStream_t stream);
-bool down16_supported(int cin, int h, int w);
-size_t down16_weight_bytes(int n_rows, int K);
-int down16_pack_weight(const float* w_packed_dev, int n_rows, int K, int dtype, void* out_dev, hipStream_t stream);
-int down16_block(const float* x, const void* w1h, const void* w2h, const void* w3h, const void* wskh, int B, int H, int W,
-                 int cin, const float* scalars10, int dtype, float* y, hipStream_t stream);
-int down_block(const float* x, const float* w1f, const float* w2f, const float* w3f, const float* wskf, int B, int H, int W,
-               int cin, const float* scalars10, int dtype, float* y, hipStream_t stream);
-bool up_tail_supported(int cb, int co);
-int up_tail(const float* q, const float* s, const float* w3_packed, int B, int H, int W, int cb, int co, float b3a, float b3b,
-            float scale, float b4, float* y, hipStream_t stream);
-int conv3x3_direct(const void* x, int x_kind, const float* mean255, const float* inv_std255, const float* w,
-                   const float* bias, int B, int H, int W, int cin, int cout, float* y, int y_nchw, int dt,
-                   hipStream_t stream);
-}  // namespace vqae
 
-namespace vqae {
 ProfState& prof_state() {
     static ProfState p;
     return p;
@@ -168,19 +98,17 @@ namespace {
 
 enum { MODE_SAME = 0, MODE_DOWN = 1, MODE_UP = 2 };
 
-struct Block {
+struct Block : vqae::FixupScalars {
     int mode, cin, cout, br;
-    float b1a, b1b, b2a, b2b, b3a, b3b, b4, scale, b1c, b1d;
     float *w1, *w2, *w3, *wskip;          // packed, device
     float* wU43 = nullptr;                // F(4x4, 3x3)-domain conv2 weights [36][C][C] (fp32, C = 128, conv_wino43.hip)
     void *wU43s = nullptr, *w1s = nullptr, *w3s = nullptr;   // the same and conv1 / conv3 as three bf16 planes (split form, C = 128)
     float* wU = nullptr;                  // Winograd-domain conv2 weights [16][C][C] (fp32 trunk blocks, C = 64 / 128, conv_wino.hip)
     float *w1f = nullptr, *w3f = nullptr; // conv1 / conv3 weights in MFMA fragment order for the fused tails (both trunk kernels)
     float *w2f = nullptr, *wskf = nullptr;// 'down' blocks: conv2 / skip_conv in fragment order too (down_fused.hip)
-    void *w1h = nullptr, *w2h = nullptr, *w3h = nullptr;   // 16-bit modes: conv1 / conv2 / conv3 as 16-bit MFMA fragments (trunk16.hip)
-    void *dw1h = nullptr, *dw2h = nullptr, *dw3h = nullptr, *dwskh = nullptr;   // 16-bit modes, 'down' blocks (down16.hip)
-    void *uw1h = nullptr, *uw2h = nullptr, *uw3h = nullptr, *uwskh = nullptr;   // 16-bit modes, 'up' blocks (head16 + up16.hip)
-    void *s8w2h = nullptr, *s8w3h = nullptr;                                    // 16-bit modes, C = 8 'same' blocks (same8_16.hip)
+    // 16-bit modes: the convs as 16-bit MFMA fragments for the one kernel family that the block's mode and width select (load_block):
+    // 'same' C >= 16: trunk16.hip / same16_16; 'same' C = 8: w2h / w3h for same8_16.hip; 'down': down16.hip; 'up': head16 (w1h) + up16.hip
+    void *w1h = nullptr, *w2h = nullptr, *w3h = nullptr, *wskh = nullptr;
     // MBConv (conv_block.py:240-321), BatchNorms folded: br = expanded width, w2 = depthwise taps [k*k][br]
     int kind = VQAE_BLOCK_FIXUP, hidden = 0;
     float *bv1 = nullptr, *bv2 = nullptr, *bv3 = nullptr;                        // folded BN shifts
@@ -225,7 +153,7 @@ struct vqae_handle {
     void* idx_scratch = nullptr;           // indices nobody asked for (vqae_forward with idx == NULL)
     size_t idx_scratch_bytes = 0;
     float* se_ws = nullptr;                // MBConv: SE partial sums, then the gate [B][E]
-    size_t se_ws_floats = 0;
+    size_t se_ws_bytes = 0;
     size_t se_gate_off = 0;
 };
 
@@ -261,55 +189,44 @@ int upload(vqae_handle* h, const float* host, int64_t numel, float** out) {
     return VQAE_OK;
 }
 
+// host tensor -> temporary device buffer -> transform(tmp, dst) into an owned allocation of out_bytes; synchronised, temporary freed
+template <class Transform>
+int upload_via(vqae_handle* h, const float* host, size_t in_bytes, size_t out_bytes, const char* what, Transform transform, void** out) {
+    void* tmp = nullptr;
+    if (hipMalloc(&tmp, in_bytes) != hipSuccess) return vqae::fail(VQAE_ERR_NOMEM, "hipMalloc failed");
+    const hipError_t e = hipMemcpy(tmp, host, in_bytes, hipMemcpyHostToDevice);
+    void* dst = nullptr;
+    int rc = (e == hipSuccess) ? dev_alloc(h, out_bytes, &dst) : vqae::fail(VQAE_ERR_HIP, "hipMemcpy failed: %s", hipGetErrorString(e));
+    if (rc == VQAE_OK) rc = transform((const float*)tmp, dst);
+    if (rc == VQAE_OK && hipDeviceSynchronize() != hipSuccess) rc = vqae::fail(VQAE_ERR_HIP, "%s failed", what);
+    (void)hipFree(tmp);
+    *out = dst;
+    return rc;
+}
+
+// conv weights [cout][cin][ks][ks] (host, PyTorch layout) -> the MFMA kernel's packed layout, rounded to the compute dtype
 int upload_packed(vqae_handle* h, const float* host, int cout, int cin, int ks, float** out) {
-    float* raw = nullptr;
-    void* tmp = nullptr;
-    const int64_t numel = (int64_t)cout * cin * ks * ks;
-    if (hipMalloc(&tmp, (size_t)numel * 4) != hipSuccess) return vqae::fail(VQAE_ERR_NOMEM, "hipMalloc failed");
-    raw = (float*)tmp;
-    hipError_t e = hipMemcpy(raw, host, (size_t)numel * 4, hipMemcpyHostToDevice);
-    void* packed = nullptr;
-    int rc = (e == hipSuccess) ? dev_alloc(h, vqae_conv_packed_floats(cout, cin, ks) * 4, &packed)
-                               : vqae::fail(VQAE_ERR_HIP, "hipMemcpy failed: %s", hipGetErrorString(e));
-    if (rc == VQAE_OK) rc = vqae_conv_pack_weight_f32(raw, cout, cin, ks, (float*)packed, nullptr);
-    if (rc == VQAE_OK) rc = vqae_round_inplace_f32((float*)packed, (int64_t)vqae_conv_packed_floats(cout, cin, ks), h->cfg.compute_dtype, nullptr);
-    if (rc == VQAE_OK && hipDeviceSynchronize() != hipSuccess) rc = vqae::fail(VQAE_ERR_HIP, "pack sync failed");
-    (void)hipFree(tmp);
-    *out = (float*)packed;
-    return rc;
+    const size_t n = vqae_conv_packed_floats(cout, cin, ks);
+    const int dt = h->cfg.compute_dtype;
+    return upload_via(h, host, (size_t)cout * cin * ks * ks * 4, n * 4, "weight packing", [=](const float* raw, void* dst) {
+        const int rc = vqae_conv_pack_weight_f32(raw, cout, cin, ks, (float*)dst, nullptr);
+        return rc ? rc : vqae_round_inplace_f32((float*)dst, (int64_t)n, dt, nullptr);
+    }, (void**)out);
 }
 
-// conv2 weights [c][c][3][3] (host, PyTorch layout) -> Winograd domain on the device
+// conv2 weights [c][c][3][3] (host, PyTorch layout) -> Winograd F(2x2, 3x3) domain on the device
 int upload_wino(vqae_handle* h, const float* host, int c, float** out) {
-    void* tmp = nullptr;
-    const size_t raw = (size_t)c * c * 9 * 4;
-    if (hipMalloc(&tmp, raw) != hipSuccess) return vqae::fail(VQAE_ERR_NOMEM, "hipMalloc failed");
-    hipError_t e = hipMemcpy(tmp, host, raw, hipMemcpyHostToDevice);
-    void* U = nullptr;
-    int rc = (e == hipSuccess) ? dev_alloc(h, vqae::wino_weight_floats(c) * 4, &U)
-                               : vqae::fail(VQAE_ERR_HIP, "hipMemcpy failed: %s", hipGetErrorString(e));
-    if (rc == VQAE_OK) rc = vqae::wino_transform_weight((const float*)tmp, c, h->cfg.compute_dtype, (float*)U, nullptr);
-    if (rc == VQAE_OK && hipDeviceSynchronize() != hipSuccess) rc = vqae::fail(VQAE_ERR_HIP, "winograd weight transform failed");
-    (void)hipFree(tmp);
-    *out = (float*)U;
-    return rc;
+    const int dt = h->cfg.compute_dtype;
+    return upload_via(h, host, (size_t)c * c * 9 * 4, vqae::wino_weight_floats(c) * 4, "winograd weight transform",
+                      [=](const float* raw, void* U) { return vqae::wino_transform_weight(raw, c, dt, (float*)U, nullptr); }, (void**)out);
 }
 
-// conv2 weights [c][c][3][3] (host, PyTorch layout) -> F(4x4, 3x3) domain on the device (conv_wino43.hip); split: as three bf16 planes
+// ... -> F(4x4, 3x3) domain (conv_wino43.hip); split: as three bf16 planes
 int upload_wino43(vqae_handle* h, const float* host, int c, bool split, void** out) {
-    void* tmp = nullptr;
-    const size_t raw = (size_t)c * c * 9 * 4;
-    if (hipMalloc(&tmp, raw) != hipSuccess) return vqae::fail(VQAE_ERR_NOMEM, "hipMalloc failed");
-    hipError_t e = hipMemcpy(tmp, host, raw, hipMemcpyHostToDevice);
-    void* U = nullptr;
-    int rc = (e == hipSuccess) ? dev_alloc(h, split ? vqae::wino43_split_weight_bytes(c) : vqae::wino43_weight_floats(c) * 4, &U)
-                               : vqae::fail(VQAE_ERR_HIP, "hipMemcpy failed: %s", hipGetErrorString(e));
-    if (rc == VQAE_OK) rc = split ? vqae::wino43_split_weight((const float*)tmp, c, U, nullptr)
-                                  : vqae::wino43_transform_weight((const float*)tmp, c, (float*)U, nullptr);
-    if (rc == VQAE_OK && hipDeviceSynchronize() != hipSuccess) rc = vqae::fail(VQAE_ERR_HIP, "winograd weight transform failed");
-    (void)hipFree(tmp);
-    *out = U;
-    return rc;
+    return upload_via(h, host, (size_t)c * c * 9 * 4, split ? vqae::wino43_split_weight_bytes(c) : vqae::wino43_weight_floats(c) * 4,
+                      "winograd weight transform", [=](const float* raw, void* U) {
+        return split ? vqae::wino43_split_weight(raw, c, U, nullptr) : vqae::wino43_transform_weight(raw, c, (float*)U, nullptr);
+    }, out);
 }
 
 int scalar(const TensorMap& tm, const std::string& name, float* out) {
@@ -321,100 +238,79 @@ int scalar(const TensorMap& tm, const std::string& name, float* out) {
 }
 
 int load_block(vqae_handle* h, const TensorMap& tm, const std::string& pre, int mode, int cin, int cout, Block* b) {
+    *b = Block();
     b->mode = mode; b->cin = cin; b->cout = cout; b->br = cin > cout ? cin : cout;   // conv_block.py:151-155
-    b->w1 = b->w2 = b->w3 = b->wskip = nullptr;
-    b->b1c = b->b1d = 0.f;
+    const int dt = h->cfg.compute_dtype;
+    const bool f32 = dt == VQAE_DT_F32, same = mode == MODE_SAME && cout == cin;
     int rc;
 #define S_(field, nm) if ((rc = scalar(tm, pre + "." nm, &b->field))) return rc;
     S_(b1a, "bias1a") S_(b1b, "bias1b") S_(b2a, "bias2a") S_(b2b, "bias2b") S_(b3a, "bias3a") S_(b3b, "bias3b")
     S_(b4, "bias4") S_(scale, "scale")
+    // Which weight forms the block gets beside the packed ones.  The widths come from the kernel files' own *_channels(); the grid is
+    // not known here, so each form is packed for every width its kernel serves and run_block's select_route decides per launch.
+    // Deliberately wider than what runs: the F(2x2, 3x3) weights stay beside the F(4x4, 3x3) ones (for the grids those refuse), the
+    // fragment-order tails are packed for the direct trunk tail even when VQAE_NO_WINOGRAD took the Winograd forms away, and the
+    // trunk16 weights are packed whatever VQAE_NO_TRUNK16 says (it is read per process, by trunk16_supported).
+    const bool wino = same && h->use_wino && vqae::wino_trunk_channels(cin, dt);
+    const bool wino43 = wino && f32 && vqae::wino43_enabled() && vqae::wino43_channels(cin);
+    const bool split = wino43 && h->w43_split && vqae::wino43_split_supported(cin);
+    const bool tail = wino || (same && vqae::conv_trunk_tail_channels(cin));            // blocks that run a fused-tail kernel
+    const bool trunk16 = same && !f32 && vqae::trunk16_channels(cin);
+    const bool same8 = same && !f32 && vqae::same8_16_channels(cin);
+    const bool down = mode == MODE_DOWN && cout == 2 * cin && h->fuse_down && vqae::down_block_channels(cin);   // any dtype
+    const bool down16 = mode == MODE_DOWN && cout == 2 * cin && !f32 && h->fuse_down16 && vqae::down16_channels(cin);
+    const bool up16 = mode == MODE_UP && cin == 2 * cout && !f32 && h->fuse_up16 && vqae::up16_channels(cin);
+
     const int k2 = mode == MODE_SAME ? 3 : (mode == MODE_DOWN ? 2 : 1);
     const float* p;
     if ((rc = find(tm, pre + ".branch_conv1.weight", (int64_t)b->br * cin, &p))) return rc;
     if ((rc = upload_packed(h, p, b->br, cin, 1, &b->w1))) return rc;
     if ((rc = find(tm, pre + ".branch_conv2.weight", (int64_t)b->br * b->br * k2 * k2, &p))) return rc;
     if ((rc = upload_packed(h, p, b->br, b->br, k2, &b->w2))) return rc;
-    b->wU = b->wU43 = b->w1f = b->w3f = nullptr;
-    b->wU43s = b->w1s = b->w3s = nullptr;
-    const bool wino = mode == MODE_SAME && cout == cin && h->use_wino &&       // conv_wino.hip: fp32 C = 32/64/128; 16-bit C = 32
-                      (h->cfg.compute_dtype == VQAE_DT_F32 ? (cin == 256 || cin == 128 || cin == 64 || cin == 32) : cin == 32);
     if (wino && (rc = upload_wino(h, p, cin, &b->wU))) return rc;
-    // F(4x4, 3x3) form (C = 256 / 128 on the 32-wide code grid, 64 on the 64-wide, 32 on the 128-wide level; the grid is not known
-    // here, vqae::wino43_supported decides per launch and the F(2x2, 3x3) weights stay for the other grids)
-    if (wino && h->cfg.compute_dtype == VQAE_DT_F32 && vqae::wino43_enabled() && vqae::wino43_supported(cin, 8, cin >= 128 ? 32 : (cin == 64 ? 64 : 128), VQAE_DT_F32) &&
-        (rc = upload_wino43(h, p, cin, false, (void**)&b->wU43))) return rc;
-    const bool split = b->wU43 && h->w43_split && vqae::wino43_split_supported(cin);
+    if (wino43 && (rc = upload_wino43(h, p, cin, false, (void**)&b->wU43))) return rc;
     if (split && (rc = upload_wino43(h, p, cin, true, &b->wU43s))) return rc;
     if ((rc = find(tm, pre + ".branch_conv3.weight", (int64_t)cout * b->br, &p))) return rc;
     if ((rc = upload_packed(h, p, cout, b->br, 1, &b->w3))) return rc;
-    if (wino || (mode == MODE_SAME && (cin == 128 || cin == 64) && cout == cin)) {      // blocks that run a fused-tail kernel
-        const int sk = wino ? 8 : vqae::conv_tail_kslice(h->cfg.compute_dtype, cin);
-        void *f1, *f3;
-        if ((rc = dev_alloc(h, (size_t)cin * cin * 4, &f1)) || (rc = dev_alloc(h, (size_t)cin * cin * 4, &f3))) return rc;
-        b->w1f = (float*)f1; b->w3f = (float*)f3;
-        if ((rc = vqae::wino_frag_weight(b->w1, cin, sk, b->w1f, nullptr)) || (rc = vqae::wino_frag_weight(b->w3, cin, sk, b->w3f, nullptr))) return rc;
-        if (split) {
-            if ((rc = dev_alloc(h, vqae::split_1x1_bytes(cin), &b->w1s)) || (rc = dev_alloc(h, vqae::split_1x1_bytes(cin), &b->w3s))) return rc;
-            if ((rc = vqae::split_1x1_weight(b->w1, cin, b->w1s, nullptr)) || (rc = vqae::split_1x1_weight(b->w3, cin, b->w3s, nullptr))) return rc;
-        }
-        VQAE_HIP_CHECK(hipDeviceSynchronize());
-    }
-    b->w1h = b->w2h = b->w3h = nullptr;
-    if (mode == MODE_SAME && cout == cin && h->cfg.compute_dtype != VQAE_DT_F32 && (cin == 16 || cin == 32 || cin == 64 || cin == 128 || cin == 256)) {
-        struct { float* src; int taps; void** dst; } m[3] = {{b->w1, 1, &b->w1h}, {b->w2, 9, &b->w2h}, {b->w3, 1, &b->w3h}};
-        for (auto& e : m) {
-            if ((rc = dev_alloc(h, vqae::trunk16_weight_bytes(cin, e.taps), e.dst))) return rc;
-            if ((rc = vqae::trunk16_pack_weight(e.src, cin, e.taps, h->cfg.compute_dtype, *e.dst, nullptr))) return rc;
-        }
-        VQAE_HIP_CHECK(hipDeviceSynchronize());
-    }
     if (mode != MODE_SAME) {
         S_(b1c, "bias1c") S_(b1d, "bias1d")
         const int ks = mode == MODE_DOWN ? 2 : 1;
         if ((rc = find(tm, pre + ".skip_conv.weight", (int64_t)cout * cin * ks * ks, &p))) return rc;
         if ((rc = upload_packed(h, p, cout, cin, ks, &b->wskip))) return rc;
     }
-    b->w2f = b->wskf = nullptr;
-    if (mode == MODE_DOWN && h->fuse_down && cout == 2 * cin &&
-        (cin == 16 || cin == 32 || cin == 64)) {             // whole block in one launch (down_fused.hip)
-        struct { float* src; int K; float** dst; } m[4] = {{b->w1, cin, &b->w1f}, {b->w2, 4 * cout, &b->w2f},
-                                                          {b->w3, cout, &b->w3f}, {b->wskip, 4 * cin, &b->wskf}};
-        for (auto& e : m) {
-            void* f;
-            if ((rc = dev_alloc(h, (size_t)cout * e.K * 4, &f))) return rc;
-            *e.dst = (float*)f;
-            if ((rc = vqae::frag_weight_rect(e.src, cout, e.K, *e.dst, nullptr))) return rc;
-        }
-        VQAE_HIP_CHECK(hipDeviceSynchronize());
-    }
-    if (mode == MODE_DOWN && cout == 2 * cin && h->cfg.compute_dtype != VQAE_DT_F32 && h->fuse_down16 &&
-        (cin == 8 || cin == 16 || cin == 32 || cin == 64)) {             // 16-bit MFMA form of the whole block (down16.hip)
-        struct { float* src; int K; void** dst; } m16[4] = {{b->w1, cin, &b->dw1h}, {b->w2, 4 * cout, &b->dw2h},
-                                                            {b->w3, cout, &b->dw3h}, {b->wskip, 4 * cin, &b->dwskh}};
-        for (auto& e : m16) {
-            if ((rc = dev_alloc(h, vqae::down16_weight_bytes(cout, e.K), e.dst))) return rc;
-            if ((rc = vqae::down16_pack_weight(e.src, cout, e.K, h->cfg.compute_dtype, *e.dst, nullptr))) return rc;
-        }
-        VQAE_HIP_CHECK(hipDeviceSynchronize());
-    }
-    if (mode == MODE_SAME && cin == 8 && cout == 8 && h->cfg.compute_dtype != VQAE_DT_F32) {   // same8_16.hip
-        if ((rc = dev_alloc(h, vqae::down16_weight_bytes(8, 72), &b->s8w2h)) || (rc = dev_alloc(h, vqae::down16_weight_bytes(8, 8), &b->s8w3h))) return rc;
-        if ((rc = vqae::down16_pack_weight(b->w2, 8, 72, h->cfg.compute_dtype, b->s8w2h, nullptr))) return rc;
-        if ((rc = vqae::down16_pack_weight(b->w3, 8, 8, h->cfg.compute_dtype, b->s8w3h, nullptr))) return rc;
-        VQAE_HIP_CHECK(hipDeviceSynchronize());
-    }
-    if (mode == MODE_UP && cin == 2 * cout && h->cfg.compute_dtype != VQAE_DT_F32 && h->fuse_up16 &&
-        (cin == 16 || cin == 32 || cin == 64 || cin == 128)) {            // 16-bit MFMA form: head16 (conv1) + up16.hip (the rest)
-        if ((rc = dev_alloc(h, vqae::trunk16_weight_bytes(cin, 1), &b->uw1h))) return rc;
-        if ((rc = vqae::trunk16_pack_weight(b->w1, cin, 1, h->cfg.compute_dtype, b->uw1h, nullptr))) return rc;
-        struct { float* src; int rows; void** dst; } mu[3] = {{b->w2, cin, &b->uw2h}, {b->w3, cout, &b->uw3h}, {b->wskip, cout, &b->uwskh}};
-        for (auto& e : mu) {
-            if ((rc = dev_alloc(h, vqae::down16_weight_bytes(e.rows, cin), e.dst))) return rc;
-            if ((rc = vqae::down16_pack_weight(e.src, e.rows, cin, h->cfg.compute_dtype, *e.dst, nullptr))) return rc;
-        }
-        VQAE_HIP_CHECK(hipDeviceSynchronize());
-    }
 #undef S_
+    // the packers below run on the null stream, in order; one synchronisation at the end covers them
+    auto frag_tail = [&](const float* src, float** dst) {                                // fp32 fragment order of a [cin][cin] 1x1 tail weight
+        if (int r = dev_alloc(h, (size_t)cin * cin * 4, (void**)dst)) return r;
+        return vqae::wino_frag_weight(src, cin, wino ? 8 : vqae::conv_tail_kslice(dt, cin), *dst, nullptr);
+    };
+    auto frag_rect = [&](const float* src, int K, float** dst) {                         // fp32 fragment order, [cout][K]
+        if (int r = dev_alloc(h, (size_t)cout * K * 4, (void**)dst)) return r;
+        return vqae::frag_weight_rect(src, cout, K, *dst, nullptr);
+    };
+    auto split3 = [&](const float* src, void** dst) {                                   // 1x1 tail weight as three bf16 planes
+        if (int r = dev_alloc(h, vqae::split_1x1_bytes(cin), dst)) return r;
+        return vqae::split_1x1_weight(src, cin, *dst, nullptr);
+    };
+    auto pack_t16 = [&](const float* src, int taps, void** dst) {                       // 16-bit fragments, [cin][taps * cin]
+        if (int r = dev_alloc(h, vqae::trunk16_weight_bytes(cin, taps), dst)) return r;
+        return vqae::trunk16_pack_weight(src, cin, taps, dt, *dst, nullptr);
+    };
+    auto pack_r16 = [&](const float* src, int rows, int K, void** dst) {                // 16-bit fragments, [rows][K]
+        if (int r = dev_alloc(h, vqae::down16_weight_bytes(rows, K), dst)) return r;
+        return vqae::down16_pack_weight(src, rows, K, dt, *dst, nullptr);
+    };
+    if (tail && ((rc = frag_tail(b->w1, &b->w1f)) || (rc = frag_tail(b->w3, &b->w3f)))) return rc;
+    if (split && ((rc = split3(b->w1, &b->w1s)) || (rc = split3(b->w3, &b->w3s)))) return rc;
+    if (trunk16 && ((rc = pack_t16(b->w1, 1, &b->w1h)) || (rc = pack_t16(b->w2, 9, &b->w2h)) || (rc = pack_t16(b->w3, 1, &b->w3h)))) return rc;
+    if (same8 && ((rc = pack_r16(b->w2, 8, 72, &b->w2h)) || (rc = pack_r16(b->w3, 8, 8, &b->w3h)))) return rc;
+    if (down && ((rc = frag_rect(b->w1, cin, &b->w1f)) || (rc = frag_rect(b->w2, 4 * cout, &b->w2f)) ||
+                 (rc = frag_rect(b->w3, cout, &b->w3f)) || (rc = frag_rect(b->wskip, 4 * cin, &b->wskf)))) return rc;
+    if (down16 && ((rc = pack_r16(b->w1, cout, cin, &b->w1h)) || (rc = pack_r16(b->w2, cout, 4 * cout, &b->w2h)) ||
+                   (rc = pack_r16(b->w3, cout, cout, &b->w3h)) || (rc = pack_r16(b->wskip, cout, 4 * cin, &b->wskh)))) return rc;
+    if (up16 && ((rc = pack_t16(b->w1, 1, &b->w1h)) || (rc = pack_r16(b->w2, cin, cin, &b->w2h)) ||
+                 (rc = pack_r16(b->w3, cout, cin, &b->w3h)) || (rc = pack_r16(b->wskip, cout, cin, &b->wskh)))) return rc;
+    VQAE_HIP_CHECK(hipDeviceSynchronize());
     return VQAE_OK;
 }
 
@@ -488,16 +384,40 @@ int load_any(vqae_handle* h, const TensorMap& tm, const std::string& pre, int mo
     return h->cfg.block_kind == VQAE_BLOCK_MBCONV ? load_mbconv(h, tm, pre, mode, cin, cout, b)
                                                   : load_block(h, tm, pre, mode, cin, cout, b);
 }
+// n consecutive 'same' blocks of width c, named <prefix><first> ...
+int load_same_run(vqae_handle* h, const TensorMap& tm, const std::string& prefix, int first, int n, int c, std::vector<Block>* v) {
+    for (int i = 0; i < n; ++i) {
+        Block b;
+        if (int rc = load_any(h, tm, prefix + std::to_string(first + i), MODE_SAME, c, c, &b)) return rc;
+        v->push_back(b);
+    }
+    return VQAE_OK;
+}
+
+// The n_down levels of a DownBlock (conv_block.py:35-47) or UpBlock (conv_block.py:72-88) stack: n_pre 'same' blocks, the
+// resampling block (MODE_DOWN: c -> 2c, MODE_UP: c -> c / 2), n_post 'same' blocks of the new width.  *c: the width, updated.
+int load_levels(vqae_handle* h, const TensorMap& tm, const std::string& prefix, int mode, int* c, std::vector<Block>* v) {
+    const vqae_config& cfg = h->cfg;
+    for (int lvl = 0; lvl < cfg.n_down; ++lvl) {
+        const std::string base = prefix + std::to_string(lvl) + ".layers.";
+        const int c2 = mode == MODE_DOWN ? 2 * *c : *c / 2;
+        int rc;
+        if ((rc = load_same_run(h, tm, base, 0, cfg.n_pre, *c, v))) return rc;
+        Block b;
+        if ((rc = load_any(h, tm, base + std::to_string(cfg.n_pre), mode, *c, c2, &b))) return rc;
+        v->push_back(b);
+        if ((rc = load_same_run(h, tm, base, cfg.n_pre + 1, cfg.n_post, c2, v))) return rc;
+        *c = c2;
+    }
+    return VQAE_OK;
+}
 
 // ---- one conv launch --------------------------------------------------------------------------
-// compute dtype of the handle currently executing (set at the top of every entry point; handles are not
-// shared across threads)
-thread_local int g_dt = VQAE_DT_F32;
 struct ConvCall {
     vqae_conv_args a;
-    ConvCall(int B, int H, int W, int cin, int cout, int ks, int stride, int pad, int pad_mode, int dt = g_dt) {
+    ConvCall(const vqae_handle* h, int B, int H, int W, int cin, int cout, int ks, int stride, int pad, int pad_mode) {
         memset(&a, 0, sizeof(a));
-        a.dtype = dt;
+        a.dtype = h->cfg.compute_dtype;
         a.batch = B; a.in_h = H; a.in_w = W; a.cin = cin; a.cout = cout;
         a.ksize = ks; a.stride = stride; a.pad = pad; a.pad_mode = pad_mode;
     }
@@ -506,6 +426,10 @@ struct ConvCall {
     ConvCall& scale_bias(float s, float b) { a.has_scale = 1; a.scale = s; a.bias_s = b; return *this; }
     ConvCall& bias(float b) { a.has_bias_s = 1; a.bias_s = b; return *this; }
 };
+// the generic conv without a bias vector: y = epilogue(conv(pre(x), w)) (+ residual)
+int conv(const ConvCall& c, const float* x, const float* w, const float* residual, float* y, hipStream_t st) {
+    return vqae_conv2d_f32(&c.a, x, w, nullptr, residual, y, st);
+}
 
 // MBConv.forward (conv_block.py:316-321), eval mode, on NHWC buffers; on return buf[0] holds the output.
 //   X --1x1 (+shift1, SiLU)--> P [E] --depthwise (+shift2, SiLU, strip sums)--> Q [E] --SE gate--> g [B][E]
@@ -519,26 +443,26 @@ int run_mbconv(vqae_handle* h, const Block& b, int B, int& H, int& W, hipStream_
     const float* skip = X;
     int Ho = H, Wo = W;
     if (b.mode == MODE_DOWN) {
-        ConvCall sk(B, H, W, b.cin, b.cout, 2, 2, 0, VQAE_PAD_NONE);
+        ConvCall sk(h, B, H, W, b.cin, b.cout, 2, 2, 0, VQAE_PAD_NONE);
         if ((rc = vqae_conv2d_f32(&sk.a, X, b.wskip, nullptr, nullptr, R, st))) return rc;
         skip = R; Ho = H / 2; Wo = W / 2;
     } else if (b.mode == MODE_UP) {
-        ConvCall sk(B, H, W, b.cin, 4 * b.cout, 1, 1, 0, VQAE_PAD_NONE);       // ConvTranspose2d(k2, s2) = 1x1 conv + pixel shuffle
+        ConvCall sk(h, B, H, W, b.cin, 4 * b.cout, 1, 1, 0, VQAE_PAD_NONE);       // ConvTranspose2d(k2, s2) = 1x1 conv + pixel shuffle
         if ((rc = vqae_conv2d_f32(&sk.a, X, b.wskip, nullptr, nullptr, Q, st))) return rc;
         if ((rc = vqae_pixel_shuffle2_f32(Q, B, H, W, b.cout, R, st))) return rc;
         skip = R; Ho = 2 * H; Wo = 2 * W;
     } else if (b.wskip) {
-        ConvCall sk(B, H, W, b.cin, b.cout, 1, 1, 0, VQAE_PAD_NONE);
+        ConvCall sk(h, B, H, W, b.cin, b.cout, 1, 1, 0, VQAE_PAD_NONE);
         if ((rc = vqae_conv2d_f32(&sk.a, X, b.wskip, nullptr, nullptr, R, st))) return rc;
         skip = R;
     }
-    ConvCall c1(B, H, W, b.cin, E, 1, 1, 0, VQAE_PAD_NONE);
+    ConvCall c1(h, B, H, W, b.cin, E, 1, 1, 0, VQAE_PAD_NONE);
     c1.a.has_act = VQAE_ACT_SILU;
     if ((rc = vqae_conv2d_f32(&c1.a, X, b.w1, b.bv1, nullptr, P, st))) return rc;
     const int dwm = b.mode == MODE_SAME ? VQAE_DW_SAME : (b.mode == MODE_DOWN ? VQAE_DW_DOWN : VQAE_DW_UP);
     if ((rc = vqae_dwconv_f32(P, b.w2, b.bv2, B, H, W, E, dwm, 1, Q, partial, st))) return rc;
     if ((rc = vqae_se_gate_f32(partial, B, Ho, Wo, E, b.fc0w, b.fc0b, b.hidden, b.fc2w, b.fc2b, gate, st))) return rc;
-    ConvCall c3(B, Ho, Wo, E, b.cout, 1, 1, 0, VQAE_PAD_NONE);
+    ConvCall c3(h, B, Ho, Wo, E, b.cout, 1, 1, 0, VQAE_PAD_NONE);
     c3.a.pre_mode = VQAE_PRE_CHANNEL_GATE;
     float* out = skip == X ? X : R;                                            // in-place residual add
     if ((rc = vqae_conv2d_gated_f32(&c3.a, Q, gate, b.w3, b.bv3, skip, out, st))) return rc;
@@ -547,195 +471,188 @@ int run_mbconv(vqae_handle* h, const Block& b, int B, int& H, int& W, hipStream_
     return VQAE_OK;
 }
 
+// ---- one Fixup block ---------------------------------------------------------------------------
+// The kernels a block can run on, in priority order within each mode: select_route returns the first whose condition holds.
+enum Route {
+    R_SAME16_16,                    // 16-bit, C = 16 / 32: a whole block per launch (same8_16.hip) beats the chained trunk16 launches
+    R_TRUNK16,                      // 16-bit, C = 64 / 128 / 256 (trunk16.hip): t1 travels as 16-bit; one launch per block
+    R_WINO43_SPLIT, R_WINO43,       // fp32 trunk, conv2 as Winograd F(4x4, 3x3) (conv_wino43.hip); split: GEMMs on the bf16 MFMA
+    R_WINO,                         // ... as F(2x2, 3x3) (conv_wino.hip; also C = 32 in the 16-bit modes)
+    R_TAIL,                         // ... direct conv2 with the same fused tail (conv_mfma.hip), C = 64 / 128
+    R_SAME8_16,                     // 16-bit, C = 8: the whole block on the 16-bit MFMA (same8_16.hip)
+    R_FIXUP_FUSED,                  // high-resolution levels: the whole block in one launch (fixup_fused.hip)
+    R_SAME,                         // three generic conv launches
+    R_DOWN16, R_DOWN_FUSED, R_DOWN, // 'down': one launch on the 16-bit MFMA (down16.hip) / on the fp32 engine (down_fused.hip) / four generic
+    R_UP_CONV_FIRST_TAIL,           // fp32 'up', 1x1 convs before the resize; stem-side levels: resizes + ELU + conv3 in one launch
+    R_UP_CONV_FIRST,
+    R_UP16,                         // 16-bit 'up': head16 + one launch (up16.hip)
+    R_UP                            // generic 'up': resize first
+};
+
+// is `next` another 'same' block of b's width (whose conv1 the trunk tail of b can run)?
+bool same_width_next(const Block& b, const Block* next) {
+    return next && next->mode == MODE_SAME && next->cin == b.cin && next->cout == b.cin;
+}
+
+Route select_route(const vqae_handle* h, const Block& b, const Block* next, int B, int H, int W) {
+    const int dt = h->cfg.compute_dtype;
+    const bool f32 = dt == VQAE_DT_F32;
+    if (b.mode == MODE_SAME) {
+        if (b.w2h && h->fuse_trunk && vqae::same16_16_supported(b.cin, H, W, dt)) return R_SAME16_16;
+        if (b.w2h && h->fuse_trunk && vqae::trunk16_supported(b.cin, H, W, dt)) return R_TRUNK16;
+        if (b.wU && h->fuse_trunk && vqae::wino_trunk_supported(b.cin, H, W, dt)) {
+            if (!(b.wU43 && vqae::wino43_supported(b.cin, H, W, dt))) return R_WINO;
+            const bool chain = same_width_next(b, next) && next->w1f;                 // the split form needs the next conv1 split too
+            return b.wU43s && (!chain || next->w1s) ? R_WINO43_SPLIT : R_WINO43;
+        }
+        if (vqae::conv_trunk_tail_channels(b.cin) && b.cout == b.cin && h->fuse_trunk) return R_TAIL;
+        if (b.w2h && !f32 && vqae::same8_16_supported(b.cin, H, W, dt)) return R_SAME8_16;
+        if (b.cin == b.cout && vqae_fixup_same_supported(b.cin, H, W)) return R_FIXUP_FUSED;
+        return R_SAME;
+    }
+    if (b.mode == MODE_DOWN) {
+        if (b.w2h && !f32 && vqae::down16_supported(b.cin, H, W)) return R_DOWN16;
+        if (b.w2f && vqae::down_block_supported(b.cin, H, W)) return R_DOWN_FUSED;
+        return R_DOWN;
+    }
+    if (f32 && h->up_conv_first) return h->fuse_up_tail && vqae::up_tail_supported(b.br, b.cout) ? R_UP_CONV_FIRST_TAIL : R_UP_CONV_FIRST;
+    if (b.w2h && vqae::up16_supported(b.cin, H, W, dt) && vqae::trunk16_head_supported(b.cin, (int64_t)B * H * W, dt)) return R_UP16;
+    return R_UP;
+}
+
+// the block's conv1 on the generic kernel: y = ELU(conv1x1(ELU(x + b1a) + b1b) + b2a) + b2b
+int run_conv1(const vqae_handle* h, const Block& b, int B, int H, int W, const float* x, float* y, hipStream_t st) {
+    return conv(ConvCall(h, B, H, W, b.cin, b.br, 1, 1, 0, VQAE_PAD_NONE).pre(VQAE_PRE_BIAS_ELU_BIAS, b.b1a, b.b1b).act(b.b2a, b.b2b), x, b.w1, nullptr, y, st);
+}
+
+// The trunk routes: conv1 (unless the previous block's tail already left t1 in P), then ONE launch for conv2 + conv3 and, when the
+// next block is another 'same' block of this width, its conv1 (t1_next -> Q, which then becomes P).
+int run_trunk(vqae_handle* h, Route r, const Block& b, const Block* next, int B, int H, int W, hipStream_t st) {
+    float *X = h->buf[0], *P = h->buf[1], *Q = h->buf[2];
+    const int dt = h->cfg.compute_dtype;
+    const int64_t M = (int64_t)B * H * W;
+    const bool t16 = r == R_TRUNK16, wino = r == R_WINO43_SPLIT || r == R_WINO43 || r == R_WINO;
+    int rc;
+    if (!h->t1_ready) {                                                                  // chain head: conv1 is a launch of its own
+        if (t16 && vqae::trunk16_head_supported(b.cin, M, dt)) {
+            rc = vqae::trunk16_head(X, b.w1h, b.b1a, b.b1b, b.b2a, b.b2b, P, M, b.cin, dt, false, st);
+        } else if (t16) {                                                                // the generic kernel (fp32 out) + the conv2 input cast
+            if ((rc = run_conv1(h, b, B, H, W, X, Q, st))) return rc;
+            rc = vqae::trunk16_round_pack(Q, P, M * b.cin, dt, st);
+        } else if (wino && dt == VQAE_DT_F32 && vqae::fixup_conv1_supported(b.cin, M)) {
+            rc = vqae::fixup_conv1(X, b.w1f, b.b1a, b.b1b, b.b2a, b.b2b, P, M, b.cin, st);
+        } else {
+            rc = run_conv1(h, b, B, H, W, X, P, st);
+        }
+        if (rc) return rc;
+    }
+    vqae::NextConv1 nx;
+    const void* next_w1 = !same_width_next(b, next) ? nullptr : (t16 ? next->w1h : (const void*)next->w1f);
+    if (next_w1) nx = {next_w1, next->w1s, next->b1a, next->b1b, next->b2a, next->b2b, Q};
+    if (t16) {
+        rc = vqae::trunk16_block(P, b.w2h, b.w3h, b.b3a, b.b3b, b.scale, b.b4, X, nx, B, H, W, b.cin, dt, st);
+    } else if (r == R_WINO43_SPLIT || r == R_WINO43) {
+        rc = vqae::wino43_trunk_tail(P, b.wU43, b.w3f, b.b3a, b.b3b, b.scale, b.b4, X, nx, B, H, W, b.cin, st,
+                                     r == R_WINO43_SPLIT ? b.wU43s : nullptr, b.w3s);
+    } else if (r == R_WINO) {
+        rc = vqae::wino_trunk_tail(P, b.wU, b.w3f, b.b3a, b.b3b, b.scale, b.b4, X, nx, B, H, W, b.cin, dt, st);
+    } else {
+        const ConvCall c2 = ConvCall(h, B, H, W, b.br, b.br, 3, 1, 1, VQAE_PAD_CIRCULAR).act(b.b3a, b.b3b);
+        rc = vqae::conv_trunk_tail(&c2.a, P, b.w2, b.w3f, b.scale, b.b4, X, nx, st);
+    }
+    if (rc) return rc;
+    if (nx.w1) std::swap(h->buf[1], h->buf[2]);
+    h->t1_ready = nx.w1 != nullptr;
+    return VQAE_OK;
+}
+
 // PreActFixupResBlock.forward (conv_block.py:196-216) on NHWC buffers.  X holds the input and, on
 // return, buf[0] holds the output (buffers are swapped for down/up).
 int run_block(vqae_handle* h, const Block& b, const Block* next, int B, int& H, int& W, hipStream_t st) {
     if (b.kind == VQAE_BLOCK_MBCONV) return run_mbconv(h, b, B, H, W, st);
     float *X = h->buf[0], *P = h->buf[1], *Q = h->buf[2], *R = h->buf[3];
-    int rc;
-    if (b.mode == MODE_SAME && b.w2h && h->fuse_trunk && vqae::same16_16_supported(b.cin, H, W, g_dt)) {
-        // 16-bit modes, C = 16 / 32: a whole block per launch (csrc/same8_16.hip) beats the chained trunk16 launches at these widths
-        const float sc[8] = {b.b1a, b.b1b, b.b2a, b.b2b, b.b3a, b.b3b, b.b4, b.scale};
-        if ((rc = vqae::same16_16_block(X, P, b.w1h, b.w2h, b.w3h, B, H, W, b.cin, sc, g_dt, st))) return rc;
-        std::swap(h->buf[0], h->buf[1]);
-        h->t1_ready = false;
-        return VQAE_OK;
-    }
-    if (b.mode == MODE_SAME && b.w2h && h->fuse_trunk && vqae::trunk16_supported(b.cin, H, W, g_dt)) {
-        // 16-bit modes, C = 64 / 128 / 256 (trunk16.hip): t1 travels as 16-bit; one launch per block
-        if (!h->t1_ready && vqae::trunk16_head_supported(b.cin, (int64_t)B * H * W, g_dt)) {   // chain head: its own conv1 launch
-            if ((rc = vqae::trunk16_head(X, b.w1h, b.b1a, b.b1b, b.b2a, b.b2b, P, (int64_t)B * H * W, b.cin, g_dt, false, st))) return rc;
-        } else if (!h->t1_ready) {                   // ... or the generic kernel (fp32 out) + the conv2 input cast
-            ConvCall c1(B, H, W, b.cin, b.br, 1, 1, 0, VQAE_PAD_NONE);
-            c1.pre(VQAE_PRE_BIAS_ELU_BIAS, b.b1a, b.b1b).act(b.b2a, b.b2b);
-            if ((rc = vqae_conv2d_f32(&c1.a, X, b.w1, nullptr, nullptr, Q, st))) return rc;
-            if ((rc = vqae::trunk16_round_pack(Q, P, (int64_t)B * H * W * b.cin, g_dt, st))) return rc;
-        }
-        const bool chain = next && next->mode == MODE_SAME && next->cin == b.cin && next->cout == b.cin && next->w1h;
-        if ((rc = vqae::trunk16_block(P, b.w2h, b.w3h, b.b3a, b.b3b, b.scale, b.b4, X, chain ? next->w1h : nullptr,
-                                      chain ? next->b1a : 0.f, chain ? next->b1b : 0.f, chain ? next->b2a : 0.f,
-                                      chain ? next->b2b : 0.f, chain ? Q : nullptr, B, H, W, b.cin, g_dt, st))) return rc;
-        if (chain) std::swap(h->buf[1], h->buf[2]);
-        h->t1_ready = chain;
-        return VQAE_OK;
-    }
-    const bool wino = b.mode == MODE_SAME && b.wU && h->fuse_trunk && vqae::wino_trunk_supported(b.cin, H, W, g_dt);
-    if (b.mode == MODE_SAME && (wino || ((b.cin == 128 || b.cin == 64) && b.cout == b.cin && h->fuse_trunk))) {
-        // trunk: conv1 (unless the previous block's tail already produced t1 in P), then ONE launch for
-        // conv2 + conv3 (+ the next block's conv1 when it is another 'same' block of this width)
-        if (!h->t1_ready) {
-            const int64_t M = (int64_t)B * H * W;
-            if (wino && g_dt == VQAE_DT_F32 && vqae::fixup_conv1_supported(b.cin, M)) {
-                if ((rc = vqae::fixup_conv1(X, b.w1f, b.b1a, b.b1b, b.b2a, b.b2b, P, M, b.cin, st))) return rc;
-            } else {
-                ConvCall c1(B, H, W, b.cin, b.br, 1, 1, 0, VQAE_PAD_NONE);
-                c1.pre(VQAE_PRE_BIAS_ELU_BIAS, b.b1a, b.b1b).act(b.b2a, b.b2b);
-                if ((rc = vqae_conv2d_f32(&c1.a, X, b.w1, nullptr, nullptr, P, st))) return rc;
-            }
-        }
-        const bool chain = next && next->mode == MODE_SAME && next->cin == b.cin && next->cout == b.cin && (!wino || next->w1f);
-        if (wino && b.wU43 && vqae::wino43_supported(b.cin, H, W, g_dt)) {
-            const bool split = b.wU43s && (!chain || next->w1s);
-            if ((rc = vqae::wino43_trunk_tail(P, b.wU43, b.w3f, b.b3a, b.b3b, b.scale, b.b4, X, chain ? next->w1f : nullptr,
-                                              chain ? next->b1a : 0.f, chain ? next->b1b : 0.f, chain ? next->b2a : 0.f,
-                                              chain ? next->b2b : 0.f, chain ? Q : nullptr, B, H, W, b.cin, st,
-                                              split ? b.wU43s : nullptr, b.w3s, chain ? next->w1s : nullptr))) return rc;
-            if (chain) std::swap(h->buf[1], h->buf[2]);
-            h->t1_ready = chain;
-            return VQAE_OK;
-        }
-        if (wino) {
-            if ((rc = vqae::wino_trunk_tail(P, b.wU, b.w3f, b.b3a, b.b3b, b.scale, b.b4, X, chain ? next->w1f : nullptr,
-                                            chain ? next->b1a : 0.f, chain ? next->b1b : 0.f, chain ? next->b2a : 0.f,
-                                            chain ? next->b2b : 0.f, chain ? Q : nullptr, B, H, W, b.cin, g_dt, st))) return rc;
-            if (chain) std::swap(h->buf[1], h->buf[2]);
-            h->t1_ready = chain;
-            return VQAE_OK;
-        }
-        ConvCall c2(B, H, W, b.br, b.br, 3, 1, 1, VQAE_PAD_CIRCULAR);
-        c2.act(b.b3a, b.b3b);
-        if ((rc = vqae::conv_trunk_tail(&c2.a, P, b.w2, b.w3f, b.scale, b.b4, X, chain ? next->w1f : nullptr,
-                                        chain ? next->b1a : 0.f, chain ? next->b1b : 0.f, chain ? next->b2a : 0.f,
-                                        chain ? next->b2b : 0.f, chain ? Q : nullptr, st))) return rc;
-        if (chain) std::swap(h->buf[1], h->buf[2]);
-        h->t1_ready = chain;
-        return VQAE_OK;
-    }
+    const int dt = h->cfg.compute_dtype;
+    const Route r = select_route(h, b, next, B, H, W);
+    if (r >= R_TRUNK16 && r <= R_TAIL) return run_trunk(h, r, b, next, B, H, W, st);
     h->t1_ready = false;
-    if (b.mode == MODE_SAME && b.s8w2h && g_dt != VQAE_DT_F32 && vqae::same8_16_supported(b.cin, H, W, g_dt)) {
-        // 16-bit modes, C = 8: the whole block on the 16-bit MFMA (csrc/same8_16.hip), X -> P, swap
-        const float sc[8] = {b.b1a, b.b1b, b.b2a, b.b2b, b.b3a, b.b3b, b.b4, b.scale};
-        if ((rc = vqae::same8_16_block(X, P, b.w1, b.s8w2h, b.s8w3h, B, H, W, sc, g_dt, st))) return rc;
-        std::swap(h->buf[0], h->buf[1]);
-        return VQAE_OK;
-    }
-    if (b.mode == MODE_SAME && b.cin == b.cout && vqae_fixup_same_supported(b.cin, H, W)) {
-        // high-resolution levels: the whole block in one launch (csrc/fixup_fused.hip), X -> P, swap
-        const float sc[8] = {b.b1a, b.b1b, b.b2a, b.b2b, b.b3a, b.b3b, b.b4, b.scale};
-        if ((rc = vqae_fixup_same_block_f32(X, P, b.w1, b.w2, b.w3, B, H, W, b.cin, sc, g_dt, st))) return rc;
-        std::swap(h->buf[0], h->buf[1]);
-        return VQAE_OK;
-    }
-    if (b.mode == MODE_SAME) {
-        ConvCall c1(B, H, W, b.cin, b.br, 1, 1, 0, VQAE_PAD_NONE);
-        c1.pre(VQAE_PRE_BIAS_ELU_BIAS, b.b1a, b.b1b).act(b.b2a, b.b2b);
-        if ((rc = vqae_conv2d_f32(&c1.a, X, b.w1, nullptr, nullptr, P, st))) return rc;
-        ConvCall c2(B, H, W, b.br, b.br, 3, 1, 1, VQAE_PAD_CIRCULAR);
-        c2.act(b.b3a, b.b3b);
-        if ((rc = vqae_conv2d_f32(&c2.a, P, b.w2, nullptr, nullptr, Q, st))) return rc;
-        ConvCall c3(B, H, W, b.br, b.cout, 1, 1, 0, VQAE_PAD_NONE);
-        c3.scale_bias(b.scale, b.b4);
-        return vqae_conv2d_f32(&c3.a, Q, b.w3, nullptr, X, X, st);          // + inp, in place
-    }
-    if (b.mode == MODE_DOWN && b.dw2h && g_dt != VQAE_DT_F32 && vqae::down16_supported(b.cin, H, W)) {
-        const float sc[10] = {b.b1a, b.b1b, b.b2a, b.b2b, b.b3a, b.b3b, b.b4, b.scale, b.b1c, b.b1d};
-        if ((rc = vqae::down16_block(X, b.dw1h, b.dw2h, b.dw3h, b.dwskh, B, H, W, b.cin, sc, g_dt, R, st))) return rc;
-        H /= 2; W /= 2;
-        std::swap(h->buf[0], h->buf[3]);
-        return VQAE_OK;
-    }
-    if (b.mode == MODE_DOWN && b.w2f && vqae::down_block_supported(b.cin, H, W)) {
-        const float sc[10] = {b.b1a, b.b1b, b.b2a, b.b2b, b.b3a, b.b3b, b.b4, b.scale, b.b1c, b.b1d};
-        if ((rc = vqae::down_block(X, b.w1f, b.w2f, b.w3f, b.wskf, B, H, W, b.cin, sc, g_dt, R, st))) return rc;
-        H /= 2; W /= 2;
-        std::swap(h->buf[0], h->buf[3]);
-        return VQAE_OK;
-    }
-    if (b.mode == MODE_DOWN) {
-        ConvCall sk(B, H, W, b.cin, b.cout, 2, 2, 0, VQAE_PAD_NONE);         // skip_conv(inp + bias1c) + bias1d
-        sk.pre(VQAE_PRE_BIAS, b.b1c, 0.f).bias(b.b1d);
-        if ((rc = vqae_conv2d_f32(&sk.a, X, b.wskip, nullptr, nullptr, R, st))) return rc;
-        ConvCall c1(B, H, W, b.cin, b.br, 1, 1, 0, VQAE_PAD_NONE);
-        c1.pre(VQAE_PRE_BIAS_ELU_BIAS, b.b1a, b.b1b).act(b.b2a, b.b2b);
-        if ((rc = vqae_conv2d_f32(&c1.a, X, b.w1, nullptr, nullptr, P, st))) return rc;
-        ConvCall c2(B, H, W, b.br, b.br, 2, 2, 0, VQAE_PAD_NONE);
-        c2.act(b.b3a, b.b3b);
-        if ((rc = vqae_conv2d_f32(&c2.a, P, b.w2, nullptr, nullptr, Q, st))) return rc;
-        H /= 2; W /= 2;
-        ConvCall c3(B, H, W, b.br, b.cout, 1, 1, 0, VQAE_PAD_NONE);
-        c3.scale_bias(b.scale, b.b4);
-        if ((rc = vqae_conv2d_f32(&c3.a, Q, b.w3, nullptr, R, R, st))) return rc;
-        std::swap(h->buf[0], h->buf[3]);
-        return VQAE_OK;
-    }
-    // MODE_UP: ResizeConv2D = conv1x1(bicubic_x2(.)) (layers/conv.py:10-11)
-    if (g_dt == VQAE_DT_F32 && h->up_conv_first) {
-        // A 1x1 conv commutes with the (channel-wise, linear) bicubic resize: run both ResizeConv2D convs at the
-        // LOW resolution and upsample their outputs -- 4x fewer MACs and 2.7x less HBM traffic than conv-after-
-        // resize.  Mathematically identical; rounding differs at the 1e-7 level (validated <= 1e-5 MSE, SURVEY
-        // §8 a5).  fp32 only: under autocast the 16-bit rounding points would move.
-        ConvCall sk(B, H, W, b.cin, b.cout, 1, 1, 0, VQAE_PAD_NONE);
-        sk.pre(VQAE_PRE_BIAS, b.b1c, 0.f).bias(b.b1d);                                   // skip_conv(inp + b1c) + b1d
-        if ((rc = vqae_conv2d_f32(&sk.a, X, b.wskip, nullptr, nullptr, Q, st))) return rc;
-        if (h->fuse_up_tail && vqae::up_tail_supported(b.br, b.cout)) {
-            // stem-side levels: both resizes, the ELU and conv3 in one launch (misc_kernels.hip up_tail_kernel)
-            ConvCall c1(B, H, W, b.cin, b.br, 1, 1, 0, VQAE_PAD_NONE);
-            c1.pre(VQAE_PRE_BIAS_ELU_BIAS, b.b1a, b.b1b).act(b.b2a, b.b2b);
-            if ((rc = vqae_conv2d_f32(&c1.a, X, b.w1, nullptr, nullptr, P, st))) return rc;
-            ConvCall c2(B, H, W, b.br, b.br, 1, 1, 0, VQAE_PAD_NONE);
-            if ((rc = vqae_conv2d_f32(&c2.a, P, b.w2, nullptr, nullptr, R, st))) return rc;
+    int rc;
+    float* out = X;                              // the buffer that holds the block's output; becomes buf[0]
+    switch (r) {
+    case R_SAME16_16:
+        if ((rc = vqae::same16_16_block(X, P, b.w1h, b.w2h, b.w3h, B, H, W, b.cin, b, dt, st))) return rc;
+        out = P;
+        break;
+    case R_SAME8_16:
+        if ((rc = vqae::same8_16_block(X, P, b.w1, b.w2h, b.w3h, B, H, W, b, dt, st))) return rc;
+        out = P;
+        break;
+    case R_FIXUP_FUSED:
+        if ((rc = vqae_fixup_same_block_f32(X, P, b.w1, b.w2, b.w3, B, H, W, b.cin, &b.b1a, dt, st))) return rc;   // scalars8: b1a .. scale
+        out = P;
+        break;
+    case R_SAME:
+        if ((rc = run_conv1(h, b, B, H, W, X, P, st))) return rc;
+        if ((rc = conv(ConvCall(h, B, H, W, b.br, b.br, 3, 1, 1, VQAE_PAD_CIRCULAR).act(b.b3a, b.b3b), P, b.w2, nullptr, Q, st))) return rc;
+        if ((rc = conv(ConvCall(h, B, H, W, b.br, b.cout, 1, 1, 0, VQAE_PAD_NONE).scale_bias(b.scale, b.b4), Q, b.w3, X, X, st))) return rc;   // + inp, in place
+        break;
+    case R_DOWN16:
+        if ((rc = vqae::down16_block(X, b.w1h, b.w2h, b.w3h, b.wskh, B, H, W, b.cin, b, dt, R, st))) return rc;
+        out = R;
+        break;
+    case R_DOWN_FUSED:
+        if ((rc = vqae::down_block(X, b.w1f, b.w2f, b.w3f, b.wskf, B, H, W, b.cin, b, dt, R, st))) return rc;
+        out = R;
+        break;
+    case R_DOWN:                                                                          // skip_conv(inp + bias1c) + bias1d first
+        if ((rc = conv(ConvCall(h, B, H, W, b.cin, b.cout, 2, 2, 0, VQAE_PAD_NONE).pre(VQAE_PRE_BIAS, b.b1c, 0.f).bias(b.b1d), X, b.wskip, nullptr, R, st))) return rc;
+        if ((rc = run_conv1(h, b, B, H, W, X, P, st))) return rc;
+        if ((rc = conv(ConvCall(h, B, H, W, b.br, b.br, 2, 2, 0, VQAE_PAD_NONE).act(b.b3a, b.b3b), P, b.w2, nullptr, Q, st))) return rc;
+        if ((rc = conv(ConvCall(h, B, H / 2, W / 2, b.br, b.cout, 1, 1, 0, VQAE_PAD_NONE).scale_bias(b.scale, b.b4), Q, b.w3, R, R, st))) return rc;
+        out = R;
+        break;
+    // 'up': ResizeConv2D = conv1x1(bicubic_x2(.)) (layers/conv.py:10-11).  CONV_FIRST: a 1x1 conv commutes with the (channel-wise,
+    // linear) bicubic resize, so both ResizeConv2D convs run at the LOW resolution and their outputs are upsampled -- 4x fewer MACs
+    // and 2.7x less HBM traffic than conv-after-resize.  Mathematically identical; rounding differs at the 1e-7 level (validated
+    // <= 1e-5 MSE).  fp32 only: under autocast the 16-bit rounding points would move.
+    case R_UP_CONV_FIRST_TAIL:
+    case R_UP_CONV_FIRST: {
+        const ConvCall sk = ConvCall(h, B, H, W, b.cin, b.cout, 1, 1, 0, VQAE_PAD_NONE).pre(VQAE_PRE_BIAS, b.b1c, 0.f).bias(b.b1d);
+        const ConvCall c2(h, B, H, W, b.br, b.br, 1, 1, 0, VQAE_PAD_NONE);                // conv2 at low resolution
+        if ((rc = conv(sk, X, b.wskip, nullptr, Q, st))) return rc;                        // skip_conv(inp + b1c) + b1d
+        if (r == R_UP_CONV_FIRST_TAIL) {
+            // stem-side levels: both resizes, the ELU and conv3 in one launch (misc_kernels.hip up_tail_kernel); output in buf[0]
+            if ((rc = run_conv1(h, b, B, H, W, X, P, st))) return rc;
+            if ((rc = conv(c2, P, b.w2, nullptr, R, st))) return rc;
             if ((rc = vqae::up_tail(R, Q, b.w3, B, H, W, b.br, b.cout, b.b3a, b.b3b, b.scale, b.b4, X, st))) return rc;
-            H *= 2; W *= 2;
-            return VQAE_OK;                                                             // output in buf[0]
+            break;
         }
         if ((rc = vqae_bicubic_up2_f32(Q, B, H, W, b.cout, 0.f, R, st))) return rc;
-        ConvCall c1(B, H, W, b.cin, b.br, 1, 1, 0, VQAE_PAD_NONE);
-        c1.pre(VQAE_PRE_BIAS_ELU_BIAS, b.b1a, b.b1b).act(b.b2a, b.b2b);
-        if ((rc = vqae_conv2d_f32(&c1.a, X, b.w1, nullptr, nullptr, P, st))) return rc;
-        ConvCall c2(B, H, W, b.br, b.br, 1, 1, 0, VQAE_PAD_NONE);                          // conv2 at low resolution
-        if ((rc = vqae_conv2d_f32(&c2.a, P, b.w2, nullptr, nullptr, Q, st))) return rc;
+        if ((rc = run_conv1(h, b, B, H, W, X, P, st))) return rc;
+        if ((rc = conv(c2, P, b.w2, nullptr, Q, st))) return rc;
         if ((rc = vqae_bicubic_up2_f32(Q, B, H, W, b.br, 0.f, P, st))) return rc;
-        H *= 2; W *= 2;
-        ConvCall c3(B, H, W, b.br, b.cout, 1, 1, 0, VQAE_PAD_NONE);
-        c3.pre(VQAE_PRE_BIAS_ELU_BIAS, b.b3a, b.b3b).scale_bias(b.scale, b.b4);
-        if ((rc = vqae_conv2d_f32(&c3.a, P, b.w3, nullptr, R, R, st))) return rc;
-        std::swap(h->buf[0], h->buf[3]);
-        return VQAE_OK;
+        if ((rc = conv(ConvCall(h, B, 2 * H, 2 * W, b.br, b.cout, 1, 1, 0, VQAE_PAD_NONE).pre(VQAE_PRE_BIAS_ELU_BIAS, b.b3a, b.b3b).scale_bias(b.scale, b.b4),
+                       P, b.w3, R, R, st))) return rc;
+        out = R;
+        break;
     }
-    if (b.uw2h && vqae::up16_supported(b.cin, H, W, g_dt) && vqae::trunk16_head_supported(b.cin, (int64_t)B * H * W, g_dt)) {
-        // 16-bit modes: conv1 at the low resolution (fp32 result of the activation), then the whole high-resolution part in one launch
-        if ((rc = vqae::trunk16_head(X, b.uw1h, b.b1a, b.b1b, b.b2a, b.b2b, Q, (int64_t)B * H * W, b.cin, g_dt, true, st))) return rc;
-        if ((rc = vqae::up16_block(X, Q, b.uw2h, b.uw3h, b.uwskh, B, H, W, b.cin, b.b3a, b.b3b, b.scale, b.b4, b.b1c, b.b1d, g_dt, R, st))) return rc;
-        H *= 2; W *= 2;
-        std::swap(h->buf[0], h->buf[3]);
-        return VQAE_OK;
+    case R_UP16:
+        // conv1 at the low resolution (fp32 result of the activation), then the whole high-resolution part in one launch
+        if ((rc = vqae::trunk16_head(X, b.w1h, b.b1a, b.b1b, b.b2a, b.b2b, Q, (int64_t)B * H * W, b.cin, dt, true, st))) return rc;
+        if ((rc = vqae::up16_block(X, Q, b.w2h, b.w3h, b.wskh, B, H, W, b.cin, b, dt, R, st))) return rc;
+        out = R;
+        break;
+    default:                                                                             // R_UP
+        if ((rc = vqae_bicubic_up2_f32(X, B, H, W, b.cin, b.b1c, P, st))) return rc;      // up(inp + bias1c)
+        if ((rc = conv(ConvCall(h, B, 2 * H, 2 * W, b.cin, b.cout, 1, 1, 0, VQAE_PAD_NONE).bias(b.b1d), P, b.wskip, nullptr, R, st))) return rc;
+        if ((rc = run_conv1(h, b, B, H, W, X, Q, st))) return rc;
+        if ((rc = vqae_bicubic_up2_f32(Q, B, H, W, b.br, 0.f, P, st))) return rc;
+        if ((rc = conv(ConvCall(h, B, 2 * H, 2 * W, b.br, b.br, 1, 1, 0, VQAE_PAD_NONE).act(b.b3a, b.b3b), P, b.w2, nullptr, Q, st))) return rc;
+        if ((rc = conv(ConvCall(h, B, 2 * H, 2 * W, b.br, b.cout, 1, 1, 0, VQAE_PAD_NONE).scale_bias(b.scale, b.b4), Q, b.w3, R, R, st))) return rc;
+        out = R;
     }
-    if ((rc = vqae_bicubic_up2_f32(X, B, H, W, b.cin, b.b1c, P, st))) return rc;               // up(inp + bias1c)
-    ConvCall sk(B, 2 * H, 2 * W, b.cin, b.cout, 1, 1, 0, VQAE_PAD_NONE);
-    sk.bias(b.b1d);
-    if ((rc = vqae_conv2d_f32(&sk.a, P, b.wskip, nullptr, nullptr, R, st))) return rc;
-    ConvCall c1(B, H, W, b.cin, b.br, 1, 1, 0, VQAE_PAD_NONE);
-    c1.pre(VQAE_PRE_BIAS_ELU_BIAS, b.b1a, b.b1b).act(b.b2a, b.b2b);
-    if ((rc = vqae_conv2d_f32(&c1.a, X, b.w1, nullptr, nullptr, Q, st))) return rc;
-    if ((rc = vqae_bicubic_up2_f32(Q, B, H, W, b.br, 0.f, P, st))) return rc;
-    H *= 2; W *= 2;
-    ConvCall c2(B, H, W, b.br, b.br, 1, 1, 0, VQAE_PAD_NONE);
-    c2.act(b.b3a, b.b3b);
-    if ((rc = vqae_conv2d_f32(&c2.a, P, b.w2, nullptr, nullptr, Q, st))) return rc;
-    ConvCall c3(B, H, W, b.br, b.cout, 1, 1, 0, VQAE_PAD_NONE);
-    c3.scale_bias(b.scale, b.b4);
-    if ((rc = vqae_conv2d_f32(&c3.a, Q, b.w3, nullptr, R, R, st))) return rc;
-    std::swap(h->buf[0], h->buf[3]);
+    if (b.mode == MODE_DOWN) { H /= 2; W /= 2; } else if (b.mode == MODE_UP) { H *= 2; W *= 2; }
+    if (out == P) std::swap(h->buf[0], h->buf[1]);
+    else if (out == R) std::swap(h->buf[0], h->buf[3]);
     return VQAE_OK;
 }
 
@@ -764,20 +681,24 @@ int ensure_bufs(vqae_handle* h, size_t need) {
     return VQAE_OK;
 }
 
+// grow-only device scratch: *p holds at least `need` bytes afterwards (contents are not kept)
+int grow(void** p, size_t* have, size_t need, const char* what) {
+    if (need <= *have) return VQAE_OK;
+    VQAE_HIP_CHECK(hipDeviceSynchronize());
+    if (*p) (void)hipFree(*p);
+    *p = nullptr; *have = 0;
+    if (hipMalloc(p, need) != hipSuccess) return vqae::fail(VQAE_ERR_NOMEM, "%s hipMalloc of %zu bytes failed", what, need);
+    *have = need;
+    return VQAE_OK;
+}
+
 int ensure_workspace(vqae_handle* h, int B, int in_h, int in_w) {
     int rc = ensure_bufs(h, max_floats_per_patch(h, in_h, in_w) * (size_t)(B > 0 ? B : 1));
     if (rc) return rc;
     const int64_t rows = (int64_t)B * (in_h >> h->cfg.n_down) * (in_w >> h->cfg.n_down);
     size_t vq_need = vqae_vq_workspace_bytes(rows, h->K, h->D);
     if (h->D == 8) vq_need = std::max(vq_need, vqae_vq_projected_workspace_bytes(rows));
-    if (vq_need > h->vq_ws_bytes) {
-        VQAE_HIP_CHECK(hipDeviceSynchronize());
-        if (h->vq_ws) (void)hipFree(h->vq_ws);
-        h->vq_ws = nullptr; h->vq_ws_bytes = 0;
-        if (hipMalloc(&h->vq_ws, vq_need) != hipSuccess)
-            return vqae::fail(VQAE_ERR_NOMEM, "vq workspace hipMalloc of %zu bytes failed", vq_need);
-        h->vq_ws_bytes = vq_need;
-    }
+    if ((rc = grow(&h->vq_ws, &h->vq_ws_bytes, vq_need, "vq workspace"))) return rc;
     if (h->cfg.block_kind == VQAE_BLOCK_MBCONV) {
         // SE workspace: strip sums of the widest (image, level) + the gate; channels * pixels is largest at full resolution
         const int e_max = 2 * h->cfg.stem * h->cfg.expand_ratio, e_lat = h->C * h->cfg.expand_ratio;
@@ -790,26 +711,11 @@ int ensure_workspace(vqae_handle* h, int B, int in_h, int in_w) {
         }
         const size_t gate_floats = (size_t)(B > 0 ? B : 1) * (size_t)(e_lat > e_max ? e_lat : e_max);
         const size_t need_se = (size_t)vqae::round_up((int64_t)part, 64) + gate_floats;
-        if (need_se > h->se_ws_floats) {
-            VQAE_HIP_CHECK(hipDeviceSynchronize());
-            if (h->se_ws) (void)hipFree(h->se_ws);
-            h->se_ws = nullptr; h->se_ws_floats = 0;
-            if (hipMalloc((void**)&h->se_ws, need_se * 4) != hipSuccess)
-                return vqae::fail(VQAE_ERR_NOMEM, "SE workspace hipMalloc of %zu bytes failed", need_se * 4);
-            h->se_ws_floats = need_se;
-        }
-        h->se_gate_off = h->se_ws_floats - gate_floats;
+        if ((rc = grow((void**)&h->se_ws, &h->se_ws_bytes, need_se * 4, "SE workspace"))) return rc;
+        h->se_gate_off = h->se_ws_bytes / 4 - gate_floats;
     }
     const size_t idx_need = (size_t)vqae::round_up(rows * 4, 256);
-    if (idx_need > h->idx_scratch_bytes) {
-        VQAE_HIP_CHECK(hipDeviceSynchronize());
-        if (h->idx_scratch) (void)hipFree(h->idx_scratch);
-        h->idx_scratch = nullptr; h->idx_scratch_bytes = 0;
-        if (hipMalloc(&h->idx_scratch, idx_need) != hipSuccess)
-            return vqae::fail(VQAE_ERR_NOMEM, "idx scratch hipMalloc of %zu bytes failed", idx_need);
-        h->idx_scratch_bytes = idx_need;
-    }
-    return VQAE_OK;
+    return grow(&h->idx_scratch, &h->idx_scratch_bytes, idx_need, "idx scratch");
 }
 
 // A handle's weights and workspaces live on the device that was current in vqae_create; kernels are launched on the
@@ -833,11 +739,12 @@ int check_geometry(const vqae_handle* h, int B, int in_h, int in_w) {
 // in_stem + down blocks + pre_enc blocks: x -> z in buf[0]  (model.py:198-208)
 int run_encoder_convs(vqae_handle* h, const void* x, int x_kind, int B, int in_h, int in_w, int* zh, int* zw,
                       hipStream_t st) {
+    const int dt = h->cfg.compute_dtype;
     int rc;
-    if (h->stem_wh && vqae::stem16_supported(h->cfg.stem, in_h, in_w, g_dt)) {          // 16-bit modes: the stem on the MFMA (stem16.hip)
-        if ((rc = vqae::istem16(x, x_kind, kMean255, kInv255, h->stem_wh, h->stem_b, B, in_h, in_w, h->cfg.stem, h->buf[0], g_dt, st))) return rc;
+    if (h->stem_wh && vqae::stem16_supported(h->cfg.stem, in_h, in_w, dt)) {          // 16-bit modes: the stem on the MFMA (stem16.hip)
+        if ((rc = vqae::istem16(x, x_kind, kMean255, kInv255, h->stem_wh, h->stem_b, B, in_h, in_w, h->cfg.stem, h->buf[0], dt, st))) return rc;
     } else if ((rc = vqae::conv3x3_direct(x, x_kind, kMean255, kInv255, h->stem_w, h->stem_b, B, in_h, in_w,
-                                          h->cfg.in_channels, h->cfg.stem, h->buf[0], 0, g_dt, st))) return rc;
+                                          h->cfg.in_channels, h->cfg.stem, h->buf[0], 0, dt, st))) return rc;
     int H = in_h, W = in_w;
     h->t1_ready = false;
     for (size_t i = 0; i < h->enc.size(); ++i)
@@ -854,17 +761,17 @@ int run_vq(vqae_handle* h, int B, int zh, int zw, void* idx, int idx_dtype, floa
     if (h->cfg.projection_dim == 8 && h->fuse_vq && h->pin_wt) {
         // reference default: the whole ProjectedEMAVectorQuantizer2d.forward in one pass over z (vq_proj.hip)
         if ((rc = vqae_vq_projected_f32(h->buf[0], h->pin_wt, h->pin_b, h->embed, h->pout_wr, h->pout_b, rows, h->C, h->D, h->K,
-                                        h->cfg.commitment_cost, g_dt, idx, idx_dtype, h->buf[1], nullptr, loss, nullptr,
+                                        h->cfg.commitment_cost, h->cfg.compute_dtype, idx, idx_dtype, h->buf[1], nullptr, loss, nullptr,
                                         h->vq_ws, st))) return rc;
         std::swap(h->buf[0], h->buf[1]);
         return VQAE_OK;
     }
     if (h->cfg.projection_dim > 0) {
-        ConvCall pin(B, zh, zw, h->C, h->D, 1, 1, 0, VQAE_PAD_NONE);
+        ConvCall pin(h, B, zh, zw, h->C, h->D, 1, 1, 0, VQAE_PAD_NONE);
         if ((rc = vqae_conv2d_f32(&pin.a, h->buf[0], h->pin_w, h->pin_b, nullptr, h->buf[1], st))) return rc;
         if ((rc = vqae_vq_forward_f32(h->buf[1], h->embed, rows, h->K, h->D, h->cfg.commitment_cost, idx, idx_dtype,
                                       h->buf[2], loss, nullptr, h->vq_ws, st))) return rc;
-        ConvCall pout(B, zh, zw, h->D, h->C, 1, 1, 0, VQAE_PAD_NONE);
+        ConvCall pout(h, B, zh, zw, h->D, h->C, 1, 1, 0, VQAE_PAD_NONE);
         return vqae_conv2d_f32(&pout.a, h->buf[2], h->pout_w, h->pout_b, nullptr, h->buf[0], st);
     }
     if ((rc = vqae_vq_forward_f32(h->buf[0], h->embed, rows, h->K, h->D, h->cfg.commitment_cost, idx, idx_dtype,
@@ -875,14 +782,15 @@ int run_vq(vqae_handle* h, int B, int zh, int zw, void* idx, int idx_dtype, floa
 
 // post_enc blocks + up blocks + out_stem: q in buf[0] -> out (model.py:278-291)
 int run_decoder_convs(vqae_handle* h, int B, int qh, int qw, int layout, float* out, hipStream_t st) {
+    const int dt = h->cfg.compute_dtype;
     int H = qh, W = qw, rc;
     h->t1_ready = false;
     for (size_t i = 0; i < h->dec.size(); ++i)
         if ((rc = run_block(h, h->dec[i], i + 1 < h->dec.size() ? &h->dec[i + 1] : nullptr, B, H, W, st))) return rc;
-    if (h->ostem_wh && vqae::stem16_supported(h->cfg.stem, H, W, g_dt))
-        return vqae::ostem16(h->buf[0], h->ostem_wh, h->ostem_b, B, H, W, h->cfg.stem, out, layout == VQAE_LAYOUT_NCHW ? 1 : 0, g_dt, st);
+    if (h->ostem_wh && vqae::stem16_supported(h->cfg.stem, H, W, dt))
+        return vqae::ostem16(h->buf[0], h->ostem_wh, h->ostem_b, B, H, W, h->cfg.stem, out, layout == VQAE_LAYOUT_NCHW ? 1 : 0, dt, st);
     return vqae::conv3x3_direct(h->buf[0], 0, nullptr, nullptr, h->ostem_w, h->ostem_b, B, H, W, h->cfg.stem,
-                                h->cfg.in_channels, out, layout == VQAE_LAYOUT_NCHW ? 1 : 0, g_dt, st);
+                                h->cfg.in_channels, out, layout == VQAE_LAYOUT_NCHW ? 1 : 0, dt, st);
 }
 
 int export_q(vqae_handle* h, int B, int zh, int zw, int layout, float* q, hipStream_t st) {
@@ -920,16 +828,16 @@ extern "C" int vqae_create(const vqae_config* cfg, const vqae_tensor* tensors, i
     vqae_handle* h = new vqae_handle();
     h->cfg = *cfg;
     if (hipGetDevice(&h->device) != hipSuccess) { delete h; return vqae::fail(VQAE_ERR_HIP, "hipGetDevice failed"); }
-    h->fuse_trunk = !(getenv("VQAE_NO_TRUNK_FUSION") && atoi(getenv("VQAE_NO_TRUNK_FUSION")));
-    h->up_conv_first = !(getenv("VQAE_NO_UP_REORDER") && atoi(getenv("VQAE_NO_UP_REORDER")));
-    h->use_wino = !(getenv("VQAE_NO_WINOGRAD") && atoi(getenv("VQAE_NO_WINOGRAD")));
-    h->w43_split = !(getenv("VQAE_W43_SPLIT") && !atoi(getenv("VQAE_W43_SPLIT")));
-    h->fuse_up_tail = !(getenv("VQAE_NO_UP_TAIL_FUSION") && atoi(getenv("VQAE_NO_UP_TAIL_FUSION")));
-    h->fuse_down = !(getenv("VQAE_NO_DOWN_FUSION") && atoi(getenv("VQAE_NO_DOWN_FUSION")));
-    h->fuse_down16 = !(getenv("VQAE_NO_DOWN16") && atoi(getenv("VQAE_NO_DOWN16")));
-    h->fuse_up16 = !(getenv("VQAE_NO_UP16") && atoi(getenv("VQAE_NO_UP16")));
-    h->fuse_stem16 = !(getenv("VQAE_NO_STEM16") && atoi(getenv("VQAE_NO_STEM16")));
-    h->fuse_vq = !(getenv("VQAE_NO_VQ_FUSION") && atoi(getenv("VQAE_NO_VQ_FUSION")));
+    h->fuse_trunk = vqae::env_int("VQAE_NO_TRUNK_FUSION", 0) == 0;
+    h->up_conv_first = vqae::env_int("VQAE_NO_UP_REORDER", 0) == 0;
+    h->use_wino = vqae::env_int("VQAE_NO_WINOGRAD", 0) == 0;
+    h->w43_split = vqae::env_int("VQAE_W43_SPLIT", 1) != 0;
+    h->fuse_up_tail = vqae::env_int("VQAE_NO_UP_TAIL_FUSION", 0) == 0;
+    h->fuse_down = vqae::env_int("VQAE_NO_DOWN_FUSION", 0) == 0;
+    h->fuse_down16 = vqae::env_int("VQAE_NO_DOWN16", 0) == 0;
+    h->fuse_up16 = vqae::env_int("VQAE_NO_UP16", 0) == 0;
+    h->fuse_stem16 = vqae::env_int("VQAE_NO_STEM16", 0) == 0;
+    h->fuse_vq = vqae::env_int("VQAE_NO_VQ_FUSION", 0) == 0;
     h->C = cfg->stem << cfg->n_down;
     h->D = cfg->projection_dim > 0 ? cfg->projection_dim : h->C;
     h->K = cfg->num_embeddings;
@@ -945,36 +853,19 @@ extern "C" int vqae_create(const vqae_config* cfg, const vqae_tensor* tensors, i
     int c = cfg->stem << cfg->n_down;
     const std::string vq = "encoder.vq_layers.0.";
 
+    const bool stem16 = cfg->compute_dtype != VQAE_DT_F32 && h->fuse_stem16 && cfg->in_channels == 3 && vqae::stem16_channels(cfg->stem);
+    auto pack_stem16 = [&](const float* w, int n_out, int cin, void** dst) {         // 16-bit modes: the stem on the MFMA (stem16.hip)
+        if (int r = dev_alloc(h, vqae::stem16_weight_bytes(cin), dst)) return r;
+        return vqae::stem16_pack_weight(w, n_out, cin, cfg->compute_dtype, *dst, nullptr);
+    };
     if (has_enc) {
         if ((rc = find(tm, "encoder.in_stem.weight", (int64_t)cfg->stem * 3 * 9, &p)) || (rc = upload(h, p, (int64_t)cfg->stem * 27, &h->stem_w))) return bail(rc);
         if ((rc = find(tm, "encoder.in_stem.bias", cfg->stem, &p)) || (rc = upload(h, p, cfg->stem, &h->stem_b))) return bail(rc);
-        if (cfg->compute_dtype != VQAE_DT_F32 && h->fuse_stem16 && cfg->in_channels == 3 && (cfg->stem == 8 || cfg->stem == 16 || cfg->stem == 32)) {
-            if ((rc = dev_alloc(h, vqae::stem16_weight_bytes(3), &h->stem_wh))) return bail(rc);
-            if ((rc = vqae::stem16_pack_weight(h->stem_w, cfg->stem, 3, cfg->compute_dtype, h->stem_wh, nullptr))) return bail(rc);
-        }
-        // encoder blocks: DownBlock levels (conv_block.py:35-47) then pre_enc (model.py:173-176)
+        if (stem16 && (rc = pack_stem16(h->stem_w, cfg->stem, 3, &h->stem_wh))) return bail(rc);
+        // encoder blocks: DownBlock levels then pre_enc (model.py:173-176)
         c = cfg->stem;
-        for (int lvl = 0; lvl < cfg->n_down; ++lvl) {
-            const std::string base = "encoder.down_layers.0.layers." + std::to_string(lvl) + ".layers.";
-            int bi = 0;
-            Block b;
-            for (int i = 0; i < cfg->n_pre; ++i, ++bi) {
-                if ((rc = load_any(h, tm, base + std::to_string(bi), MODE_SAME, c, c, &b))) return bail(rc);
-                h->enc.push_back(b);
-            }
-            if ((rc = load_any(h, tm, base + std::to_string(bi), MODE_DOWN, c, 2 * c, &b))) return bail(rc);
-            h->enc.push_back(b); ++bi;
-            for (int i = 0; i < cfg->n_post; ++i, ++bi) {
-                if ((rc = load_any(h, tm, base + std::to_string(bi), MODE_SAME, 2 * c, 2 * c, &b))) return bail(rc);
-                h->enc.push_back(b);
-            }
-            c *= 2;
-        }
-        for (int i = 0; i < cfg->n_enc; ++i) {
-            Block b;
-            if ((rc = load_any(h, tm, "encoder.pre_enc_layers.0." + std::to_string(i), MODE_SAME, c, c, &b))) return bail(rc);
-            h->enc.push_back(b);
-        }
+        if ((rc = load_levels(h, tm, "encoder.down_layers.0.layers.", MODE_DOWN, &c, &h->enc))) return bail(rc);
+        if ((rc = load_same_run(h, tm, "encoder.pre_enc_layers.0.", 0, cfg->n_enc, c, &h->enc))) return bail(rc);
     }
     // VQ (codebook is required with an encoder, optional for decode-only handles)
     if (has_enc || tm.count(vq + "embed")) {
@@ -1000,33 +891,11 @@ extern "C" int vqae_create(const vqae_config* cfg, const vqae_tensor* tensors, i
     if (has_dec) {
         if ((rc = find(tm, "decoder.out_stem.weight", (int64_t)3 * cfg->stem * 9, &p)) || (rc = upload(h, p, (int64_t)cfg->stem * 27, &h->ostem_w))) return bail(rc);
         if ((rc = find(tm, "decoder.out_stem.bias", 3, &p)) || (rc = upload(h, p, 3, &h->ostem_b))) return bail(rc);
-        if (cfg->compute_dtype != VQAE_DT_F32 && h->fuse_stem16 && cfg->in_channels == 3 && (cfg->stem == 8 || cfg->stem == 16 || cfg->stem == 32)) {
-            if ((rc = dev_alloc(h, vqae::stem16_weight_bytes(cfg->stem), &h->ostem_wh))) return bail(rc);
-            if ((rc = vqae::stem16_pack_weight(h->ostem_w, 3, cfg->stem, cfg->compute_dtype, h->ostem_wh, nullptr))) return bail(rc);
-        }
-        // decoder blocks: post_enc then UpBlock levels (conv_block.py:72-88)
+        if (stem16 && (rc = pack_stem16(h->ostem_w, 3, cfg->stem, &h->ostem_wh))) return bail(rc);
+        // decoder blocks: post_enc then UpBlock levels
         c = cfg->stem << cfg->n_down;
-        for (int i = 0; i < cfg->n_enc; ++i) {
-            Block b;
-            if ((rc = load_any(h, tm, "decoder.post_enc_layers.0." + std::to_string(i), MODE_SAME, c, c, &b))) return bail(rc);
-            h->dec.push_back(b);
-        }
-        for (int lvl = 0; lvl < cfg->n_down; ++lvl) {
-            const std::string base = "decoder.up_layers.0.layers." + std::to_string(lvl) + ".layers.";
-            int bi = 0;
-            Block b;
-            for (int i = 0; i < cfg->n_pre; ++i, ++bi) {
-                if ((rc = load_any(h, tm, base + std::to_string(bi), MODE_SAME, c, c, &b))) return bail(rc);
-                h->dec.push_back(b);
-            }
-            if ((rc = load_any(h, tm, base + std::to_string(bi), MODE_UP, c, c / 2, &b))) return bail(rc);
-            h->dec.push_back(b); ++bi;
-            for (int i = 0; i < cfg->n_post; ++i, ++bi) {
-                if ((rc = load_any(h, tm, base + std::to_string(bi), MODE_SAME, c / 2, c / 2, &b))) return bail(rc);
-                h->dec.push_back(b);
-            }
-            c /= 2;
-        }
+        if ((rc = load_same_run(h, tm, "decoder.post_enc_layers.0.", 0, cfg->n_enc, c, &h->dec))) return bail(rc);
+        if ((rc = load_levels(h, tm, "decoder.up_layers.0.layers.", MODE_UP, &c, &h->dec))) return bail(rc);
     }
     void* ls = nullptr;
     if ((rc = dev_alloc(h, 256, &ls))) return bail(rc);
@@ -1063,7 +932,6 @@ extern "C" int vqae_set_codebook(vqae_handle* h, const float* embed_host) {
 
 static int encode_impl(vqae_handle* h, const void* x, int x_kind, int B, int in_h, int in_w, void* idx, int idx_dtype,
                        float* q, int q_layout, float* loss, hipStream_t st) {
-    if (h) g_dt = h->cfg.compute_dtype;
     VQAE_REQUIRE(h && x && idx, VQAE_ERR_INVALID, "vqae_encode: null pointer");
     VQAE_REQUIRE(h->has_encoder, VQAE_ERR_INVALID, "vqae_encode: handle was created without encoder.* tensors");
     int rc = check_geometry(h, B, in_h, in_w);
@@ -1089,7 +957,6 @@ extern "C" int vqae_encode_u8(vqae_handle* h, const uint8_t* x, int B, int in_h,
 
 extern "C" int vqae_encode_features(vqae_handle* h, const float* x, int B, int in_h, int in_w, int layout, float* z,
                                     void* stream) {
-    if (h) g_dt = h->cfg.compute_dtype;
     hipStream_t st = (hipStream_t)stream;
     VQAE_REQUIRE(h && x && z, VQAE_ERR_INVALID, "vqae_encode_features: null pointer");
     VQAE_REQUIRE(h->has_encoder, VQAE_ERR_INVALID, "vqae_encode_features: handle has no encoder");
@@ -1100,7 +967,7 @@ extern "C" int vqae_encode_features(vqae_handle* h, const float* x, int B, int i
     int zh, zw;
     if ((rc = run_encoder_convs(h, x, layout == VQAE_LAYOUT_NCHW ? 1 : 0, B, in_h, in_w, &zh, &zw, st))) return rc;
     if (h->cfg.projection_dim > 0) {
-        ConvCall pin(B, zh, zw, h->C, h->D, 1, 1, 0, VQAE_PAD_NONE);
+        ConvCall pin(h, B, zh, zw, h->C, h->D, 1, 1, 0, VQAE_PAD_NONE);
         return vqae_conv2d_f32(&pin.a, h->buf[0], h->pin_w, h->pin_b, nullptr, z, st);
     }
     VQAE_HIP_CHECK(hipMemcpyAsync(z, h->buf[0], (size_t)B * zh * zw * h->C * 4, hipMemcpyDeviceToDevice, st));
@@ -1108,7 +975,6 @@ extern "C" int vqae_encode_features(vqae_handle* h, const float* x, int B, int i
 }
 
 extern "C" int vqae_decode(vqae_handle* h, const float* q, int B, int qh, int qw, int layout, float* out, void* stream) {
-    if (h) g_dt = h->cfg.compute_dtype;
     hipStream_t st = (hipStream_t)stream;
     VQAE_REQUIRE(h && q && out, VQAE_ERR_INVALID, "vqae_decode: null pointer");
     VQAE_REQUIRE(h->has_decoder, VQAE_ERR_INVALID, "vqae_decode: handle was created without decoder.* tensors");
@@ -1127,7 +993,6 @@ extern "C" int vqae_decode(vqae_handle* h, const float* q, int B, int qh, int qw
 
 extern "C" int vqae_decode_indices(vqae_handle* h, const void* idx, int idx_dtype, int B, int qh, int qw, int layout,
                                    float* out, void* stream) {
-    if (h) g_dt = h->cfg.compute_dtype;
     hipStream_t st = (hipStream_t)stream;
     VQAE_REQUIRE(h && idx && out, VQAE_ERR_INVALID, "vqae_decode_indices: null pointer");
     VQAE_REQUIRE(h->has_decoder && h->embed, VQAE_ERR_INVALID, "vqae_decode_indices: handle needs decoder.* tensors and a codebook");
@@ -1139,7 +1004,7 @@ extern "C" int vqae_decode_indices(vqae_handle* h, const void* idx, int idx_dtyp
     const int64_t rows = (int64_t)B * qh * qw;
     if (h->cfg.projection_dim > 0) {
         if ((rc = vqae_embed_code_f32(idx, idx_dtype, h->embed, rows, h->K, h->D, h->buf[1], st))) return rc;
-        ConvCall pout(B, qh, qw, h->D, h->C, 1, 1, 0, VQAE_PAD_NONE);
+        ConvCall pout(h, B, qh, qw, h->D, h->C, 1, 1, 0, VQAE_PAD_NONE);
         if ((rc = vqae_conv2d_f32(&pout.a, h->buf[1], h->pout_w, h->pout_b, nullptr, h->buf[0], st))) return rc;
     } else {
         if ((rc = vqae_embed_code_f32(idx, idx_dtype, h->embed, rows, h->K, h->D, h->buf[0], st))) return rc;
@@ -1154,7 +1019,6 @@ extern "C" int vqae_block_count(const vqae_handle* h, int side) {
 
 extern "C" int vqae_run_blocks(vqae_handle* h, int side, int first, int count, const float* x, int B, int in_h, int in_w,
                                float* y, int* out_h, int* out_w, void* stream) {
-    if (h) g_dt = h->cfg.compute_dtype;
     hipStream_t st = (hipStream_t)stream;
     VQAE_REQUIRE(h && x && y, VQAE_ERR_INVALID, "vqae_run_blocks: null pointer");
     VQAE_REQUIRE(side == 0 || side == 1, VQAE_ERR_INVALID, "vqae_run_blocks: side %d", side);
@@ -1195,7 +1059,6 @@ extern "C" int vqae_run_blocks(vqae_handle* h, int side, int first, int count, c
 
 extern "C" int vqae_forward(vqae_handle* h, const float* x, int B, int in_h, int in_w, int layout, float* out, void* idx,
                             int idx_dtype, float* loss, void* stream) {
-    if (h) g_dt = h->cfg.compute_dtype;
     hipStream_t st = (hipStream_t)stream;
     VQAE_REQUIRE(h && x && out, VQAE_ERR_INVALID, "vqae_forward: null pointer");
     VQAE_REQUIRE(h->has_encoder && h->has_decoder, VQAE_ERR_INVALID, "vqae_forward: handle needs encoder.* and decoder.* tensors");

@@ -1,6 +1,6 @@
 // HBM-bound helper kernels of the VQ-AE hot path (gfx950): the 3-channel stems, bicubic x2,
 // boundary layout shuffles, label max-pool and slide-grid stitching.
-#include "common.h"
+#include "kernels.h"
 
 namespace {
 
@@ -546,7 +546,7 @@ void conv_small_k_kernel(const SmallK p) {
 }  // namespace
 
 namespace vqae {
-// Fused tail of an 'up' block (up_tail_kernel): (branch channels, out channels) in {(64, 32), (32, 16), (16, 8)}.
+// Fused tail of an 'up' block (up_tail_kernel)
 bool up_tail_supported(int cb, int co) { return (cb == 64 && co == 32) || (cb == 32 && co == 16) || (cb == 16 && co == 8); }
 
 int up_tail(const float* q, const float* s, const float* w3_packed, int B, int H, int W, int cb, int co, float b3a, float b3b,
@@ -565,7 +565,7 @@ int up_tail(const float* q, const float* s, const float* w3_packed, int B, int H
     return VQAE_OK;
 }
 
-// 1x1 / stride 1 or 2x2 / stride 2, no padding, cin == 8, cout % 4 == 0: see conv_small_k_kernel.
+// see conv_small_k_kernel
 bool conv_small_k_supported(const vqae_conv_args* a) {
     return a->cin == 8 && a->pad == 0 && a->ksize == a->stride && (a->ksize == 1 || a->ksize == 2) && a->cout % 4 == 0 &&
            a->cout <= 64 && a->pre_mode <= VQAE_PRE_BIAS_ELU_BIAS && a->in_h % a->ksize == 0 && a->in_w % a->ksize == 0;
@@ -589,7 +589,6 @@ int conv_small_k(const vqae_conv_args* a, const float* x, const float* w, const 
     return VQAE_OK;
 }
 
-// internal entry shared with handle.hip: x_kind 0 NHWC f32 / 1 NCHW f32 / 2 u8 NHWC; y_nchw 0/1
 int conv3x3_direct(const void* x, int x_kind, const float* mean255, const float* inv_std255, const float* w,
                    const float* bias, int B, int H, int W, int cin, int cout, float* y, int y_nchw, int dt,
                    hipStream_t stream) {
@@ -601,7 +600,7 @@ int conv3x3_direct(const void* x, int x_kind, const float* mean255, const float*
     VQAE_REQUIRE(x && w && bias && y, VQAE_ERR_INVALID, "conv3x3_direct: null pointer");
     VQAE_REQUIRE(x_kind != 2 || cin == 3, VQAE_ERR_UNSUPPORTED, "conv3x3_direct: uint8 input needs cin == 3");
     if ((int64_t)B * H * W == 0) return VQAE_OK;
-    static const bool no_rb = getenv("VQAE_NO_STEM_RB") && atoi(getenv("VQAE_NO_STEM_RB"));
+    static const bool no_rb = env_int("VQAE_NO_STEM_RB", 0) != 0;
     if (!no_rb && dt == VQAE_DT_F32) {                                      // register-blocked fp32 stems
         if (cout == 3 && x_kind == 0 && (cin == 8 || cin == 16 || cin == 32)) {
             const int64_t npix = (int64_t)B * H * W;
@@ -622,22 +621,12 @@ int conv3x3_direct(const void* x, int x_kind, const float* mean255, const float*
 }
 }  // namespace vqae
 
-namespace vqae {
-bool stem16_supported(int c0, int h, int w, int dtype);
-size_t stem16_weight_bytes(int cin);
-int stem16_pack_weight(const float* w_dev, int n_out, int cin, int dtype, void* out_dev, hipStream_t stream);
-int istem16(const void* x, int x_kind, const float* mean255, const float* inv_std255, const void* wf, const float* bias, int B,
-            int H, int W, int c0, float* y, int dtype, hipStream_t stream);
-int ostem16(const float* x, const void* wf, const float* bias, int B, int H, int W, int c, float* y, int y_nchw, int dtype,
-            hipStream_t stream);
-}  // namespace vqae
-
 extern "C" int vqae_conv3x3_direct_f32(const float* x, const uint8_t* x_u8, const float* mean255, const float* inv_std255,
                                        const float* w, const float* bias, int B, int H, int W, int cin, int cout,
                                        float* y, int dtype, void* stream) {
     VQAE_REQUIRE(dtype >= VQAE_DT_F32 && dtype <= VQAE_DT_F16, VQAE_ERR_INVALID, "conv3x3_direct: dtype %d", dtype);
     // 16-bit modes, stem shapes the MFMA kernels cover (stem16.hip): the same dispatch the model handle uses
-    static const bool no16 = getenv("VQAE_NO_STEM16") && atoi(getenv("VQAE_NO_STEM16"));
+    static const bool no16 = vqae::env_int("VQAE_NO_STEM16", 0) != 0;
     const int c0 = cin == 3 ? cout : (cout == 3 ? cin : 0);
     if (!no16 && dtype != VQAE_DT_F32 && c0 && (cin == 3) != (cout == 3) && vqae::stem16_supported(c0, H, W, dtype) && (cin == 3 || x)) {
         VQAE_REQUIRE((x || x_u8) && w && bias && y, VQAE_ERR_INVALID, "conv3x3_direct: null pointer");

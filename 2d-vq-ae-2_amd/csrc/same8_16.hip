@@ -15,7 +15,7 @@
 //       read per lane and k-step is the whole operand; result layout D[channel][pixel]: lane (pixel, hh) holds channels
 //       4 hh .. 4 hh + 3 in its first register quad -> activation -> the two lane halves swap their 4 channels (one cross-lane
 //       read) -> conv3 (K = 8, padded) -> epilogue with the residual, both as whole 1 KiB rows per wave instruction.
-#include "common.h"
+#include "kernels.h"
 
 namespace {
 
@@ -342,18 +342,18 @@ void same_small16_kernel(const S16K p) {
 
 namespace vqae {
 
+bool same8_16_channels(int c) { return c == 8; }
+
 bool same8_16_supported(int c, int h, int w, int dtype) {
-    static const bool off = getenv("VQAE_NO_SAME8_16") && atoi(getenv("VQAE_NO_SAME8_16"));
+    static const bool off = env_int("VQAE_NO_SAME8_16", 0) != 0;
     if (off || (dtype != VQAE_DT_BF16 && dtype != VQAE_DT_F16)) return false;
-    return c == 8 && h % S8_TH == 0 && w % S8_TW == 0;
+    return same8_16_channels(c) && h % S8_TH == 0 && w % S8_TW == 0;
 }
 
-// x -> y (x != y), [B][H][W][8] fp32; w1: packed fp32 (rounded) [>= 8][8]; w2h / w3h: down16_pack_weight(w2 [8][72]) / (w3 [8][8]);
-// scalars8 = {b1a, b1b, b2a, b2b, b3a, b3b, b4, scale}
 int same8_16_block(const float* x, float* y, const float* w1_packed, const void* w2h, const void* w3h, int B, int H, int W,
-                   const float* scalars8, int dtype, hipStream_t stream) {
+                   const FixupScalars& s, int dtype, hipStream_t stream) {
     if (B == 0) return VQAE_OK;
-    VQAE_REQUIRE(x && y && x != y && w1_packed && w2h && w3h && scalars8, VQAE_ERR_INVALID, "same8_16_block: bad pointer");
+    VQAE_REQUIRE(x && y && x != y && w1_packed && w2h && w3h, VQAE_ERR_INVALID, "same8_16_block: bad pointer");
     VQAE_REQUIRE(same8_16_supported(8, H, W, dtype), VQAE_ERR_UNSUPPORTED, "same8_16_block: %dx%d, dtype %d", H, W, dtype);
     S8K k;
     k.x = x; k.y = y; k.w1 = w1_packed; k.w2f = w2h; k.w3f = w3h;
@@ -361,8 +361,7 @@ int same8_16_block(const float* x, float* y, const float* w1_packed, const void*
     const int64_t n_tiles = (int64_t)B * k.tiles_x * k.tiles_y;
     VQAE_REQUIRE(n_tiles < (1ll << 31), VQAE_ERR_UNSUPPORTED, "same8_16_block: too many tiles");
     k.n_tiles = (int)n_tiles;
-    k.b1a = scalars8[0]; k.b1b = scalars8[1]; k.b2a = scalars8[2]; k.b2b = scalars8[3];
-    k.b3a = scalars8[4]; k.b3b = scalars8[5]; k.b4 = scalars8[6]; k.scale = scalars8[7];
+    k.b1a = s.b1a; k.b1b = s.b1b; k.b2a = s.b2a; k.b2b = s.b2b; k.b3a = s.b3a; k.b3b = s.b3b; k.b4 = s.b4; k.scale = s.scale;
     const unsigned grid = (unsigned)(n_tiles < 256 * 8 ? n_tiles : 256 * 8);
     if (dtype == VQAE_DT_BF16) same8_16_kernel<VQAE_DT_BF16><<<grid, 256, 0, stream>>>(k);
     else same8_16_kernel<VQAE_DT_F16><<<grid, 256, 0, stream>>>(k);
@@ -370,18 +369,17 @@ int same8_16_block(const float* x, float* y, const float* w1_packed, const void*
     return VQAE_OK;
 }
 
-// C = 16 / 32: x -> y (x != y), [B][H][W][C] fp32; w1h / w2h / w3h: trunk16_pack_weight(c = C; taps 1 / 9 / 1)
 bool same16_16_supported(int c, int h, int w, int dtype) {
-    static const bool off = getenv("VQAE_NO_SAME16_16") && atoi(getenv("VQAE_NO_SAME16_16"));
-    static const bool off32 = getenv("VQAE_NO_SAME32_16") && atoi(getenv("VQAE_NO_SAME32_16"));
+    static const bool off = env_int("VQAE_NO_SAME16_16", 0) != 0;
+    static const bool off32 = env_int("VQAE_NO_SAME32_16", 0) != 0;
     if (off || (dtype != VQAE_DT_BF16 && dtype != VQAE_DT_F16)) return false;
     return (c == 16 || (c == 32 && !off32)) && h % S8_TH == 0 && w % S8_TW == 0;
 }
 
 int same16_16_block(const float* x, float* y, const void* w1h, const void* w2h, const void* w3h, int B, int H, int W, int c,
-                    const float* scalars8, int dtype, hipStream_t stream) {
+                    const FixupScalars& s, int dtype, hipStream_t stream) {
     if (B == 0) return VQAE_OK;
-    VQAE_REQUIRE(x && y && x != y && w1h && w2h && w3h && scalars8, VQAE_ERR_INVALID, "same16_16_block: bad pointer");
+    VQAE_REQUIRE(x && y && x != y && w1h && w2h && w3h, VQAE_ERR_INVALID, "same16_16_block: bad pointer");
     VQAE_REQUIRE(same16_16_supported(c, H, W, dtype), VQAE_ERR_UNSUPPORTED, "same16_16_block: C = %d, %dx%d, dtype %d", c, H, W, dtype);
     S16K k;
     k.x = x; k.y = y; k.w1f = w1h; k.w2f = w2h; k.w3f = w3h;
@@ -389,8 +387,7 @@ int same16_16_block(const float* x, float* y, const void* w1h, const void* w2h, 
     const int64_t n_tiles = (int64_t)B * k.tiles_x * k.tiles_y;
     VQAE_REQUIRE(n_tiles < (1ll << 31), VQAE_ERR_UNSUPPORTED, "same16_16_block: too many tiles");
     k.n_tiles = (int)n_tiles;
-    k.b1a = scalars8[0]; k.b1b = scalars8[1]; k.b2a = scalars8[2]; k.b2b = scalars8[3];
-    k.b3a = scalars8[4]; k.b3b = scalars8[5]; k.b4 = scalars8[6]; k.scale = scalars8[7];
+    k.b1a = s.b1a; k.b1b = s.b1b; k.b2a = s.b2a; k.b2b = s.b2b; k.b3a = s.b3a; k.b3b = s.b3b; k.b4 = s.b4; k.scale = s.scale;
     const unsigned grid = (unsigned)(n_tiles < 256 * 6 ? n_tiles : 256 * 6);
     if (c == 16) {
         if (dtype == VQAE_DT_BF16) same_small16_kernel<16, VQAE_DT_BF16><<<grid, 256, 0, stream>>>(k);

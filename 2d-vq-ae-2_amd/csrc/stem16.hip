@@ -12,7 +12,7 @@
 //             per lane and k-step (C0 = 8: a tap pair per step); 3 real output rows; stores NCHW planes or NHWC.
 // Out-of-image halo pixels are zeros (Conv2d padding = 1).  Arithmetic: bias and operands rounded to the 16-bit type, products
 // exact, fp32 accumulation (from the bias), result rounded -- conv3x3_direct_kernel's recipe; only the summation order differs.
-#include "common.h"
+#include "kernels.h"
 
 namespace {
 
@@ -272,14 +272,15 @@ void ostem16_kernel(const OStemK p) {
 
 namespace vqae {
 
+bool stem16_channels(int c0) { return c0 == 8 || c0 == 16 || c0 == 32; }
+
 bool stem16_supported(int c0, int h, int w, int dtype) {
     if (dtype != VQAE_DT_BF16 && dtype != VQAE_DT_F16) return false;
-    return (c0 == 8 || c0 == 16 || c0 == 32) && h % ST_TH == 0 && w % ST_TW == 0;
+    return stem16_channels(c0) && h % ST_TH == 0 && w % ST_TW == 0;
 }
 
 size_t stem16_weight_bytes(int cin) { return (size_t)((9 * cin + 15) / 16) * 1024; }
 
-// w: PyTorch [n_out][cin][3][3] fp32 (device) -> 16-bit fragments (device)
 int stem16_pack_weight(const float* w_dev, int n_out, int cin, int dtype, void* out_dev, hipStream_t stream) {
     VQAE_REQUIRE(w_dev && out_dev && n_out <= 32 && (dtype == VQAE_DT_BF16 || dtype == VQAE_DT_F16), VQAE_ERR_INVALID, "stem16_pack_weight");
     const int KS = (9 * cin + 15) / 16;
@@ -289,7 +290,6 @@ int stem16_pack_weight(const float* w_dev, int n_out, int cin, int dtype, void* 
     return VQAE_OK;
 }
 
-// in-stem: x (x_kind 0 NHWC f32 / 1 NCHW f32 / 2 uint8 NHWC + normalisation) -> y [B][H][W][c0] fp32
 int istem16(const void* x, int x_kind, const float* mean255, const float* inv_std255, const void* wf, const float* bias, int B,
             int H, int W, int c0, float* y, int dtype, hipStream_t stream) {
     if ((int64_t)B * H * W == 0) return VQAE_OK;
@@ -312,7 +312,6 @@ int istem16(const void* x, int x_kind, const float* mean255, const float* inv_st
     return VQAE_OK;
 }
 
-// out-stem: x [B][H][W][c] fp32 -> y (NCHW [B][3][H][W] if y_nchw else NHWC) fp32
 int ostem16(const float* x, const void* wf, const float* bias, int B, int H, int W, int c, float* y, int y_nchw, int dtype,
             hipStream_t stream) {
     if ((int64_t)B * H * W == 0) return VQAE_OK;

@@ -17,7 +17,7 @@
 //
 // Rounding points are those of conv_mfma.hip (= torch.autocast): conv operands and conv outputs RNE to the 16-bit
 // type, fp32 accumulation, fp32 scalar bias / ELU / scale / residual arithmetic, no FMA contraction.
-#include "common.h"
+#include "kernels.h"
 
 namespace {
 
@@ -521,10 +521,12 @@ int launch_t16_cw(const T16K& k, bool next, int c, int w, int64_t n_px, hipStrea
 
 namespace vqae {
 
+bool trunk16_channels(int c) { return c == 16 || c == 32 || c == 64 || c == 128 || c == 256; }
+
 // (C, grid width) pairs with a kernel: the trunk of cfg A / B (128 @ 32), cfg C (256 @ 32) and the levels above them
 bool trunk16_supported(int c, int h, int w, int dtype) {
-    static const bool off = getenv("VQAE_NO_TRUNK16") && atoi(getenv("VQAE_NO_TRUNK16"));
-    if (off || (dtype != VQAE_DT_BF16 && dtype != VQAE_DT_F16)) return false;
+    static const bool off = env_int("VQAE_NO_TRUNK16", 0) != 0;
+    if (off || !trunk16_channels(c) || (dtype != VQAE_DT_BF16 && dtype != VQAE_DT_F16)) return false;
     const bool cw = (c == 128 && w == 32) || (c == 256 && w == 32) || (c == 64 && w == 64) || (c == 128 && w == 64) ||
                     (c == 64 && w == 128) || (c == 32 && w == 128) || (c == 32 && w == 256) || (c == 16 && w == 128) || (c == 16 && w == 256);
     const int tw = (c >= 64 && c <= 128 && w >= 64) ? 32 : (w < 128 ? w : 128);       // T16Cfg::TW
@@ -534,7 +536,6 @@ bool trunk16_supported(int c, int h, int w, int dtype) {
 // + the ring's look-ahead past the last n-tile's fragments (trunk16_kernel reads, never uses, NB KiB beyond them)
 size_t trunk16_weight_bytes(int c, int taps) { return (size_t)(c < 32 ? 32 : c) * c * taps * 2 + (size_t)(NB_MAX + 1) * 1024; }
 
-// packed (vqae_conv_pack_weight_f32, rounded) fp32 weights [c][taps * c] on the device -> 16-bit fragment order
 int trunk16_pack_weight(const float* w_packed_dev, int c, int taps, int dtype, void* out_dev, hipStream_t stream) {
     VQAE_REQUIRE(c % 16 == 0 && (taps == 1 || taps == 9), VQAE_ERR_INVALID, "trunk16_pack_weight: c %d taps %d", c, taps);
     const int64_t n = (int64_t)(c < 32 ? 32 : c) * c * taps;
@@ -544,9 +545,9 @@ int trunk16_pack_weight(const float* w_packed_dev, int c, int taps, int dtype, v
     return VQAE_OK;
 }
 
-// chain-head conv1 (head16_kernel): x fp32 [M][c] -> t1 16-bit [M][c] (out32: fp32, not rounded after the activation); w1f from trunk16_pack_weight(.., taps = 1); M % 32 == 0
+// chain-head conv1 (head16_kernel)
 bool trunk16_head_supported(int c, int64_t m, int dtype) {
-    static const bool off = getenv("VQAE_NO_T16_HEAD") && atoi(getenv("VQAE_NO_T16_HEAD"));
+    static const bool off = env_int("VQAE_NO_T16_HEAD", 0) != 0;
     if (off || (dtype != VQAE_DT_BF16 && dtype != VQAE_DT_F16)) return false;
     return (c == 16 || c == 32 || c == 64 || c == 128) && m > 0 && m % 32 == 0 && m / 32 < (1ll << 31);   // C = 256: generic conv + cast
 }
@@ -580,7 +581,6 @@ int trunk16_head(const float* x, const void* w1f, float b1a, float b1b, float b2
 #undef VQAE_H16
 }
 
-// fp32 [n] (n % 4 == 0) -> 16-bit, RNE: t1 of a chain head produced by the generic conv1 launch
 int trunk16_round_pack(const float* src, void* dst, int64_t n, int dtype, hipStream_t stream) {
     VQAE_REQUIRE(n % 4 == 0, VQAE_ERR_INVALID, "trunk16_round_pack: n %% 4");
     const int64_t n4 = n / 4;
@@ -590,11 +590,11 @@ int trunk16_round_pack(const float* src, void* dst, int64_t n, int dtype, hipStr
     return VQAE_OK;
 }
 
-// One trunk Fixup block: t1 (16-bit) -> xio updated in place (+ t1_next, 16-bit, when w1nf != null).
 int trunk16_block(const void* t1, const void* w2f, const void* w3f, float act_a, float act_b, float t_scale, float t_b4,
-                  float* xio, const void* w1nf, float n_b1a, float n_b1b, float n_b2a, float n_b2b, void* t1_next,
-                  int batch, int h, int w, int c, int dtype, hipStream_t stream) {
+                  float* xio, const NextConv1& next, int batch, int h, int w, int c, int dtype, hipStream_t stream) {
     if (batch == 0) return VQAE_OK;
+    const void* w1nf = next.w1;
+    void* t1_next = next.t1_next;
     VQAE_REQUIRE(t1 && w2f && w3f && xio && (!w1nf || t1_next), VQAE_ERR_INVALID, "trunk16_block: null pointer");
     VQAE_REQUIRE(trunk16_supported(c, h, w, dtype), VQAE_ERR_UNSUPPORTED, "trunk16_block: C = %d, H = %d, W = %d, dtype %d", c, h, w, dtype);
     const int64_t M = (int64_t)batch * h * w;
@@ -602,7 +602,7 @@ int trunk16_block(const void* t1, const void* w2f, const void* w3f, float act_a,
     T16K k;
     k.t1 = t1; k.w2f = w2f; k.w3f = w3f; k.w1nf = w1nf; k.xio = xio; k.t1n = t1_next; k.H = h;
     k.act_a = act_a; k.act_b = act_b; k.t_scale = t_scale; k.t_b4 = t_b4;
-    k.n_b1a = n_b1a; k.n_b1b = n_b1b; k.n_b2a = n_b2a; k.n_b2b = n_b2b;
+    k.n_b1a = next.b1a; k.n_b1b = next.b1b; k.n_b2a = next.b2a; k.n_b2b = next.b2b;
     if (dtype == VQAE_DT_BF16) return launch_t16_cw<VQAE_DT_BF16>(k, w1nf != nullptr, c, w, M, stream);
     return launch_t16_cw<VQAE_DT_F16>(k, w1nf != nullptr, c, w, M, stream);
 }

@@ -17,7 +17,7 @@
 //            combines them for the ROWS output rows; results go to LDS as 16-bit (the conv input cast): S (skip), U (branch)
 //   convs    v_mfma_f32_32x32x16_{bf16,f16}, weights (fragment order, from L2) as the row operand: conv2 from U -> t2 (16-bit,
 //            over U) -> conv3 from t2 and skip_conv from S -> epilogue, fp32 store.
-#include "common.h"
+#include "kernels.h"
 
 namespace {
 
@@ -243,15 +243,15 @@ int launch_up16(const Up16K& k, int64_t n_tiles, hipStream_t stream) {
 
 namespace vqae {
 
-// C (= the block's input channels) in {16, 32, 64, 128}; low-resolution width a multiple of 16
+bool up16_channels(int c) { return c == 16 || c == 32 || c == 64 || c == 128; }
+
 bool up16_supported(int c, int h, int w, int dtype) {
     if (dtype != VQAE_DT_BF16 && dtype != VQAE_DT_F16) return false;
-    return (c == 16 || c == 32 || c == 64 || c == 128) && h >= 1 && w % 16 == 0;
+    return up16_channels(c) && h >= 1 && w % 16 == 0;
 }
 
-// x, t1: [B][H][W][c] fp32 -> y [B][2H][2W][c / 2] fp32; weights: down16_pack_weight([c][c]), ([c / 2][c]), ([c / 2][c])
 int up16_block(const float* x, const float* t1, const void* w2h, const void* w3h, const void* wskh, int B, int H, int W, int c,
-               float b3a, float b3b, float scale, float b4, float b1c, float b1d, int dtype, float* y, hipStream_t stream) {
+               const FixupScalars& s, int dtype, float* y, hipStream_t stream) {
     if (B == 0) return VQAE_OK;
     VQAE_REQUIRE(x && t1 && w2h && w3h && wskh && y, VQAE_ERR_INVALID, "up16_block: null pointer");
     VQAE_REQUIRE(up16_supported(c, H, W, dtype), VQAE_ERR_UNSUPPORTED, "up16_block: C = %d, %dx%d, dtype %d", c, H, W, dtype);
@@ -261,7 +261,7 @@ int up16_block(const float* x, const float* t1, const void* w2h, const void* w3h
     k.H = H; k.W = W;
     const int rows = c == 128 ? 2 : 4;
     k.tiles_x = 2 * W / 32; k.tiles_y = 2 * H / rows;
-    k.b3a = b3a; k.b3b = b3b; k.scale = scale; k.b4 = b4; k.b1c = b1c; k.b1d = b1d;
+    k.b3a = s.b3a; k.b3b = s.b3b; k.scale = s.scale; k.b4 = s.b4; k.b1c = s.b1c; k.b1d = s.b1d;
     const int64_t n_tiles = (int64_t)B * k.tiles_x * k.tiles_y;
     VQAE_REQUIRE(n_tiles < (1ll << 31) && 2 * H % rows == 0, VQAE_ERR_UNSUPPORTED, "up16_block: tiling");
 #define VQAE_U16(C_, R_) (dtype == VQAE_DT_BF16 ? launch_up16<C_, VQAE_DT_BF16, R_>(k, n_tiles, stream) : launch_up16<C_, VQAE_DT_F16, R_>(k, n_tiles, stream))

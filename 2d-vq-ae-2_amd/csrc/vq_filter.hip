@@ -22,7 +22,7 @@
 // replace), survivors appended to a (row, code) pair list in LDS; then 8 lanes per pair evaluate the exact distances (several
 // pairs per group in flight) and two rounds of 64-bit LDS atomic minima (distance bits << 32 | code) leave the best and the
 // second best pair of every row.
-#include "common.h"
+#include "kernels.h"
 
 namespace {
 
@@ -373,17 +373,15 @@ namespace vqae {
 static int vqf_kp(int K) { return (int)round_up(K, 128); }
 
 bool vq_filter_supported(int K, int D) {
-    static const bool off = getenv("VQAE_NO_VQ_FILTER") && atoi(getenv("VQAE_NO_VQ_FILTER"));
+    static const bool off = env_int("VQAE_NO_VQ_FILTER", 0) != 0;
     // measured (N = 262 144): D = 256, K = 1024: 4.14 -> 1.86 ms; D = 128, K = 256 with 128-row tiles (one 4-wave workgroup per CU):
     // 0.52 -> 0.48 ms; round 3, 64-row tiles (two workgroups per CU): 0.60 -> 0.46 ms on N(0, 1) data: taken for 128 channels too
-    static const bool no128 = getenv("VQAE_NO_VQ_FILTER_128") && atoi(getenv("VQAE_NO_VQ_FILTER_128"));
+    static const bool no128 = env_int("VQAE_NO_VQ_FILTER_128", 0) != 0;
     return !off && (D == 256 || (D == 128 && !no128)) && K >= 32 && K <= 32768;
 }
 
 size_t vq_filter_table_bytes(int K, int D) { return (size_t)vqf_kp(K) * (3 * D + 16) * 2; }
 
-// flags: 4 zeroed ints ([0] = flagged-row counter shared with tier 1 / tier 2).  After this call either idx32 / flag_list are
-// filled (flags[1] == 0) or nothing was done and flags[1] != 0 tells vq_tier1_kernel to run.
 int vq_filter_run(const float* z, const float* embed, int64_t N, int K, int D, float thr, int* idx32, int* flags, int* flag_list,
                   void* table, hipStream_t stream) {
     VQAE_REQUIRE(vq_filter_supported(K, D) && table, VQAE_ERR_UNSUPPORTED, "vq_filter: K = %d, D = %d", K, D);

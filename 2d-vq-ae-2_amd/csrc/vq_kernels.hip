@@ -16,7 +16,7 @@
 //           (or exact ties) are re-evaluated with the reference's bit recipe -- per-term
 //           RN_f32(d^4) (via fp64), sequential fp32 adds, RN_f32(agg^(1/4)) finish, lowest index on
 //           equal finished values (ATen cdist + argmin semantics) -- one wave per flagged row.
-#include "common.h"
+#include "kernels.h"
 
 namespace {
 
@@ -389,11 +389,6 @@ inline VqWorkspace carve(void* ws, int64_t N, int K, int D) {
 }  // namespace
 
 namespace vqae {
-bool vq_filter_supported(int K, int D);
-size_t vq_filter_table_bytes(int K, int D);
-int vq_filter_run(const float* z, const float* embed, int64_t N, int K, int D, float thr, int* idx32, int* flags, int* flag_list,
-                  void* table, hipStream_t stream);
-// shared with the fused projected quantiser (vq_proj.hip)
 int vq_tier2_run(const float* z, const float* embed, int K, int D, int* idx32, const int* flag_count, const int* flag_list,
                  hipStream_t stream) {
     vq_tier2_kernel<4><<<256, 256, 0, stream>>>(z, embed, K, D, idx32, flag_count, flag_list);
@@ -401,7 +396,6 @@ int vq_tier2_run(const float* z, const float* embed, int K, int D, int* idx32, c
     return VQAE_OK;
 }
 
-// *loss = commitment * mean((z - embed[idx])^2) (vq.py:143); partials: >= 1024 doubles of scratch
 int vq_loss_from_idx(const float* z, const float* embed, const int* idx32, int64_t N, int D, float commitment, double* partials,
                      float* loss, hipStream_t stream) {
     const int64_t total4 = N * (D / 4);

@@ -21,15 +21,7 @@
 //
 // 16-bit autocast modes (DT): proj_in / proj_out are convolutions, so their operands and results are rounded to the
 // 16-bit type exactly as vqae_conv2d_f32 does (weights / biases arrive pre-rounded); the distance, q and the loss stay fp32.
-#include "common.h"
-
-namespace vqae {
-int vq_tier2_run(const float* z, const float* embed, int K, int D, int* idx32, const int* flag_count, const int* flag_list,
-                 hipStream_t stream);
-int vq_loss_from_idx(const float* z, const float* embed, const int* idx32, int64_t N, int D, float commitment, double* partials,
-                     float* loss, hipStream_t stream);
-int vq_write_idx(const int* idx32, int64_t N, void* out, int idx_dtype, hipStream_t stream);
-}  // namespace vqae
+#include "kernels.h"
 
 namespace {
 
@@ -536,7 +528,7 @@ void vq_proj16_kernel(const VqProjK p, const int n_units, const int use_filter) 
 template <int C, int DT>
 int launch_vq_proj16(const VqProjK& k, hipStream_t stream) {
     const int n_units = (int)vqae::ceil_div(k.N, 16);
-    static const bool nofilter = getenv("VQAE_VQ16_NOFILTER") && atoi(getenv("VQAE_VQ16_NOFILTER"));
+    static const bool nofilter = vqae::env_int("VQAE_VQ16_NOFILTER", 0) != 0;
     const int use_filter = !nofilter && !k.margin && k.K <= 256 && (k.K & 15) == 0;   // the margin output wants the true second best
     // 4 waves per SIMD: 512-thread workgroups, 2 per CU, without the register prefetch of the next step's rows
     constexpr int nwv = 8;
@@ -621,7 +613,7 @@ extern "C" int vqae_vq_projected_f32(const float* x, const float* wt_in, const f
     k.margin = margin; k.N = N; k.C = C; k.K = K;
     k.thr = (4.0f * (float)PD + 16.0f) * 5.9604645e-8f;           // as vqae_vq_forward_f32
     VQAE_HIP_CHECK(hipMemsetAsync(k.flag_count, 0, 16, stream));
-    static const bool v1 = getenv("VQAE_VQ_PROJ_V1") && atoi(getenv("VQAE_VQ_PROJ_V1"));
+    static const bool v1 = vqae::env_int("VQAE_VQ_PROJ_V1", 0) != 0;
     int rc;
     if (!v1 && C == 128 && K <= 1024)                                // the reference default (conf/model/vq_ae.yaml: 8 * 2^4 channels)
         rc = dtype == VQAE_DT_BF16 ? launch_vq_proj16<128, VQAE_DT_BF16>(k, stream)
