@@ -102,6 +102,10 @@ SYMBOLS = {
     "vqae_label_maxpool_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vqae_stitch_tiles": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int,
                                   c_void_p]),
+    "vqae_unstitch_tiles": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int,
+                                    c_void_p]),
+    "vqae_pixels_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, POINTER(c_float), POINTER(c_float), c_void_p,
+                               c_int, c_int, c_void_p]),
     "vqae_create": (c_int, [POINTER(Config), POINTER(Tensor), c_int, POINTER(c_void_p)]),
     "vqae_destroy": (None, [c_void_p]),
     "vqae_reserve": (c_int, [c_void_p, c_int, c_int, c_int]),
@@ -113,6 +117,8 @@ SYMBOLS = {
     "vqae_encode_features": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vqae_decode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vqae_decode_indices": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "vqae_decode_indices_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
+                                       c_void_p]),
     "vqae_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
                              c_void_p]),
     "vqae_block_count": (c_int, [c_void_p, c_int]),

@@ -118,6 +118,7 @@ struct Block : vqae::FixupScalars {
 // CAMELYON16 normalisation (conf/transforms/camelyon16_transforms.yaml:15-23), x255
 const float kMean255[3] = {0.7279f * 255.0f, 0.5955f * 255.0f, 0.7762f * 255.0f};
 const float kInv255[3] = {1.0f / (0.2419f * 255.0f), 1.0f / (0.3083f * 255.0f), 1.0f / (0.1741f * 255.0f)};
+const float kStd255[3] = {0.2419f * 255.0f, 0.3083f * 255.0f, 0.1741f * 255.0f};      // the way back (vqae_decode_indices_u8)
 
 }  // namespace
 
@@ -780,13 +781,14 @@ int run_vq(vqae_handle* h, int B, int zh, int zw, void* idx, int idx_dtype, floa
     return VQAE_OK;
 }
 
-// post_enc blocks + up blocks + out_stem: q in buf[0] -> out (model.py:278-291)
+// post_enc blocks + up blocks + out_stem: q in buf[0] -> out (model.py:278-291); out == nullptr: into the workspace buf[1]
 int run_decoder_convs(vqae_handle* h, int B, int qh, int qw, int layout, float* out, hipStream_t st) {
     const int dt = h->cfg.compute_dtype;
     int H = qh, W = qw, rc;
     h->t1_ready = false;
     for (size_t i = 0; i < h->dec.size(); ++i)
         if ((rc = run_block(h, h->dec[i], i + 1 < h->dec.size() ? &h->dec[i + 1] : nullptr, B, H, W, st))) return rc;
+    if (!out) out = h->buf[1];                                     // (the blocks swap the buffers: only now is it known which is free)
     if (h->ostem_wh && vqae::stem16_supported(h->cfg.stem, H, W, dt))
         return vqae::ostem16(h->buf[0], h->ostem_wh, h->ostem_b, B, H, W, h->cfg.stem, out, layout == VQAE_LAYOUT_NCHW ? 1 : 0, dt, st);
     return vqae::conv3x3_direct(h->buf[0], 0, nullptr, nullptr, h->ostem_w, h->ostem_b, B, H, W, h->cfg.stem,
@@ -991,14 +993,9 @@ extern "C" int vqae_decode(vqae_handle* h, const float* q, int B, int qh, int qw
     return run_decoder_convs(h, B, qh, qw, layout, out, st);
 }
 
-extern "C" int vqae_decode_indices(vqae_handle* h, const void* idx, int idx_dtype, int B, int qh, int qw, int layout,
-                                   float* out, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    VQAE_REQUIRE(h && idx && out, VQAE_ERR_INVALID, "vqae_decode_indices: null pointer");
-    VQAE_REQUIRE(h->has_decoder && h->embed, VQAE_ERR_INVALID, "vqae_decode_indices: handle needs decoder.* tensors and a codebook");
-    VQAE_REQUIRE(B >= 0 && qh >= 1 && qw >= 1, VQAE_ERR_INVALID, "vqae_decode_indices: bad shape");
-    if (int rcd = check_device(h)) return rcd;
-    if (B == 0) return VQAE_OK;
+// idx -> the decoder's output: `out` in `layout`, or (out == nullptr) NHWC in the workspace buf[1]
+static int decode_indices_impl(vqae_handle* h, const void* idx, int idx_dtype, int B, int qh, int qw, int layout, float* out,
+                               hipStream_t st) {
     int rc;
     if ((rc = ensure_workspace(h, B, qh << h->cfg.n_down, qw << h->cfg.n_down))) return rc;
     const int64_t rows = (int64_t)B * qh * qw;
@@ -1010,6 +1007,34 @@ extern "C" int vqae_decode_indices(vqae_handle* h, const void* idx, int idx_dtyp
         if ((rc = vqae_embed_code_f32(idx, idx_dtype, h->embed, rows, h->K, h->D, h->buf[0], st))) return rc;
     }
     return run_decoder_convs(h, B, qh, qw, layout, out, st);
+}
+
+extern "C" int vqae_decode_indices(vqae_handle* h, const void* idx, int idx_dtype, int B, int qh, int qw, int layout,
+                                   float* out, void* stream) {
+    VQAE_REQUIRE(h && idx && out, VQAE_ERR_INVALID, "vqae_decode_indices: null pointer");
+    VQAE_REQUIRE(h->has_decoder && h->embed, VQAE_ERR_INVALID, "vqae_decode_indices: handle needs decoder.* tensors and a codebook");
+    VQAE_REQUIRE(B >= 0 && qh >= 1 && qw >= 1, VQAE_ERR_INVALID, "vqae_decode_indices: bad shape");
+    if (int rcd = check_device(h)) return rcd;
+    if (B == 0) return VQAE_OK;
+    return decode_indices_impl(h, idx, idx_dtype, B, qh, qw, layout, out, (hipStream_t)stream);
+}
+
+extern "C" int vqae_decode_indices_u8(vqae_handle* h, const void* idx, int idx_dtype, int B, int qh, int qw, const int32_t* rc_dev,
+                                      uint8_t* canvas, int canvas_h, int canvas_w, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    VQAE_REQUIRE(h && idx && canvas, VQAE_ERR_INVALID, "vqae_decode_indices_u8: null pointer");
+    VQAE_REQUIRE(h->has_decoder && h->embed, VQAE_ERR_INVALID, "vqae_decode_indices_u8: handle needs decoder.* tensors and a codebook");
+    VQAE_REQUIRE(B >= 0 && qh >= 1 && qw >= 1, VQAE_ERR_INVALID, "vqae_decode_indices_u8: bad shape");
+    const int H = qh << h->cfg.n_down, W = qw << h->cfg.n_down;
+    if (rc_dev)
+        VQAE_REQUIRE(canvas_h >= H && canvas_w >= W, VQAE_ERR_INVALID, "vqae_decode_indices_u8: canvas %d x %d is smaller than one %d x %d tile",
+                     canvas_h, canvas_w, H, W);
+    else
+        VQAE_REQUIRE(canvas_h == 0 && canvas_w == 0, VQAE_ERR_INVALID, "vqae_decode_indices_u8: canvas sizes given for a dense destination");
+    if (int rcd = check_device(h)) return rcd;
+    if (B == 0) return VQAE_OK;
+    if (int rc = decode_indices_impl(h, idx, idx_dtype, B, qh, qw, VQAE_LAYOUT_NHWC, nullptr, st)) return rc;
+    return vqae::pixels_u8(h->buf[1], VQAE_LAYOUT_NHWC, B, H, W, rc_dev, kMean255, kStd255, canvas, canvas_h, canvas_w, st);
 }
 
 extern "C" int vqae_block_count(const vqae_handle* h, int side) {

@@ -159,6 +159,13 @@ int conv3x3_direct(const void* x, int x_kind, const float* mean255, const float*
                    const float* bias, int B, int H, int W, int cin, int cout, float* y, int y_nchw, int dt,
                    hipStream_t stream);
 
+// ---- pixels.hip --------------------------------------------------------------------------------
+// vqae_unstitch_tiles / vqae_pixels_u8 (include/vqae_hip.h) on a hipStream_t
+int unstitch_tiles(const void* grid, int grid_dtype, const int32_t* rc, int n_tiles, int th, int tw, void* tiles,
+                   int idx_dtype, int gh, int gw, hipStream_t stream);
+int pixels_u8(const float* x, int layout, int B, int H, int W, const int32_t* rc, const float* mean255, const float* std255,
+              uint8_t* out, int canvas_h, int canvas_w, hipStream_t stream);
+
 // ---- vq_filter.hip / vq_kernels.hip ------------------------------------------------------------
 bool vq_filter_supported(int K, int D);
 size_t vq_filter_table_bytes(int K, int D);

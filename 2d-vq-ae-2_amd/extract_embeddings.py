@@ -21,8 +21,7 @@ from . import dist as vdist
 from . import hdf5
 from . import ops
 
-MEAN = (0.7279, 0.5955, 0.7762)      # conf/transforms/camelyon16_transforms.yaml:15-23
-STD = (0.2419, 0.3083, 0.1741)
+MEAN, STD = ops.MEAN, ops.STD        # conf/transforms/camelyon16_transforms.yaml:15-23
 
 
 class CheckpointNotFoundError(ValueError):       # extract_embeddings.py:35-36

@@ -160,6 +160,32 @@ class NativeVQAE:
                                             ops._stream()))
         return out
 
+    def decode_indices_u8(self, idx, rc=None, canvas=None):
+        """idx [B,h,w] -> displayable pixels, de-normalised with the handle's ingest constants, rounded and clamped on the
+        device: uint8 [B,H,W,3], or with rc [B, 2] (int32 patch positions) + canvas [ch, cw, 3] uint8 each tile pasted into
+        the canvas at pixel (rc[t, 0] * H, rc[t, 1] * W) and the canvas returned."""
+        ops._need_gpu(idx, rc, canvas)
+        idx = idx.contiguous()
+        B, qh, qw = idx.shape
+        H, W = qh * self.factor, qw * self.factor
+        if rc is None:
+            assert canvas is None, "decode_indices_u8: a canvas needs rc"
+            out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=idx.device)
+            if B == 0:                                                 # (an empty tensor has no pointer to hand over)
+                return out
+            L.check(L.lib().vqae_decode_indices_u8(self._h, ops._p(idx), ops.idx_code(idx.dtype), B, qh, qw, None,
+                                                   ops._p(out), 0, 0, ops._stream()))
+            return out
+        assert canvas is not None and canvas.dtype == torch.uint8 and canvas.dim() == 3 and canvas.shape[2] == 3 and \
+            canvas.is_contiguous(), "decode_indices_u8: canvas must be a contiguous uint8 [h, w, 3] tensor"
+        rc = rc.to(torch.int32).contiguous()
+        assert tuple(rc.shape) == (B, 2), rc.shape
+        if B == 0:
+            return canvas
+        L.check(L.lib().vqae_decode_indices_u8(self._h, ops._p(idx), ops.idx_code(idx.dtype), B, qh, qw, ops._p(rc),
+                                               ops._p(canvas), canvas.shape[0], canvas.shape[1], ops._stream()))
+        return canvas
+
     def forward(self, x, layout="NCHW", idx_dtype=torch.int64, want_idx=True):
         """VQAE.forward: x -> (out, idx | None, loss)."""
         ops._need_gpu(x)

@@ -11,6 +11,10 @@ if hasattr(torch, "uint16"):
     _IDX_DTYPES[torch.uint16] = L.IDX_U16
 
 
+MEAN = (0.7279, 0.5955, 0.7762)      # conf/transforms/camelyon16_transforms.yaml:15-23
+STD = (0.2419, 0.3083, 0.1741)
+
+
 def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -278,3 +282,58 @@ def stitch_tiles(tiles, rc, grid):
     L.check(L.lib().vqae_stitch_tiles(_p(tiles), idx_code(tiles.dtype), _p(rc), n, th, tw, _p(grid),
                                       idx_code(grid.dtype), grid.shape[0], grid.shape[1], _stream()))
     return grid
+
+
+def unstitch_tiles(grid, rc, th, tw, dtype=torch.int64, out=None):
+    """The inverse of stitch_tiles: grid [gh, gw] (any index dtype) cut into tiles [n, th, tw] of `dtype` at the patch positions
+    rc [n, 2] (int32).  Positions are the caller's to validate: elements outside the grid are not written (they keep what
+    `out`, a contiguous [n, th, tw] tensor to fill, held; without `out` they are whatever the allocation held)."""
+    _need_gpu(grid, rc, out)
+    grid = grid.contiguous()
+    rc = rc.to(torch.int32).contiguous()
+    n = rc.shape[0]
+    if out is not None:
+        assert tuple(out.shape) == (n, th, tw) and out.is_contiguous(), out.shape
+        tiles, dtype = out, out.dtype
+    else:
+        tiles = torch.empty((n, th, tw), dtype=dtype, device=grid.device)
+    L.check(L.lib().vqae_unstitch_tiles(_p(grid), idx_code(grid.dtype), _p(rc), n, th, tw, _p(tiles), idx_code(dtype),
+                                        grid.shape[0], grid.shape[1], _stream()))
+    return tiles
+
+
+def _f32x3(values, scale):
+    """host float[3] of fp32(v) * fp32(scale), the product formed in fp32 as the kernels' own constants are"""
+    import numpy as np
+    return (ctypes.c_float * 3)(*[float(np.float32(v) * np.float32(scale)) for v in values])
+
+
+def pixels_u8(x, layout="NCHW", rc=None, canvas=None, mean=MEAN, std=STD):
+    """fp32 reconstruction x ([B,3,H,W], or [B,H,W,3] with layout="NHWC") -> uint8 NHWC pixels
+    clamp(rint(x * std * 255 + mean * 255), 0, 255) (one fma, round-to-nearest-even, NaN -> 0): the inverse of the ingest
+    Normalize.  rc=None -> a dense [B,H,W,3] tensor; rc [B, 2] (int32) + canvas [ch, cw, 3] uint8 -> tile t pasted in place at
+    pixel (rc[t, 0] * H, rc[t, 1] * W), the canvas returned.  mean / std: 3 floats, or None for 0 / 1."""
+    _need_gpu(x, rc, canvas)
+    assert layout in ("NCHW", "NHWC"), layout
+    x = x.contiguous()
+    assert x.dtype == torch.float32 and x.dim() == 4, (x.dtype, x.shape)
+    if layout == "NCHW":
+        B, C, H, W = x.shape
+    else:
+        B, H, W, C = x.shape
+    assert C == 3, x.shape
+    m = _f32x3(mean, 255.0) if mean is not None else None
+    s = _f32x3(std, 255.0) if std is not None else None
+    lay = L.LAYOUT_NCHW if layout == "NCHW" else L.LAYOUT_NHWC
+    if rc is None:
+        assert canvas is None, "pixels_u8: a canvas needs rc"
+        out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=x.device)
+        L.check(L.lib().vqae_pixels_u8(_p(x), lay, B, H, W, None, m, s, _p(out), 0, 0, _stream()))
+        return out
+    assert canvas is not None and canvas.dtype == torch.uint8 and canvas.dim() == 3 and canvas.shape[2] == 3 and \
+        canvas.is_contiguous(), "pixels_u8: canvas must be a contiguous uint8 [h, w, 3] tensor"
+    rc = rc.to(torch.int32).contiguous()
+    assert tuple(rc.shape) == (B, 2), rc.shape
+    L.check(L.lib().vqae_pixels_u8(_p(x), lay, B, H, W, _p(rc), m, s, _p(canvas), canvas.shape[0], canvas.shape[1],
+                                   _stream()))
+    return canvas

@@ -235,6 +235,28 @@ int vqae_label_maxpool_u8(const uint8_t* labels_dev, int batch, int h, int w, in
 int vqae_stitch_tiles(const void* tiles_dev, int idx_dtype, const int32_t* rc_dev, int n_tiles, int th, int tw,
                       void* grid_dev, int grid_dtype, int grid_h, int grid_w, void* stream);
 
+/* Cut a stored slide grid back into code tiles: the exact inverse of vqae_stitch_tiles, i.e. of the grid layout of
+ * get_encodings (scripts/extract_embeddings/extract_embeddings.py:77-84):
+ * tiles[t][y][x] = grid[(r*th + y) * grid_w + c*tw + x] for (r, c) = rc[t].
+ * grid grid_dtype in (as stored: uint8 / uint16 / wider), tiles idx_dtype out (VQAE_IDX_*, every pairing vqae_stitch_tiles
+ * takes; widening is exact).  An element whose grid position lies outside the grid is neither read nor written (the tile
+ * keeps what it held): the caller validates positions on the host. */
+int vqae_unstitch_tiles(const void* grid_dev, int grid_dtype, const int32_t* rc_dev, int n_tiles, int th, int tw,
+                        void* tiles_dev, int idx_dtype, int grid_h, int grid_w, void* stream);
+
+/* fp32 reconstruction -> uint8 NHWC pixels: the inverse of the Normalize transform vqae_conv3x3_direct_f32 applies on ingest
+ * (albumentations Normalize, camelyon16_transforms.yaml:15-23), per channel c
+ *   u = clamp(rintf(fmaf(x, std255[c], mean255[c])), 0, 255)     one fused multiply-add, round-to-nearest-even, NaN -> 0.
+ *   x_dev      [B][H][W][3] (VQAE_LAYOUT_NHWC) or [B][3][H][W] (VQAE_LAYOUT_NCHW) fp32
+ *   mean255, std255  host arrays of 3 (NULL -> 0 / 1)
+ *   rc_dev == NULL: out_dev is a dense [B][H][W][3] batch and canvas_h = canvas_w = 0;
+ *   otherwise tile t is pasted into the canvas out_dev [canvas_h][canvas_w][3] at pixel (rc[t].r * H, rc[t].c * W); a tile
+ *   that does not lie wholly inside the canvas is skipped (no access outside it), the rest of the canvas is not written.
+ * Errors: null pointers / bad layout / canvas sizes with a dense destination / a canvas smaller than one tile ->
+ * VQAE_ERR_INVALID. */
+int vqae_pixels_u8(const float* x_dev, int layout, int batch, int h, int w, const int32_t* rc_dev, const float* mean255,
+                   const float* std255, uint8_t* out_dev, int canvas_h, int canvas_w, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * 3. Whole-model handle -- replaces Encoder.forward (vq_ae/model.py:189-217), Decoder.forward
  *    (:274-291) and VQAE.forward (:41-48) for the single-VQ-level Fixup model that every shipped
@@ -291,6 +313,17 @@ int vqae_decode(vqae_handle* h, const float* q_dev, int batch, int q_h, int q_w,
 /* Decode from code indices: embed_code (+ proj_out) then Decoder.forward. */
 int vqae_decode_indices(vqae_handle* h, const void* idx_dev, int idx_dtype, int batch, int q_h, int q_w, int layout,
                         float* out_dev, void* stream);
+/* The same, down to displayable pixels: embed_code (vq.py:44-45; + proj_out when the model projects) -> Decoder.forward
+ * (vq_ae/model.py:274-291) with the out-stem writing into the handle's own NHWC fp32 workspace -> vqae_pixels_u8 with the
+ * constants of the handle's ingest normalisation (mean255 = MEAN * 255, std255 = STD * 255, formed in fp32): no fp32 tensor
+ * of the caller's and no layout transpose.  idx [B][q_h][q_w] of idx_dtype; tile size H x W = q_h, q_w * 2^n_down.
+ *   rc_dev == NULL: canvas_dev is a dense uint8 [B][H][W][3] batch and canvas_h = canvas_w = 0;
+ *   otherwise tile t lands in canvas_dev [canvas_h][canvas_w][3] at pixel (rc[t].r * H, rc[t].c * W), i.e. rc are the patch
+ *   positions of get_encodings (scripts/extract_embeddings/extract_embeddings.py:77-84) relative to the canvas.
+ * Preconditions and errors as vqae_decode_indices; canvas sizes with a dense destination, or a canvas smaller than one
+ * tile -> VQAE_ERR_INVALID.  batch == 0 -> VQAE_OK. */
+int vqae_decode_indices_u8(vqae_handle* h, const void* idx_dev, int idx_dtype, int batch, int q_h, int q_w,
+                           const int32_t* rc_dev, uint8_t* canvas_dev, int canvas_h, int canvas_w, void* stream);
 /* VQAE.forward: out [B,3,H,W], idx (optional), loss (optional). */
 int vqae_forward(vqae_handle* h, const float* x_dev, int batch, int in_h, int in_w, int layout, float* out_dev,
                  void* idx_dev, int idx_dtype, float* loss_dev, void* stream);
