@@ -11,5 +11,5 @@ validation driver), reconstruct.py (stored code grids -> uint8 slide pixels), di
 """
 from . import _lib, ops, reconstruct, spec  # noqa: F401
 from .native import NativeVQAE  # noqa: F401
-from .reconstruct import reconstruct_hdf5, reconstruct_region, reconstruct_slide  # noqa: F401
+from .reconstruct import reconstruct_hdf5, reconstruct_overview, reconstruct_region, reconstruct_slide  # noqa: F401
 from .spec import SPECS, VQAESpec  # noqa: F401

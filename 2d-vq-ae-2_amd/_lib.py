@@ -21,6 +21,7 @@ ACT_NONE, ACT_ELU, ACT_SILU = 0, 1, 2
 DW_SAME, DW_DOWN, DW_UP = 0, 1, 2
 BLOCK_FIXUP, BLOCK_MBCONV = 0, 1
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
+MAX_PIXEL_LEVEL = 6                     # VQAE_MAX_PIXEL_LEVEL: overview levels 0 .. 6 (vqae_pixels_u8_level)
 # VQAE_METRIC_*: columns of the vqae_recon_metrics_f32 output rows
 METRIC_NAMES = ("mse", "huber", "psnr", "ssim", "pred_min", "pred_max", "target_min", "target_max")
 DTYPES = {"f32": DT_F32, "fp32": DT_F32, "float32": DT_F32, "bf16": DT_BF16, "bfloat16": DT_BF16,
@@ -106,6 +107,8 @@ SYMBOLS = {
                                     c_void_p]),
     "vqae_pixels_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, POINTER(c_float), POINTER(c_float), c_void_p,
                                c_int, c_int, c_void_p]),
+    "vqae_pixels_u8_level": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, POINTER(c_float), POINTER(c_float),
+                                     c_void_p, c_int, c_int, c_void_p]),
     "vqae_create": (c_int, [POINTER(Config), POINTER(Tensor), c_int, POINTER(c_void_p)]),
     "vqae_destroy": (None, [c_void_p]),
     "vqae_reserve": (c_int, [c_void_p, c_int, c_int, c_int]),
@@ -119,6 +122,8 @@ SYMBOLS = {
     "vqae_decode_indices": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vqae_decode_indices_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                                        c_void_p]),
+    "vqae_decode_indices_u8_levels": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, POINTER(c_int),
+                                              POINTER(c_void_p), POINTER(c_int), POINTER(c_int), c_void_p]),
     "vqae_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
                              c_void_p]),
     "vqae_block_count": (c_int, [c_void_p, c_int]),

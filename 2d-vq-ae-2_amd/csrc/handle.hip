@@ -1037,6 +1037,32 @@ extern "C" int vqae_decode_indices_u8(vqae_handle* h, const void* idx, int idx_d
     return vqae::pixels_u8(h->buf[1], VQAE_LAYOUT_NHWC, B, H, W, rc_dev, kMean255, kStd255, canvas, canvas_h, canvas_w, st);
 }
 
+extern "C" int vqae_decode_indices_u8_levels(vqae_handle* h, const void* idx, int idx_dtype, int B, int qh, int qw,
+                                             const int32_t* rc_dev, int n_levels, const int* levels, uint8_t* const* canvases,
+                                             const int* canvas_h, const int* canvas_w, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const char* who = "vqae_decode_indices_u8_levels";
+    VQAE_REQUIRE(h && idx, VQAE_ERR_INVALID, "%s: null pointer", who);
+    VQAE_REQUIRE(h->has_decoder && h->embed, VQAE_ERR_INVALID, "%s: handle needs decoder.* tensors and a codebook", who);
+    VQAE_REQUIRE(B >= 0 && qh >= 1 && qw >= 1, VQAE_ERR_INVALID, "%s: bad shape", who);
+    VQAE_REQUIRE(n_levels >= 1 && n_levels <= VQAE_MAX_PIXEL_LEVEL + 1, VQAE_ERR_INVALID, "%s: %d levels", who, n_levels);
+    VQAE_REQUIRE(levels && canvases && canvas_h && canvas_w, VQAE_ERR_INVALID, "%s: null array", who);
+    const int H = qh << h->cfg.n_down, W = qw << h->cfg.n_down;
+    for (int i = 0; i < n_levels; ++i) {                             // all of them before anything is launched
+        if (int e = vqae::pixels_u8_level_check(who, H, W, levels[i], rc_dev != nullptr, canvas_h[i], canvas_w[i])) return e;
+        VQAE_REQUIRE(canvases[i], VQAE_ERR_INVALID, "%s: null canvas %d", who, i);
+        for (int k = 0; k < i; ++k) VQAE_REQUIRE(levels[k] != levels[i], VQAE_ERR_INVALID, "%s: level %d given twice", who, levels[i]);
+    }
+    if (int rcd = check_device(h)) return rcd;
+    if (B == 0) return VQAE_OK;
+    if (int rc = decode_indices_impl(h, idx, idx_dtype, B, qh, qw, VQAE_LAYOUT_NHWC, nullptr, st)) return rc;
+    for (int i = 0; i < n_levels; ++i)
+        if (int rc = vqae::pixels_u8_level(h->buf[1], VQAE_LAYOUT_NHWC, B, H, W, levels[i], rc_dev, kMean255, kStd255, canvases[i],
+                                           canvas_h[i], canvas_w[i], st))
+            return rc;
+    return VQAE_OK;
+}
+
 extern "C" int vqae_block_count(const vqae_handle* h, int side) {
     if (!h) return 0;
     return (int)(side == 0 ? h->enc.size() : h->dec.size());

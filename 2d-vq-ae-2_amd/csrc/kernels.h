@@ -165,6 +165,11 @@ int unstitch_tiles(const void* grid, int grid_dtype, const int32_t* rc, int n_ti
                    int idx_dtype, int gh, int gw, hipStream_t stream);
 int pixels_u8(const float* x, int layout, int B, int H, int W, const int32_t* rc, const float* mean255, const float* std255,
               uint8_t* out, int canvas_h, int canvas_w, hipStream_t stream);
+// vqae_pixels_u8_level; its argument checks on their own (who: the caller's name for the message), so that a caller with
+// several levels can refuse all of them before it launches anything
+int pixels_u8_level_check(const char* who, int H, int W, int level, bool canvas, int canvas_h, int canvas_w);
+int pixels_u8_level(const float* x, int layout, int B, int H, int W, int level, const int32_t* rc, const float* mean255,
+                    const float* std255, uint8_t* out, int canvas_h, int canvas_w, hipStream_t stream);
 
 // ---- vq_filter.hip / vq_kernels.hip ------------------------------------------------------------
 bool vq_filter_supported(int K, int D);

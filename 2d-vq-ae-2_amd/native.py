@@ -160,31 +160,47 @@ class NativeVQAE:
                                             ops._stream()))
         return out
 
-    def decode_indices_u8(self, idx, rc=None, canvas=None):
+    def decode_indices_u8(self, idx, rc=None, canvas=None, level=0):
         """idx [B,h,w] -> displayable pixels, de-normalised with the handle's ingest constants, rounded and clamped on the
         device: uint8 [B,H,W,3], or with rc [B, 2] (int32 patch positions) + canvas [ch, cw, 3] uint8 each tile pasted into
-        the canvas at pixel (rc[t, 0] * H, rc[t, 1] * W) and the canvas returned."""
-        ops._need_gpu(idx, rc, canvas)
+        the canvas at pixel (rc[t, 0] * H, rc[t, 1] * W) and the canvas returned.
+        level L (0 .. 6, f = 2**L dividing H and W): the overview at 1/f scale, every pixel the integer mean (rounding half
+        up) of an f x f block of the level-0 pixels (ops.pixels_u8): uint8 [B,H/f,W/f,3], or the tile pasted at pixel
+        (rc[t, 0] * H/f, rc[t, 1] * W/f) of a canvas given in level-L pixels.  A sequence of distinct levels takes a matching
+        sequence of canvases (None: dense outputs) and returns a tuple, all from ONE decode."""
+        ops._need_gpu(idx, rc, *(canvas if isinstance(canvas, (tuple, list)) else (canvas,)))
         idx = idx.contiguous()
         B, qh, qw = idx.shape
         H, W = qh * self.factor, qw * self.factor
+        many = not isinstance(level, (int, np.integer))
+        levels = [int(v) for v in level] if many else [int(level)]
         if rc is None:
             assert canvas is None, "decode_indices_u8: a canvas needs rc"
-            out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=idx.device)
-            if B == 0:                                                 # (an empty tensor has no pointer to hand over)
-                return out
-            L.check(L.lib().vqae_decode_indices_u8(self._h, ops._p(idx), ops.idx_code(idx.dtype), B, qh, qw, None,
-                                                   ops._p(out), 0, 0, ops._stream()))
-            return out
-        assert canvas is not None and canvas.dtype == torch.uint8 and canvas.dim() == 3 and canvas.shape[2] == 3 and \
-            canvas.is_contiguous(), "decode_indices_u8: canvas must be a contiguous uint8 [h, w, 3] tensor"
-        rc = rc.to(torch.int32).contiguous()
-        assert tuple(rc.shape) == (B, 2), rc.shape
-        if B == 0:
-            return canvas
-        L.check(L.lib().vqae_decode_indices_u8(self._h, ops._p(idx), ops.idx_code(idx.dtype), B, qh, qw, ops._p(rc),
-                                               ops._p(canvas), canvas.shape[0], canvas.shape[1], ops._stream()))
-        return canvas
+            # (a shape for any level; the library judges the levels)
+            outs = [torch.empty((B, H >> min(max(v, 0), 31), W >> min(max(v, 0), 31), 3), dtype=torch.uint8, device=idx.device)
+                    for v in levels]
+            sizes = [(0, 0)] * len(levels)
+        else:
+            outs = list(canvas) if many else [canvas]
+            assert len(outs) == len(levels), "decode_indices_u8: one canvas per level"
+            for c in outs:
+                assert c is not None and c.dtype == torch.uint8 and c.dim() == 3 and c.shape[2] == 3 and c.is_contiguous(), \
+                    "decode_indices_u8: canvas must be a contiguous uint8 [h, w, 3] tensor"
+            sizes = [(c.shape[0], c.shape[1]) for c in outs]
+            rc = rc.to(torch.int32).contiguous()
+            assert tuple(rc.shape) == (B, 2), rc.shape
+        if not many and levels[0] == 0:
+            if B:                                                      # (an empty tensor has no pointer to hand over)
+                L.check(L.lib().vqae_decode_indices_u8(self._h, ops._p(idx), ops.idx_code(idx.dtype), B, qh, qw, ops._p(rc),
+                                                       ops._p(outs[0]), sizes[0][0], sizes[0][1], ops._stream()))
+            return outs[0]
+        n = len(levels)
+        if B:                                                          # (as above)
+            L.check(L.lib().vqae_decode_indices_u8_levels(
+                self._h, ops._p(idx), ops.idx_code(idx.dtype), B, qh, qw, ops._p(rc), n, (ctypes.c_int * n)(*levels),
+                (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs]), (ctypes.c_int * n)(*[s[0] for s in sizes]),
+                (ctypes.c_int * n)(*[s[1] for s in sizes]), ops._stream()))
+        return tuple(outs) if many else outs[0]
 
     def forward(self, x, layout="NCHW", idx_dtype=torch.int64, want_idx=True):
         """VQAE.forward: x -> (out, idx | None, loss)."""

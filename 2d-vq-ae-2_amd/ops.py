@@ -308,11 +308,14 @@ def _f32x3(values, scale):
     return (ctypes.c_float * 3)(*[float(np.float32(v) * np.float32(scale)) for v in values])
 
 
-def pixels_u8(x, layout="NCHW", rc=None, canvas=None, mean=MEAN, std=STD):
+def pixels_u8(x, layout="NCHW", rc=None, canvas=None, mean=MEAN, std=STD, level=0):
     """fp32 reconstruction x ([B,3,H,W], or [B,H,W,3] with layout="NHWC") -> uint8 NHWC pixels
     clamp(rint(x * std * 255 + mean * 255), 0, 255) (one fma, round-to-nearest-even, NaN -> 0): the inverse of the ingest
     Normalize.  rc=None -> a dense [B,H,W,3] tensor; rc [B, 2] (int32) + canvas [ch, cw, 3] uint8 -> tile t pasted in place at
-    pixel (rc[t, 0] * H, rc[t, 1] * W), the canvas returned.  mean / std: 3 floats, or None for 0 / 1."""
+    pixel (rc[t, 0] * H, rc[t, 1] * W), the canvas returned.  mean / std: 3 floats, or None for 0 / 1.
+    level L > 0 (at most 6, f = 2**L dividing H and W): the integer mean, rounding half up, of every f x f block of those
+    pixels, (sum + f*f/2) >> 2L -- a dense [B,H/f,W/f,3], or tile t at pixel (rc[t, 0] * H/f, rc[t, 1] * W/f) of a canvas given
+    in level-L pixels."""
     _need_gpu(x, rc, canvas)
     assert layout in ("NCHW", "NHWC"), layout
     x = x.contiguous()
@@ -322,18 +325,25 @@ def pixels_u8(x, layout="NCHW", rc=None, canvas=None, mean=MEAN, std=STD):
     else:
         B, H, W, C = x.shape
     assert C == 3, x.shape
+    level = int(level)
     m = _f32x3(mean, 255.0) if mean is not None else None
     s = _f32x3(std, 255.0) if std is not None else None
     lay = L.LAYOUT_NCHW if layout == "NCHW" else L.LAYOUT_NHWC
+
+    def run(rc_p, out, ch, cw):
+        if level == 0:
+            L.check(L.lib().vqae_pixels_u8(_p(x), lay, B, H, W, rc_p, m, s, _p(out), ch, cw, _stream()))
+        else:
+            L.check(L.lib().vqae_pixels_u8_level(_p(x), lay, B, H, W, level, rc_p, m, s, _p(out), ch, cw, _stream()))
+        return out
+
     if rc is None:
         assert canvas is None, "pixels_u8: a canvas needs rc"
-        out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=x.device)
-        L.check(L.lib().vqae_pixels_u8(_p(x), lay, B, H, W, None, m, s, _p(out), 0, 0, _stream()))
-        return out
+        lv = min(max(level, 0), 31)                                    # (a shape for any level; the library judges the level)
+        out = torch.empty((B, H >> lv, W >> lv, 3), dtype=torch.uint8, device=x.device)
+        return run(None, out, 0, 0)
     assert canvas is not None and canvas.dtype == torch.uint8 and canvas.dim() == 3 and canvas.shape[2] == 3 and \
         canvas.is_contiguous(), "pixels_u8: canvas must be a contiguous uint8 [h, w, 3] tensor"
     rc = rc.to(torch.int32).contiguous()
     assert tuple(rc.shape) == (B, 2), rc.shape
-    L.check(L.lib().vqae_pixels_u8(_p(x), lay, B, H, W, _p(rc), m, s, _p(canvas), canvas.shape[0], canvas.shape[1],
-                                   _stream()))
-    return canvas
+    return run(_p(rc), canvas, canvas.shape[0], canvas.shape[1])

@@ -6,6 +6,10 @@ stitch), decode the tiles (embed_code -> Decoder.forward, vq_ae/model.py:274-291
 clamped uint8 pixels of every tile into place (NativeVQAE.decode_indices_u8) -- the tile at patch position (r, c) of the
 extraction lands at pixel (r * P, c * P).  The reference model wraps circularly inside a tile, so a faithful
 reconstruction has seams between tiles.
+
+Every function takes `level`: the picture at 1/2**level scale (0 .. 6), each pixel the integer mean, rounding half up, of a
+2**level-square block of the level-0 pixels, reduced on the device before anything is stored (vqae_pixels_u8_level), so an
+overview of a whole slide is one resident canvas and one download (reconstruct_overview).
 """
 from pathlib import Path
 
@@ -14,6 +18,7 @@ import torch
 
 from . import hdf5
 from . import ops
+from ._lib import MAX_PIXEL_LEVEL
 
 
 def _tile_hw(tile):
@@ -43,6 +48,21 @@ def _device_grid(grid, decode_fn):
     return t
 
 
+def _levels(level, ph, pw):
+    """(levels as a list, whether a sequence was given); ValueError for a level outside 0 .. MAX_PIXEL_LEVEL or a factor that
+    does not divide the ph x pw pixels of a tile"""
+    many = not isinstance(level, (int, np.integer))
+    levels = [int(v) for v in level] if many else [int(level)]
+    if many and (not levels or len(set(levels)) != len(levels)):
+        raise ValueError(f"levels {level!r}: one or more distinct levels")
+    for v in levels:
+        if not 0 <= v <= MAX_PIXEL_LEVEL:
+            raise ValueError(f"level {v} is outside 0 .. {MAX_PIXEL_LEVEL}")
+        if ph % (1 << v) or pw % (1 << v):
+            raise ValueError(f"level {v}: {1 << v} does not divide the {ph} x {pw} pixels of a tile")
+    return levels, many
+
+
 def _cut(grid, rc, th, tw):
     """code tiles [n, th, tw] at patch positions rc, in the grid's own dtype"""
     if grid.is_cuda:
@@ -61,9 +81,12 @@ def _handle(model, autocast_dtype):
 
 @torch.no_grad()
 def reconstruct_region(model, grid, tile=32, *, r0=0, c0=0, rows=None, cols=None, batch_size=64, autocast_dtype=None,
-                       decode_fn=None):
+                       decode_fn=None, level=0):
     """Pixels of the tiles [r0, r0 + rows) x [c0, c0 + cols) of a stored code grid: a uint8 device tensor
     [rows * P_h, cols * P_w, 3] with P = tile * 2**n_down, the pixel size of one tile.
+
+    level: an int L gives the region at 1/f scale, f = 2**L: [rows * P_h / f, cols * P_w / f, 3]; a sequence of distinct
+    levels gives a tuple of such canvases, filled by ONE decode per batch.
 
     grid: numpy array as stored (uint8 / uint16 / wider) or a device tensor; uploaded once, in its own width.
     tile: the latent tile side, or (th, tw); 32 for every shipped configuration (512 / 2**4, 256 / 2**3).
@@ -71,9 +94,15 @@ def reconstruct_region(model, grid, tile=32, *, r0=0, c0=0, rows=None, cols=None
     nothing synchronises with the host per batch.
     model: a NativeVQAE or the VQAE mirror, as run_eval takes them.  autocast_dtype=None keeps the handle's own compute
     dtype, a torch dtype selects `with_dtype`.
-    decode_fn(idx_tiles, rc, canvas) replaces the HIP decode (CPU tests of the host logic only, like run_eval's encode_fn).
-    ValueError: grid sides that are not multiples of the tile; a region outside the grid."""
+    decode_fn(idx_tiles, rc, canvas) replaces the HIP decode (CPU tests of the host logic only, like run_eval's encode_fn);
+    with a level other than the int 0 it is called as decode_fn(idx_tiles, rc, canvas, level), level as given and canvas a
+    tuple when level is a sequence.
+    ValueError: grid sides that are not multiples of the tile; a region outside the grid; a level outside 0 .. 6 or one
+    whose factor does not divide the tile's pixel size (before anything is allocated)."""
     th, tw = _tile_hw(tile)
+    from .extract_embeddings import _factor                        # (the driver module pulls in the loader machinery: on first use)
+    f = _factor(model)
+    levels, many = _levels(level, th * f, tw * f)                   # refused before the grid goes up
     g = _device_grid(grid, decode_fn)
     gh, gw = int(g.shape[0]), int(g.shape[1])
     if gh % th or gw % tw or gh == 0 or gw == 0:
@@ -85,9 +114,9 @@ def reconstruct_region(model, grid, tile=32, *, r0=0, c0=0, rows=None, cols=None
         raise ValueError(f"region rows [{r0}, {r0 + rows}) x cols [{c0}, {c0 + cols}) is outside the {R} x {C}-tile grid")
     if batch_size < 1:
         raise ValueError(f"batch_size {batch_size}")
-    from .extract_embeddings import _factor                        # (the driver module pulls in the loader machinery: on first use)
-    f = _factor(model)
-    canvas = torch.empty((rows * th * f, cols * tw * f, 3), dtype=torch.uint8, device=g.device)
+    canvases = tuple(torch.empty((rows * th * f >> v, cols * tw * f >> v, 3), dtype=torch.uint8, device=g.device) for v in levels)
+    canvas = canvases if many else canvases[0]
+    extra = () if not many and levels[0] == 0 else (level,)
     decode = decode_fn or _handle(model, autocast_dtype).decode_indices_u8
     # row-major positions: [0] in the grid (where to cut), [1] in the canvas (where to paste); one upload
     rr, cc = np.divmod(np.arange(rows * cols, dtype=np.int32), np.int32(cols))
@@ -97,7 +126,7 @@ def reconstruct_region(model, grid, tile=32, *, r0=0, c0=0, rows=None, cols=None
     rc = rc_host.to(g.device, non_blocking=True)
     for lo in range(0, rows * cols, batch_size):
         hi = min(lo + batch_size, rows * cols)
-        decode(_cut(g, rc[0, lo:hi], th, tw), rc[1, lo:hi], canvas)
+        decode(_cut(g, rc[0, lo:hi], th, tw), rc[1, lo:hi], canvas, *extra)
     return canvas
 
 
@@ -105,7 +134,8 @@ def reconstruct_slide(model, grid, tile=32, *, band_rows=1, **kw):
     """Generator of (r0, band): the slide in bands of `band_rows` tile rows, each a host uint8 array
     [band_rows * P_h, cols * P_w, 3] (the last band may be lower) -- for slides whose pixels do not fit in device memory
     (200 x 400 tiles of 512 x 512 pixels are 63 GB).  The grid goes up once; every band is one reconstruct_region (whose
-    keyword arguments pass through) and one synchronous download."""
+    keyword arguments pass through, `level` among them: the bands are then [band_rows * P_h / f, ...], or tuples of arrays
+    for a sequence of levels) and one synchronous download."""
     if band_rows < 1:
         raise ValueError(f"band_rows {band_rows}")
     th, _ = _tile_hw(tile)
@@ -115,14 +145,26 @@ def reconstruct_slide(model, grid, tile=32, *, band_rows=1, **kw):
     R = int(g.shape[0]) // th
     for r0 in range(0, R, band_rows):
         band = reconstruct_region(model, g, tile, r0=r0, rows=min(band_rows, R - r0), **kw)
-        yield r0, band.cpu().numpy()
+        yield r0, tuple(b.cpu().numpy() for b in band) if isinstance(band, tuple) else band.cpu().numpy()
+
+
+def _read_grid(path, name):
+    if Path(path).suffix == ".npy":
+        return np.load(str(path), allow_pickle=False)
+    return hdf5.read_hdf5(path)["images"][name]
 
 
 def reconstruct_hdf5(model, path, name, **kw):
     """reconstruct_slide over the grid `images/<name>` of an archive written by save_encodings_hdf5 / convert_npy_to_hdf5
     (read with this package's own reader), or over a `<name>.npy` file of save_encodings given as `path`."""
-    if Path(path).suffix == ".npy":
-        grid = np.load(str(path), allow_pickle=False)
-    else:
-        grid = hdf5.read_hdf5(path)["images"][name]
-    return reconstruct_slide(model, grid, **kw)
+    return reconstruct_slide(model, _read_grid(path, name), **kw)
+
+
+def reconstruct_overview(model, grid_or_path, name=None, *, tile=32, level=5, **kw):
+    """The whole slide at one level as a host uint8 array [R * P_h / f, C * P_w / f, 3]: one reconstruct_region whose canvas
+    stays on the device (at level 5 a 200 x 400-tile slide of 512 x 512 tiles is 62 MB) and one download.  grid_or_path: a
+    code grid (array or device tensor), or the path of an archive / `.npy` file as reconstruct_hdf5 takes it, with `name`.
+    Keyword arguments pass through to reconstruct_region."""
+    grid = _read_grid(grid_or_path, name) if isinstance(grid_or_path, (str, Path)) else grid_or_path
+    out = reconstruct_region(model, grid, tile, level=level, **kw)
+    return tuple(o.cpu().numpy() for o in out) if isinstance(out, tuple) else out.cpu().numpy()

@@ -257,6 +257,23 @@ int vqae_unstitch_tiles(const void* grid_dev, int grid_dtype, const int32_t* rc_
 int vqae_pixels_u8(const float* x_dev, int layout, int batch, int h, int w, const int32_t* rc_dev, const float* mean255,
                    const float* std255, uint8_t* out_dev, int canvas_h, int canvas_w, void* stream);
 
+/* The same pixels, box-reduced to overview level L (f = 2^level) on the device: with u[y][x][c] the level-0 pixel exactly as
+ * vqae_pixels_u8 defines it,
+ *   out[Y][X][c] = ( sum over dy < f, dx < f of u[f*Y + dy][f*X + dx][c]  +  f*f/2 ) >> (2*level)
+ * an integer mean of the rounded uint8 pixels that rounds half up -- what box-filtering the level-0 image gives.  The sums are
+ * integers (255 * 4^level + f*f/2 fits 32 bits), so the result does not depend on the summation order; every level is
+ * defined from level 0, not from the level below.  level == 0 is vqae_pixels_u8.
+ *   rc_dev == NULL: out_dev is a dense [B][H/f][W/f][3] batch and canvas_h = canvas_w = 0;
+ *   otherwise tile t is pasted as an (H/f) x (W/f) block into the canvas out_dev [canvas_h][canvas_w][3], given in level-L
+ *   pixels, at pixel (rc[t].r * H/f, rc[t].c * W/f); a tile at a negative position or one that does not lie wholly inside the
+ *   canvas is skipped (no access outside it), the rest of the canvas is not written.
+ * Errors: as vqae_pixels_u8 (a canvas smaller than one reduced tile); level < 0, or f not dividing both h and w ->
+ * VQAE_ERR_INVALID; level > VQAE_MAX_PIXEL_LEVEL -> VQAE_ERR_UNSUPPORTED. */
+enum { VQAE_MAX_PIXEL_LEVEL = 6 };
+int vqae_pixels_u8_level(const float* x_dev, int layout, int batch, int h, int w, int level, const int32_t* rc_dev,
+                         const float* mean255, const float* std255, uint8_t* out_dev, int canvas_h, int canvas_w,
+                         void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * 3. Whole-model handle -- replaces Encoder.forward (vq_ae/model.py:189-217), Decoder.forward
  *    (:274-291) and VQAE.forward (:41-48) for the single-VQ-level Fixup model that every shipped
@@ -324,6 +341,19 @@ int vqae_decode_indices(vqae_handle* h, const void* idx_dev, int idx_dtype, int 
  * tile -> VQAE_ERR_INVALID.  batch == 0 -> VQAE_OK. */
 int vqae_decode_indices_u8(vqae_handle* h, const void* idx_dev, int idx_dtype, int batch, int q_h, int q_w,
                            const int32_t* rc_dev, uint8_t* canvas_dev, int canvas_h, int canvas_w, void* stream);
+/* Overview levels of the same reconstruction: ONE decoder pass into the handle's NHWC fp32 workspace, then one
+ * vqae_pixels_u8_level launch per requested level on that tensor (the decoder is tens of milliseconds, a pixel pass tens of
+ * microseconds).  levels, canvases, canvas_h, canvas_w: host arrays of n_levels entries, 1 <= n_levels <= 7, the levels
+ * distinct and each 0 .. VQAE_MAX_PIXEL_LEVEL with 2^level dividing the tile size H x W = q_h, q_w * 2^n_down; canvases[i] is the
+ * device destination of levels[i]:
+ *   rc_dev == NULL: a dense uint8 [B][H/f][W/f][3] batch, canvas_h[i] = canvas_w[i] = 0;
+ *   otherwise a canvas [canvas_h[i]][canvas_w[i]][3] in level pixels, tile t at pixel (rc[t].r * H/f, rc[t].c * W/f).
+ * Every level is validated before anything is launched: on an error no destination is written.
+ * Preconditions and errors as vqae_decode_indices_u8 and vqae_pixels_u8_level; n_levels outside 1 .. 7, a repeated level or a
+ * null array / canvas -> VQAE_ERR_INVALID.  batch == 0 -> VQAE_OK. */
+int vqae_decode_indices_u8_levels(vqae_handle* h, const void* idx_dev, int idx_dtype, int batch, int q_h, int q_w,
+                                  const int32_t* rc_dev, int n_levels, const int* levels, uint8_t* const* canvases,
+                                  const int* canvas_h, const int* canvas_w, void* stream);
 /* VQAE.forward: out [B,3,H,W], idx (optional), loss (optional). */
 int vqae_forward(vqae_handle* h, const float* x_dev, int batch, int in_h, int in_w, int layout, float* out_dev,
                  void* idx_dev, int idx_dtype, float* loss_dev, void* stream);
