@@ -7,9 +7,11 @@ through the loader module of the same name at the repository root.
 Layout: csrc/ (HIP kernels + C ABI, built into libvqae_hip.so), _lib.py / ops.py (ctypes binding),
 native.py (whole-model handle), layers/ + model.py (mirrors of the reference's module API),
 extract_embeddings.py (whole-slide driver), metrics.py (reconstruction metrics) + validate.py (dataset
-validation driver), reconstruct.py (stored code grids -> uint8 slide pixels), dist.py (one-process-per-GPU sharding over RCCL).
+validation driver), reconstruct.py (stored code grids -> uint8 slide pixels), classifier.py (the downstream slide
+classifier on stored code grids: heatmaps and scores), dist.py (one-process-per-GPU sharding over RCCL).
 """
-from . import _lib, ops, reconstruct, spec  # noqa: F401
+from . import _lib, classifier, ops, reconstruct, spec  # noqa: F401
+from .classifier import CNNClassifier, classify_hdf5, classify_slide  # noqa: F401
 from .native import NativeVQAE  # noqa: F401
 from .reconstruct import reconstruct_hdf5, reconstruct_overview, reconstruct_region, reconstruct_slide  # noqa: F401
 from .spec import SPECS, VQAESpec  # noqa: F401

@@ -24,6 +24,8 @@ DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 MAX_PIXEL_LEVEL = 6                     # VQAE_MAX_PIXEL_LEVEL: overview levels 0 .. 6 (vqae_pixels_u8_level)
 # VQAE_METRIC_*: columns of the vqae_recon_metrics_f32 output rows
 METRIC_NAMES = ("mse", "huber", "psnr", "ssim", "pred_min", "pred_max", "target_min", "target_max")
+# VQAE_CLS_*: columns of the vqae_classifier_forward stats rows
+CLS_STATS_NAMES = ("tp", "fp", "fn", "tn", "n_valid", "loss_sum")
 DTYPES = {"f32": DT_F32, "fp32": DT_F32, "float32": DT_F32, "bf16": DT_BF16, "bfloat16": DT_BF16,
           "f16": DT_F16, "fp16": DT_F16, "float16": DT_F16, "half": DT_F16}
 
@@ -132,6 +134,11 @@ SYMBOLS = {
     "vqae_recon_metrics_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "vqae_recon_metrics_f32": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_float), POINTER(c_float), c_int, c_int, c_int,
                                        c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "vqae_classifier_create": (c_int, [c_int, c_int, c_int, c_int, POINTER(Tensor), c_int, POINTER(c_void_p)]),
+    "vqae_classifier_destroy": (None, [c_void_p]),
+    "vqae_classifier_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "vqae_classifier_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float,
+                                        c_void_p, c_void_p, c_void_p]),
     "vqae_flops_per_patch": (c_double, [c_void_p, c_int, c_int, c_int, c_int]),
     "vqae_prof_begin": (c_int, [c_int, c_int]),
     "vqae_prof_end": (c_int, [POINTER(c_double), POINTER(c_int), POINTER(c_double)]),

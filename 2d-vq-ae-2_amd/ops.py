@@ -347,3 +347,26 @@ def pixels_u8(x, layout="NCHW", rc=None, canvas=None, mean=MEAN, std=STD, level=
     rc = rc.to(torch.int32).contiguous()
     assert tuple(rc.shape) == (B, 2), rc.shape
     return run(_p(rc), canvas, canvas.shape[0], canvas.shape[1])
+
+
+def classifier_forward(handle, codes, n_out=1, logits=True, heat=False, mask=None, pos_weight=1.0):
+    """vqae_classifier_forward on codes [B,H,W] (uint8 / uint16 / int32 / int64, in HBM) with the vqae_classifier `handle`
+    (a ctypes pointer; classifier.NativeClassifier owns one) of `n_out` outputs -> (logits fp32 [B,n_out,H,W] | None,
+    heat uint8 [B,H,W] | None, stats float64 [B, 6] in _lib.CLS_STATS_NAMES order | None).  stats are computed when `mask`
+    (uint8 [B,H,W]: 0 background, 1 tissue, 2 cancer) is given; heat and stats need n_out == 1 (the library refuses)."""
+    _need_gpu(codes, mask)
+    assert codes.dim() == 3, codes.shape
+    codes = codes.contiguous()
+    B, H, W = codes.shape
+    dev = codes.device
+    lg = torch.empty((B, n_out, H, W), dtype=torch.float32, device=dev) if logits else None
+    ht = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if heat else None
+    stats = ws = None
+    if mask is not None:
+        assert mask.dtype == torch.uint8 and tuple(mask.shape) == (B, H, W), (mask.dtype, mask.shape)
+        mask = mask.contiguous()
+        stats = torch.empty((B, len(L.CLS_STATS_NAMES)), dtype=torch.float64, device=dev)
+        ws = torch.empty(max(1, L.lib().vqae_classifier_workspace_bytes(handle, B, H, W)), dtype=torch.uint8, device=dev)
+    L.check(L.lib().vqae_classifier_forward(handle, _p(codes), idx_code(codes.dtype), B, H, W, _p(lg), _p(ht), _p(mask),
+                                            float(pos_weight), _p(stats), _p(ws), _stream()))
+    return lg, ht, stats

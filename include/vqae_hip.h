@@ -416,6 +416,57 @@ int vqae_prof_begin(int kernel_class, int max_launches);
  * launch also ran the fused conv3 / next-conv1 tail, their 2*M*128*128 each; class 3: 3*N*K*D VALU ops). */
 int vqae_prof_end(double* total_ms, int* n_launches, double* total_work);
 
+/* ---------------------------------------------------------------------------------------------
+ * 6. Slide classifier on stored code grids -- replaces CNNClassifier.forward (validation_nn/model.py:141-142,
+ *    `self.layers(data)`) for the layer stack conf/model/cnn_classifier.yaml composes:
+ *      nn.Embedding(K, E) -> FlattenAfterEmbedding (validation_nn/layers/misc.py:9-22: [B,1,H,W,E] -> [B,E,H,W])
+ *      -> Conv2d(E, C, 3, padding 1, zeros, bias) -> ELU(1) -> Conv2d(C, C, 3) -> ELU(1) -> Conv2d(C, n_out, 3)
+ *    and, for n_out == 1, the scoring Camelyon16BCELoss (utils/train_helpers.py:101-138) and the precision / recall
+ *    collection of cnn_classifier.yaml apply to its output.  One fused launch per call: HBM sees the codes once (plus
+ *    halo re-reads) and each requested output once; the 8- or 16-channel activations never leave the CU.
+ *    Every conv pads ITS OWN input with zeros at the grid border (activations outside the grid are 0, not
+ *    ELU(bias + ...)); a code outside 0 .. K-1 contributes a zero embedding vector and reads nothing outside the table
+ *    (the Python layer raises IndexError for it, as nn.Embedding does).  fp32 fmaf sums; ELU's negative side to <= 3 ulp
+ *    of expm1.
+ * ------------------------------------------------------------------------------------------- */
+/* Columns of a stats row.  Over the codes of one slide with mask != 0 (labels 0 background, 1 tissue, 2 cancer: the contract
+ * Camelyon16BCELoss checks, train_helpers.py:115-119), target t = mask - 1 (train_helpers.py:121-127), prediction = logit > 0:
+ * the four confusion counts and their total (exact integers held in doubles), and
+ *   loss_sum = sum of pos_weight * t * softplus(-x) + (1 - t) * softplus(x)
+ * = Camelyon16BCELoss(reduction='sum', pos_weight, label_smoothing=0) (train_helpers.py:129-138), softplus in fp32, the
+ * sum in fp64. */
+enum { VQAE_CLS_TP = 0, VQAE_CLS_FP = 1, VQAE_CLS_FN = 2, VQAE_CLS_TN = 3, VQAE_CLS_N_VALID = 4, VQAE_CLS_LOSS_SUM = 5,
+       VQAE_CLS_STATS_K = 6 };
+
+typedef struct vqae_classifier vqae_classifier;
+
+/* Builds the classifier from named fp32 host tensors in the reference's state-dict naming and PyTorch shapes
+ * (cnn_classifier.yaml's layer names under `layers.`): layers.embedding.weight [K][E], layers.in_conv.weight [C][E][3][3],
+ * layers.in_conv.bias [C], layers.hidden_conv1.weight [C][C][3][3], layers.hidden_conv1.bias [C],
+ * layers.out_conv.weight [n_out][C][3][3], layers.out_conv.bias [n_out]; other tensors are ignored.  The weights are
+ * copied; nothing touches the device before the first vqae_classifier_forward.
+ * Errors: embedding_dim outside 1 .. 8, hidden not 8 or 16, n_out outside 1 .. 4, num_embeddings outside 1 .. 65536 ->
+ * VQAE_ERR_UNSUPPORTED; a missing tensor -> VQAE_ERR_NOT_FOUND; a tensor of another size, null pointers -> VQAE_ERR_INVALID. */
+int vqae_classifier_create(int num_embeddings, int embedding_dim, int hidden, int n_out, const vqae_tensor* tensors,
+                           int n_tensors, vqae_classifier** out);
+void vqae_classifier_destroy(vqae_classifier* c);
+/* Bytes of scratch a call with stats needs for `batch` grids of h x w codes (0 for an empty batch or a bad shape). */
+size_t vqae_classifier_workspace_bytes(const vqae_classifier* c, int batch, int h, int w);
+/* CNNClassifier.forward (validation_nn/model.py:141-142) on codes_dev [B][h][w] of idx_dtype (VQAE_IDX_*, as stored), any
+ * h, w >= 1.  Each output is optional, at least one is required:
+ *   logits_dev   fp32 [B][n_out][h][w], the reference's NCHW output;
+ *   heat_u8_dev  uint8 [B][h][w] = rintf(255 * sigmoid(logit)), n_out == 1 only;
+ *   stats_dev    double [B][VQAE_CLS_STATS_K] (VQAE_CLS_*) over mask_dev uint8 [B][h][w] with `pos_weight`, n_out == 1
+ *                only; needs workspace_dev of vqae_classifier_workspace_bytes(c, B, h, w) bytes.  Per-workgroup partials
+ *                are reduced in a fixed order (no atomics) and the partition depends on (h, w) only: a slide's row is
+ *                bit-identical run to run and at any batch position.
+ * Errors, all before any HIP call: null c / codes, no output at all, stats without a mask or without the workspace, heat or
+ * stats with n_out != 1, a bad idx_dtype, h < 1 or w < 1, batch < 0, a negative or non-finite pos_weight with stats ->
+ * VQAE_ERR_INVALID; batch > 65535 -> VQAE_ERR_UNSUPPORTED; batch == 0 -> VQAE_OK. */
+int vqae_classifier_forward(vqae_classifier* c, const void* codes_dev, int idx_dtype, int batch, int h, int w,
+                            float* logits_dev, uint8_t* heat_u8_dev, const uint8_t* mask_dev, float pos_weight,
+                            double* stats_dev, void* workspace_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
