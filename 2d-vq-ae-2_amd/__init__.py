@@ -10,8 +10,10 @@ extract_embeddings.py (whole-slide driver), metrics.py (reconstruction metrics) 
 validation driver), reconstruct.py (stored code grids -> uint8 slide pixels), classifier.py (the downstream slide
 classifier on stored code grids: heatmaps and scores), dist.py (one-process-per-GPU sharding over RCCL).
 """
-from . import _lib, classifier, ops, reconstruct, spec  # noqa: F401
+from . import _lib, classifier, classifier_train, ops, reconstruct, spec  # noqa: F401
 from .classifier import CNNClassifier, classify_hdf5, classify_slide  # noqa: F401
+from .classifier_train import (collate_random_crop, embeddings_split, loss_and_grads, smooth_targets,  # noqa: F401
+                               train_hdf5)
 from .native import NativeVQAE  # noqa: F401
 from .reconstruct import reconstruct_hdf5, reconstruct_overview, reconstruct_region, reconstruct_slide  # noqa: F401
 from .spec import SPECS, VQAESpec  # noqa: F401

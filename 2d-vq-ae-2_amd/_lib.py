@@ -139,6 +139,11 @@ SYMBOLS = {
     "vqae_classifier_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
     "vqae_classifier_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float,
                                         c_void_p, c_void_p, c_void_p]),
+    "vqae_classifier_update": (c_int, [c_void_p, POINTER(Tensor), c_int]),
+    "vqae_classifier_grad_floats": (c_size_t, [c_void_p]),
+    "vqae_classifier_train_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "vqae_classifier_loss_grad": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_int,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vqae_flops_per_patch": (c_double, [c_void_p, c_int, c_int, c_int, c_int]),
     "vqae_prof_begin": (c_int, [c_int, c_int]),
     "vqae_prof_end": (c_int, [POINTER(c_double), POINTER(c_int), POINTER(c_double)]),

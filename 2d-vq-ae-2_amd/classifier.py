@@ -6,7 +6,8 @@ reference trains a small CNN on exactly that file (validation_nn/model.py, conf/
     nn.Embedding(256, 1) -> FlattenAfterEmbedding -> Conv2d(1, 8, 3, pad 1, bias) -> ELU -> Conv2d(8, 8, 3) -> ELU
     -> Conv2d(8, 1, 3)
 
-a per-code tumour logit for a whole slide.  `CNNClassifier` mirrors that module for inference: on tensors in HBM its forward
+a per-code tumour logit for a whole slide.  `CNNClassifier` mirrors that module for inference (training is functional, in
+classifier_train.py: `loss_and_grads` writes `.grad` from the fused backward and any torch.optim optimiser steps): on tensors in HBM its forward
 is one fused HIP launch (csrc/classifier.hip); on CPU tensors it is a plain torch restatement of the same layers, the
 yardstick the tests pin against the reference's recorded output.  `classify_slide` / `classify_hdf5` add what the codes
 were made for: the uint8 probability map at code resolution and the masked precision / recall / BCE of
@@ -47,16 +48,29 @@ class NativeClassifier:
 
     def __init__(self, num_embeddings, embedding_dim, hidden, n_out, tensors):
         self.num_embeddings, self.n_out = int(num_embeddings), int(n_out)
+        self.dims = (int(num_embeddings), int(embedding_dim), int(hidden), int(n_out))
+        keep, arr = self._tensor_array(tensors)
+        h = ctypes.c_void_p()
+        L.check(L.lib().vqae_classifier_create(*self.dims, arr, len(arr), ctypes.byref(h)))
+        self._h = h
+
+    @staticmethod
+    def _tensor_array(tensors):
         keep, items = [], []
         for name, t in tensors.items():
             a = np.ascontiguousarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t), dtype=np.float32)
             keep.append(a)
             items.append(L.Tensor(name.encode(), a.ctypes.data_as(ctypes.c_void_p), a.size))
-        arr = (L.Tensor * len(items))(*items)
-        h = ctypes.c_void_p()
-        L.check(L.lib().vqae_classifier_create(int(num_embeddings), int(embedding_dim), int(hidden), int(n_out), arr,
-                                               len(items), ctypes.byref(h)))
-        self._h = h
+        return keep, (L.Tensor * len(items))(*items)
+
+    def update(self, tensors):
+        """New weights of the same shapes into the existing handle (vqae_classifier_update): what an optimiser step needs."""
+        keep, arr = self._tensor_array(tensors)
+        L.check(L.lib().vqae_classifier_update(self._h, arr, len(arr)))
+
+    def loss_grad(self, codes, mask, target=None, pos_weight=1.0, reduction="sum"):
+        """codes, mask [B,H,W] in HBM -> (loss [1], packed grads, stats [B,6]) in fp64, see ops.classifier_loss_grad"""
+        return ops.classifier_loss_grad(self._h, codes, mask, target=target, pos_weight=pos_weight, reduction=reduction)
 
     def forward(self, codes, logits=True, heat=False, mask=None, pos_weight=1.0):
         """codes [B,H,W] in HBM -> (logits | None, heat | None, stats | None), see ops.classifier_forward"""
@@ -213,15 +227,20 @@ class CNNClassifier(nn.Module):
         self._native = None
 
     def native(self):
-        """The vqae_classifier of the current weights: built on first use, rebuilt when a parameter changed or was replaced."""
+        """The vqae_classifier of the current weights: built on first use; when a parameter changed or was replaced (an
+        optimiser step) the same handle takes the new weights, and only another shape builds a new one."""
         self._check_structure()
         sig = tuple((id(t), t._version) for t in self.parameters())
         if self._native is None or self._native[0] != sig:
-            self.refresh()
             ls = self.layers
             tensors = {"layers." + n: p for n, p in ls.named_parameters()}
-            self._native = (sig, NativeClassifier(ls.embedding.num_embeddings, ls.embedding.embedding_dim,
-                                                  ls.in_conv.out_channels, ls.out_conv.out_channels, tensors))
+            dims = (ls.embedding.num_embeddings, ls.embedding.embedding_dim, ls.in_conv.out_channels, ls.out_conv.out_channels)
+            if self._native is not None and self._native[1].dims == dims:
+                self._native[1].update(tensors)
+                self._native = (sig, self._native[1])
+            else:
+                self.refresh()
+                self._native = (sig, NativeClassifier(*dims, tensors))
         return self._native[1]
 
     def __getstate__(self):

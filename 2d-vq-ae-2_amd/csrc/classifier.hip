@@ -20,18 +20,15 @@
 // Stats: per-thread integer counts and an fp64 loss sum -> wave shuffles -> the workgroup's row of `part`; a second launch
 // sums a slide's rows in a fixed order.  No atomics; the partition depends on (h, w) only, so a slide's stats are
 // bit-identical run to run and at any batch position.
-#include "common.h"
+#include "classifier_impl.h"
 
 #include <cmath>
-#include <mutex>
 #include <string>
-#include <vector>
+
+using namespace vqae_cls;
 
 namespace {
 
-constexpr int NT = 256;                 // threads per workgroup
-constexpr int TH = 14;                  // output rows per tile
-constexpr int SK = VQAE_CLS_STATS_K;
 constexpr int LDS_PER_WG = 80 * 1024;   // half a CU's 160 KiB: two workgroups per CU
 
 template <int TW> struct Geo {
@@ -46,43 +43,6 @@ int plane_floats(int tw, int E, int C) {
     return a + (e0 > b ? e0 : b);
 }
 
-// ELU(alpha = 1) with the negative side to <= 3 ulp of expm1: the degree-7 Taylor series for v > -0.3 (next term
-// 0.3^7 / 40320 = 5e-9 relative), the hardware exponential minus one beyond (no cancellation there: |result| >= 0.26).
-__device__ __forceinline__ float elu1(float v) {
-    const float e = __builtin_amdgcn_exp2f(v * 1.44269504088896341f) - 1.0f;
-    float p = 1.0f / 5040.0f;
-    p = fmaf(p, v, 1.0f / 720.0f);
-    p = fmaf(p, v, 1.0f / 120.0f);
-    p = fmaf(p, v, 1.0f / 24.0f);
-    p = fmaf(p, v, 1.0f / 6.0f);
-    p = fmaf(p, v, 0.5f);
-    p = fmaf(p, v, 1.0f);
-    const float n = v > -0.3f ? p * v : e;
-    return v > 0.0f ? v : n;
-}
-
-__device__ __forceinline__ int64_t load_code(const void* __restrict__ p, int dt, int64_t i) {
-    switch (dt) {
-        case VQAE_IDX_U8: return ((const uint8_t*)p)[i];
-        case VQAE_IDX_U16: return ((const uint16_t*)p)[i];
-        case VQAE_IDX_I32: return ((const int32_t*)p)[i];
-        default: return ((const int64_t*)p)[i];
-    }
-}
-
-__device__ __forceinline__ float softplus(float x) { return fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x))); }
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
 template <int C, int NO, int TW, int P>
 __global__ __launch_bounds__(NT)
 void classifier_kernel(const void* __restrict__ codes, int idx_dtype, int H, int W, int tiles_x,
@@ -90,7 +50,8 @@ void classifier_kernel(const void* __restrict__ codes, int idx_dtype, int H, int
                        const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w2,
                        const float* __restrict__ b2, const float* __restrict__ w3, const float* __restrict__ b3,
                        float* __restrict__ logits, uint8_t* __restrict__ heat, const uint8_t* __restrict__ mask,
-                       float pos_weight, double* __restrict__ part) {
+                       const float* __restrict__ target, float pos_weight, float* __restrict__ glogit,
+                       double* __restrict__ part) {
     using G = Geo<TW>;
     constexpr int EN = G::EH * G::EW, AN = G::AH * G::AW, BN = G::BH * G::BW;
     static_assert(BN / P == NT && G::BH % P == 0, "stage 3: one column strip per thread");
@@ -229,11 +190,27 @@ void classifier_kernel(const void* __restrict__ codes, int idx_dtype, int H, int
                     if (heat) heat[(int64_t)b * hw + pos] = (uint8_t)rintf(255.0f * (1.0f / (1.0f + expf(-x))));
                     if (mask) {
                         const uint8_t m = mask[(int64_t)b * hw + pos];
+                        float g = 0.0f;
                         if (m != 0) {
                             const bool t = m >= 2, pr = x > 0.0f;
                             n_tp += pr && t; n_fp += pr && !t; n_fn += !pr && t; n_tn += !pr && !t;
-                            loss += t ? (double)pos_weight * (double)softplus(-x) : (double)softplus(x);
+                            if (target) {                          // soft target (label smoothing), read where valid only
+                                const float ts = target[(int64_t)b * hw + pos];
+                                loss += (double)pos_weight * (double)ts * (double)softplus(-x) +
+                                        (1.0 - (double)ts) * (double)softplus(x);
+                                if (glogit) {
+                                    const float pt = pos_weight * ts;
+                                    g = (1.0f / (1.0f + expf(-x))) * ((1.0f - ts) + pt) - pt;
+                                }
+                            } else {
+                                loss += t ? (double)pos_weight * (double)softplus(-x) : (double)softplus(x);
+                                if (glogit) {
+                                    const float sg = 1.0f / (1.0f + expf(-x));
+                                    g = t ? pos_weight * sg - pos_weight : sg;
+                                }
+                            }
                         }
+                        if (glogit) glogit[(int64_t)b * hw + pos] = g;
                     }
                 }
             }
@@ -286,18 +263,6 @@ __global__ __launch_bounds__(NT) void classifier_stats_final(const double* __res
 
 }  // namespace
 
-struct vqae_classifier {
-    int K = 0, E = 0, C = 0, NO = 0;
-    int tw = 0;                       // tile width of the geometry this (E, C) runs on: 62 or 30
-    // one packed host image, uploaded on the first forward on a device: table [K][E], w1 [E][9][C], b1 [C], w2 [C][9][C],
-    // b2 [C], w3 [C][9][NO], b3 [NO]  (conv weights repacked from PyTorch's [cout][cin][3][3] to [cin][tap][cout])
-    std::vector<float> host;
-    size_t o_table = 0, o_w1 = 0, o_b1 = 0, o_w2 = 0, o_b2 = 0, o_w3 = 0, o_b3 = 0;
-    float* dev = nullptr;
-    int dev_id = -1;
-    std::mutex mu;
-};
-
 namespace {
 
 const vqae_tensor* find_tensor(const vqae_tensor* ts, int n, const char* name) {
@@ -312,33 +277,40 @@ void pack_conv(const float* w, int cout, int cin, float* dst) {
             for (int t = 0; t < 9; ++t) dst[((size_t)ci * 9 + t) * cout + co] = w[((size_t)co * cin + ci) * 9 + t];
 }
 
-int64_t tile_count(const vqae_classifier* c, int h, int w, int* tiles_x) {
-    const int64_t tx = vqae::ceil_div(w, c->tw), ty = vqae::ceil_div(h, TH);
-    if (tiles_x) *tiles_x = (int)tx;
-    return tx * ty;
+// The seven named tensors of a (K, E, C, NO) classifier, checked and found: what create and update share.
+int find_weights(const char* who, int K, int E, int C, int NO, const vqae_tensor* tensors, int n_tensors, const vqae_tensor* t[7]) {
+    struct Want { const char* name; int64_t numel; };
+    const Want want[7] = {{"layers.embedding.weight", (int64_t)K * E},
+                          {"layers.in_conv.weight", (int64_t)C * E * 9}, {"layers.in_conv.bias", C},
+                          {"layers.hidden_conv1.weight", (int64_t)C * C * 9}, {"layers.hidden_conv1.bias", C},
+                          {"layers.out_conv.weight", (int64_t)NO * C * 9}, {"layers.out_conv.bias", NO}};
+    for (int i = 0; i < 7; ++i) {
+        t[i] = find_tensor(tensors, n_tensors, want[i].name);
+        VQAE_REQUIRE(t[i], VQAE_ERR_NOT_FOUND, "%s: tensor '%s' is missing", who, want[i].name);
+        VQAE_REQUIRE(t[i]->data && t[i]->numel == want[i].numel, VQAE_ERR_INVALID,
+                     "%s: tensor '%s' has %lld elements, expected %lld", who, want[i].name, (long long)t[i]->numel,
+                     (long long)want[i].numel);
+    }
+    return VQAE_OK;
 }
 
-int ensure_device(vqae_classifier* c, hipStream_t st) {
-    int dev = 0;
-    VQAE_HIP_CHECK(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(c->mu);
-    if (c->dev && c->dev_id == dev) return VQAE_OK;
-    if (c->dev) {
-        (void)hipFree(c->dev);
-        c->dev = nullptr;
-    }
-    VQAE_HIP_CHECK(hipMalloc((void**)&c->dev, c->host.size() * sizeof(float)));
-    c->dev_id = dev;
-    VQAE_HIP_CHECK(hipMemcpyAsync(c->dev, c->host.data(), c->host.size() * sizeof(float), hipMemcpyHostToDevice, st));
-    VQAE_HIP_CHECK(hipStreamSynchronize(st));     // once per object and device: the host image may be pageable
-    return VQAE_OK;
+void pack_weights(vqae_classifier* c, const vqae_tensor* const t[7]) {
+    const int K = c->K, E = c->E, C = c->C, NO = c->NO;
+    float* h = c->host.data();
+    std::memcpy(h + c->o_table, t[0]->data, sizeof(float) * (size_t)K * E);
+    pack_conv(t[1]->data, C, E, h + c->o_w1);
+    std::memcpy(h + c->o_b1, t[2]->data, sizeof(float) * C);
+    pack_conv(t[3]->data, C, C, h + c->o_w2);
+    std::memcpy(h + c->o_b2, t[4]->data, sizeof(float) * C);
+    pack_conv(t[5]->data, NO, C, h + c->o_w3);
+    std::memcpy(h + c->o_b3, t[6]->data, sizeof(float) * NO);
 }
 
 struct Launch {
     const void* codes; int idx_dtype, H, W, tiles_x;
     const float* table; int K, E, table_lds;
     const float *w1, *b1, *w2, *b2, *w3, *b3;
-    float* logits; uint8_t* heat; const uint8_t* mask; float pos_weight; double* part;
+    float* logits; uint8_t* heat; const uint8_t* mask; const float* target; float pos_weight; float* glogit; double* part;
     dim3 grid; int lds_bytes; hipStream_t st;
 };
 
@@ -347,7 +319,8 @@ int launch(const Launch& a) {
     auto kern = classifier_kernel<C, NO, TW, P>;
     if (int rc = vqae::set_max_dynamic_lds((const void*)kern, LDS_PER_WG)) return rc;
     kern<<<a.grid, NT, a.lds_bytes, a.st>>>(a.codes, a.idx_dtype, a.H, a.W, a.tiles_x, a.table, a.K, a.E, a.table_lds, a.w1,
-                                           a.b1, a.w2, a.b2, a.w3, a.b3, a.logits, a.heat, a.mask, a.pos_weight, a.part);
+                                           a.b1, a.w2, a.b2, a.w3, a.b3, a.logits, a.heat, a.mask, a.target, a.pos_weight,
+                                           a.glogit, a.part);
     VQAE_LAUNCH_CHECK();
     return VQAE_OK;
 }
@@ -364,46 +337,98 @@ int launch_no(int no, const Launch& a) {
 
 }  // namespace
 
+int64_t vqae_cls::tile_count(const vqae_classifier* c, int h, int w, int* tiles_x) {
+    const int64_t tx = vqae::ceil_div(w, c->tw), ty = vqae::ceil_div(h, TH);
+    if (tiles_x) *tiles_x = (int)tx;
+    return tx * ty;
+}
+
+int vqae_cls::ensure_device(vqae_classifier* c, hipStream_t st) {
+    int dev = 0;
+    VQAE_HIP_CHECK(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (c->dev && c->dev_id == dev && !c->dev_stale) return VQAE_OK;
+    if (c->dev && c->dev_id != dev) {
+        (void)hipFree(c->dev);
+        c->dev = nullptr;
+    }
+    if (!c->dev) VQAE_HIP_CHECK(hipMalloc((void**)&c->dev, c->host.size() * sizeof(float)));
+    c->dev_id = dev;
+    VQAE_HIP_CHECK(hipMemcpyAsync(c->dev, c->host.data(), c->host.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    VQAE_HIP_CHECK(hipStreamSynchronize(st));     // once per upload: the host image may be pageable
+    c->dev_stale = false;
+    return VQAE_OK;
+}
+
+int vqae_cls::forward_launch(vqae_classifier* c, const void* codes_dev, int idx_dtype, int batch, int h, int w, float* logits_dev,
+                             uint8_t* heat_u8_dev, const uint8_t* mask_dev, const float* target_dev, float pos_weight,
+                             float* grad_logit_dev, double* stats_dev, void* workspace_dev, hipStream_t st) {
+    int tiles_x = 0;
+    const int64_t ntiles = tile_count(c, h, w, &tiles_x);
+    if (int rc = ensure_device(c, st)) return rc;
+    const int planes = plane_floats(c->tw, c->E, c->C) * 4, table = c->K * c->E * 4;
+    const bool table_lds = planes + table + 256 <= LDS_PER_WG;     // (256: the kernel's static reduction scratch)
+    Launch a;
+    a.codes = codes_dev; a.idx_dtype = idx_dtype; a.H = h; a.W = w; a.tiles_x = tiles_x;
+    a.table = c->dev + c->o_table; a.K = c->K; a.E = c->E; a.table_lds = table_lds;
+    a.w1 = c->dev + c->o_w1; a.b1 = c->dev + c->o_b1; a.w2 = c->dev + c->o_w2; a.b2 = c->dev + c->o_b2;
+    a.w3 = c->dev + c->o_w3; a.b3 = c->dev + c->o_b3;
+    a.logits = logits_dev; a.heat = heat_u8_dev; a.mask = (stats_dev || grad_logit_dev) ? mask_dev : nullptr;
+    a.target = target_dev; a.pos_weight = pos_weight; a.glogit = grad_logit_dev;
+    a.part = stats_dev ? (double*)workspace_dev : nullptr;
+    a.grid = dim3((unsigned)ntiles, (unsigned)batch);
+    a.lds_bytes = planes + (table_lds ? table : 0);
+    a.st = st;
+    int rc;
+    if (c->tw == 62) rc = launch_no<8, 62, 4>(c->NO, a);
+    else if (c->C == 8) rc = launch_no<8, 30, 2>(c->NO, a);
+    else rc = launch_no<16, 30, 2>(c->NO, a);
+    if (rc) return rc;
+    if (stats_dev) {
+        classifier_stats_final<<<(unsigned)batch, NT, 0, st>>>((const double*)workspace_dev, (int)ntiles, stats_dev);
+        VQAE_LAUNCH_CHECK();
+    }
+    return VQAE_OK;
+}
+
+static int check_dims(const char* who, int K, int E, int C, int NO) {
+    VQAE_REQUIRE(E >= 1 && E <= 8, VQAE_ERR_UNSUPPORTED, "%s: embedding_dim %d is outside 1 .. 8", who, E);
+    VQAE_REQUIRE(C == 8 || C == 16, VQAE_ERR_UNSUPPORTED, "%s: hidden width %d is not 8 or 16", who, C);
+    VQAE_REQUIRE(NO >= 1 && NO <= 4, VQAE_ERR_UNSUPPORTED, "%s: n_out %d is outside 1 .. 4", who, NO);
+    VQAE_REQUIRE(K >= 1 && K <= 65536, VQAE_ERR_UNSUPPORTED, "%s: num_embeddings %d is outside 1 .. 65536", who, K);
+    return VQAE_OK;
+}
+
 extern "C" int vqae_classifier_create(int num_embeddings, int embedding_dim, int hidden, int n_out, const vqae_tensor* tensors,
                                       int n_tensors, vqae_classifier** out) {
     VQAE_REQUIRE(out, VQAE_ERR_INVALID, "classifier_create: null out");
     *out = nullptr;
     VQAE_REQUIRE(n_tensors >= 0 && (tensors || n_tensors == 0), VQAE_ERR_INVALID, "classifier_create: null tensors");
     const int K = num_embeddings, E = embedding_dim, C = hidden, NO = n_out;
-    VQAE_REQUIRE(E >= 1 && E <= 8, VQAE_ERR_UNSUPPORTED, "classifier_create: embedding_dim %d is outside 1 .. 8", E);
-    VQAE_REQUIRE(C == 8 || C == 16, VQAE_ERR_UNSUPPORTED, "classifier_create: hidden width %d is not 8 or 16", C);
-    VQAE_REQUIRE(NO >= 1 && NO <= 4, VQAE_ERR_UNSUPPORTED, "classifier_create: n_out %d is outside 1 .. 4", NO);
-    VQAE_REQUIRE(K >= 1 && K <= 65536, VQAE_ERR_UNSUPPORTED, "classifier_create: num_embeddings %d is outside 1 .. 65536", K);
-    struct Want { const char* name; int64_t numel; };
-    const Want want[7] = {{"layers.embedding.weight", (int64_t)K * E},
-                          {"layers.in_conv.weight", (int64_t)C * E * 9}, {"layers.in_conv.bias", C},
-                          {"layers.hidden_conv1.weight", (int64_t)C * C * 9}, {"layers.hidden_conv1.bias", C},
-                          {"layers.out_conv.weight", (int64_t)NO * C * 9}, {"layers.out_conv.bias", NO}};
+    if (int rc = check_dims("classifier_create", K, E, C, NO)) return rc;
     const vqae_tensor* t[7];
-    for (int i = 0; i < 7; ++i) {
-        t[i] = find_tensor(tensors, n_tensors, want[i].name);
-        VQAE_REQUIRE(t[i], VQAE_ERR_NOT_FOUND, "classifier_create: tensor '%s' is missing", want[i].name);
-        VQAE_REQUIRE(t[i]->data && t[i]->numel == want[i].numel, VQAE_ERR_INVALID,
-                     "classifier_create: tensor '%s' has %lld elements, expected %lld", want[i].name, (long long)t[i]->numel,
-                     (long long)want[i].numel);
-    }
+    if (int rc = find_weights("classifier_create", K, E, C, NO, tensors, n_tensors, t)) return rc;
     vqae_classifier* c = new vqae_classifier;
     c->K = K; c->E = E; c->C = C; c->NO = NO;
     c->tw = (C == 8 && E <= 6) ? 62 : 30;
     size_t n = 0;
     auto take = [&n](int64_t numel) { const size_t o = n; n += (size_t)vqae::round_up(numel, 16); return o; };   // 64-byte rows
-    c->o_table = take(want[0].numel); c->o_w1 = take(want[1].numel); c->o_b1 = take(C); c->o_w2 = take(want[3].numel);
-    c->o_b2 = take(C); c->o_w3 = take(want[5].numel); c->o_b3 = take(NO);
+    c->o_table = take((int64_t)K * E); c->o_w1 = take((int64_t)C * E * 9); c->o_b1 = take(C); c->o_w2 = take((int64_t)C * C * 9);
+    c->o_b2 = take(C); c->o_w3 = take((int64_t)NO * C * 9); c->o_b3 = take(NO);
     c->host.assign(n, 0.0f);
-    float* h = c->host.data();
-    std::memcpy(h + c->o_table, t[0]->data, sizeof(float) * want[0].numel);
-    pack_conv(t[1]->data, C, E, h + c->o_w1);
-    std::memcpy(h + c->o_b1, t[2]->data, sizeof(float) * C);
-    pack_conv(t[3]->data, C, C, h + c->o_w2);
-    std::memcpy(h + c->o_b2, t[4]->data, sizeof(float) * C);
-    pack_conv(t[5]->data, NO, C, h + c->o_w3);
-    std::memcpy(h + c->o_b3, t[6]->data, sizeof(float) * NO);
+    pack_weights(c, t);
     *out = c;
+    return VQAE_OK;
+}
+
+extern "C" int vqae_classifier_update(vqae_classifier* c, const vqae_tensor* tensors, int n_tensors) {
+    VQAE_REQUIRE(c, VQAE_ERR_INVALID, "classifier_update: null classifier");
+    VQAE_REQUIRE(n_tensors >= 0 && (tensors || n_tensors == 0), VQAE_ERR_INVALID, "classifier_update: null tensors");
+    const vqae_tensor* t[7];
+    if (int rc = find_weights("classifier_update", c->K, c->E, c->C, c->NO, tensors, n_tensors, t)) return rc;
+    std::lock_guard<std::mutex> lock(c->mu);
+    pack_weights(c, t);
+    c->dev_stale = true;              // the next call uploads on its own stream, behind the launches that read the old image
     return VQAE_OK;
 }
 
@@ -427,39 +452,13 @@ extern "C" int vqae_classifier_forward(vqae_classifier* c, const void* codes_dev
     VQAE_REQUIRE(!stats_dev || workspace_dev, VQAE_ERR_INVALID, "classifier_forward: stats need the workspace");
     VQAE_REQUIRE(c->NO == 1 || (!heat_u8_dev && !stats_dev), VQAE_ERR_INVALID,
                  "classifier_forward: heat and stats are defined for n_out == 1, this classifier has %d", c->NO);
-    VQAE_REQUIRE(idx_dtype == VQAE_IDX_I64 || idx_dtype == VQAE_IDX_U8 || idx_dtype == VQAE_IDX_U16 || idx_dtype == VQAE_IDX_I32,
-                 VQAE_ERR_INVALID, "classifier_forward: bad index dtype %d", idx_dtype);
+    VQAE_REQUIRE(idx_dtype_ok(idx_dtype), VQAE_ERR_INVALID, "classifier_forward: bad index dtype %d", idx_dtype);
     VQAE_REQUIRE(batch >= 0 && h >= 1 && w >= 1, VQAE_ERR_INVALID, "classifier_forward: bad shape batch=%d h=%d w=%d", batch, h, w);
     VQAE_REQUIRE(!stats_dev || (std::isfinite(pos_weight) && pos_weight >= 0.f), VQAE_ERR_INVALID,
                  "classifier_forward: pos_weight must be finite and >= 0");
     VQAE_REQUIRE(batch <= 65535, VQAE_ERR_UNSUPPORTED, "classifier_forward: batch %d > 65535", batch);
-    int tiles_x = 0;
-    const int64_t ntiles = tile_count(c, h, w, &tiles_x);
-    VQAE_REQUIRE(ntiles < (1ll << 31), VQAE_ERR_UNSUPPORTED, "classifier_forward: a grid of %d x %d codes", h, w);
+    VQAE_REQUIRE(tile_count(c, h, w, nullptr) < (1ll << 31), VQAE_ERR_UNSUPPORTED, "classifier_forward: a grid of %d x %d codes", h, w);
     if (batch == 0) return VQAE_OK;
-
-    const hipStream_t st = (hipStream_t)stream;
-    if (int rc = ensure_device(c, st)) return rc;
-    const int planes = plane_floats(c->tw, c->E, c->C) * 4, table = c->K * c->E * 4;
-    const bool table_lds = planes + table + 256 <= LDS_PER_WG;     // (256: the kernel's static reduction scratch)
-    Launch a;
-    a.codes = codes_dev; a.idx_dtype = idx_dtype; a.H = h; a.W = w; a.tiles_x = tiles_x;
-    a.table = c->dev + c->o_table; a.K = c->K; a.E = c->E; a.table_lds = table_lds;
-    a.w1 = c->dev + c->o_w1; a.b1 = c->dev + c->o_b1; a.w2 = c->dev + c->o_w2; a.b2 = c->dev + c->o_b2;
-    a.w3 = c->dev + c->o_w3; a.b3 = c->dev + c->o_b3;
-    a.logits = logits_dev; a.heat = heat_u8_dev; a.mask = stats_dev ? mask_dev : nullptr; a.pos_weight = pos_weight;
-    a.part = stats_dev ? (double*)workspace_dev : nullptr;
-    a.grid = dim3((unsigned)ntiles, (unsigned)batch);
-    a.lds_bytes = planes + (table_lds ? table : 0);
-    a.st = st;
-    int rc;
-    if (c->tw == 62) rc = launch_no<8, 62, 4>(c->NO, a);
-    else if (c->C == 8) rc = launch_no<8, 30, 2>(c->NO, a);
-    else rc = launch_no<16, 30, 2>(c->NO, a);
-    if (rc) return rc;
-    if (stats_dev) {
-        classifier_stats_final<<<(unsigned)batch, NT, 0, st>>>((const double*)workspace_dev, (int)ntiles, stats_dev);
-        VQAE_LAUNCH_CHECK();
-    }
-    return VQAE_OK;
+    return forward_launch(c, codes_dev, idx_dtype, batch, h, w, logits_dev, heat_u8_dev, mask_dev, nullptr, pos_weight, nullptr,
+                          stats_dev, workspace_dev, (hipStream_t)stream);
 }

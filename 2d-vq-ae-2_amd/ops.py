@@ -370,3 +370,31 @@ def classifier_forward(handle, codes, n_out=1, logits=True, heat=False, mask=Non
     L.check(L.lib().vqae_classifier_forward(handle, _p(codes), idx_code(codes.dtype), B, H, W, _p(lg), _p(ht), _p(mask),
                                             float(pos_weight), _p(stats), _p(ws), _stream()))
     return lg, ht, stats
+
+
+def classifier_loss_grad(handle, codes, mask, target=None, pos_weight=1.0, reduction="sum"):
+    """vqae_classifier_loss_grad on codes [B,H,W] (as stored, in HBM) and mask uint8 [B,H,W] (0 background, 1 tissue,
+    2 cancer) with the vqae_classifier `handle` (n_out == 1) -> (loss float64 [1], grads float64
+    [vqae_classifier_grad_floats]: the seven tensors packed in PyTorch's shapes and parameter order, stats float64 [B, 6] in
+    _lib.CLS_STATS_NAMES order).  target: optional fp32 [B,H,W] soft targets in [0, 1], read where mask != 0.  Codes are not
+    checked against the table: one outside it is a zero vector without a gradient."""
+    _need_gpu(codes, mask, target)
+    assert codes.dim() == 3, codes.shape
+    assert reduction in ("sum", "mean"), reduction
+    codes = codes.contiguous()
+    B, H, W = codes.shape
+    dev = codes.device
+    assert mask.dtype == torch.uint8 and tuple(mask.shape) == (B, H, W), (mask.dtype, mask.shape)
+    mask = mask.contiguous()
+    if target is not None:
+        assert target.dtype == torch.float32 and tuple(target.shape) == (B, H, W), (target.dtype, target.shape)
+        target = target.contiguous()
+    lib = L.lib()
+    grads = torch.empty(lib.vqae_classifier_grad_floats(handle), dtype=torch.float64, device=dev)
+    stats = torch.empty((B, len(L.CLS_STATS_NAMES)), dtype=torch.float64, device=dev)
+    loss = torch.empty(1, dtype=torch.float64, device=dev)
+    ws = torch.empty(max(1, lib.vqae_classifier_train_workspace_bytes(handle, B, H, W)), dtype=torch.uint8, device=dev)
+    L.check(lib.vqae_classifier_loss_grad(handle, _p(codes), idx_code(codes.dtype), B, H, W, _p(mask), _p(target),
+                                          float(pos_weight), 1 if reduction == "mean" else 0, _p(grads), _p(stats), _p(loss),
+                                          _p(ws), _stream()))
+    return loss, grads, stats

@@ -467,6 +467,45 @@ int vqae_classifier_forward(vqae_classifier* c, const void* codes_dev, int idx_d
                             float* logits_dev, uint8_t* heat_u8_dev, const uint8_t* mask_dev, float pos_weight,
                             double* stats_dev, void* workspace_dev, void* stream);
 
+/* ---- Training: replaces CNNClassifier.step (validation_nn/model.py:131-139: forward, then the loss Lightning
+ * differentiates) with Camelyon16BCELoss (utils/train_helpers.py:101-138) as loss_f, and the backward() autograd runs over
+ * both, for n_out == 1.  No activation tensor is stored: the backward recomputes the tiles from the codes. ---- */
+/* Replaces the weights of an existing classifier: the same names, shapes and checks as vqae_classifier_create (dimensions are
+ * those the handle was created with).  The host copy changes at once; the device copy is refreshed by the next call that
+ * uses the handle, on that call's stream.  No HIP call is made here, so an optimiser step does not rebuild the handle.
+ * Errors: null pointers, a tensor of another size -> VQAE_ERR_INVALID; a missing tensor -> VQAE_ERR_NOT_FOUND. */
+int vqae_classifier_update(vqae_classifier* c, const vqae_tensor* tensors, int n_tensors);
+/* Length of the packed gradient vector of vqae_classifier_loss_grad (0 for a null handle): the seven tensors, dense, in
+ * PyTorch's shapes and parameter order --
+ *   embedding.weight [K][E], in_conv.weight [C][E][3][3], in_conv.bias [C], hidden_conv1.weight [C][C][3][3],
+ *   hidden_conv1.bias [C], out_conv.weight [n_out][C][3][3], out_conv.bias [n_out]. */
+size_t vqae_classifier_grad_floats(const vqae_classifier* c);
+/* Bytes of scratch vqae_classifier_loss_grad needs for `batch` grids of h x w codes: the forward's stats partials, dL/dlogit
+ * (4 B per code), the fixed-point table gradient (8 B per table entry) and at most 512 fp64 rows of weight-gradient
+ * partials.  0 for an empty batch, a bad shape or n_out != 1. */
+size_t vqae_classifier_train_workspace_bytes(const vqae_classifier* c, int batch, int h, int w);
+/* Loss and gradients for codes_dev [B][h][w] (idx_dtype as stored) and mask_dev uint8 [B][h][w] (0 background, 1 tissue,
+ * 2 cancer), over the codes with mask != 0:
+ *   loss_sum = sum of pos_weight * t * softplus(-x) + (1 - t) * softplus(x),   t = mask - 1 (train_helpers.py:121-127), or,
+ *   with target_dev (optional fp32 [B][h][w], read only where mask != 0), the soft target in [0, 1] stored there: the
+ *   caller's label smoothing (train_helpers.py:133-135; the noise is the caller's);
+ *   dL/dlogit = sigmoid(x) * (1 - t + pos_weight * t) - pos_weight * t on those codes, 0 elsewhere.
+ * reduction 0 = 'sum', 1 = 'mean' (loss and gradients times 1 / n_valid of the WHOLE batch, applied once, in fp64; with no
+ * valid code the loss is nan and the gradients are 0).  Outputs:
+ *   grads_dev  double [vqae_classifier_grad_floats(c)], the gradients of the loss summed over the batch;
+ *   stats_dev  double [B][VQAE_CLS_STATS_K], exactly vqae_classifier_forward's rows (counts against the hard labels);
+ *   loss_dev   double [1].
+ * Border rule: activations and embeddings outside the grid are the constant 0 and pass no gradient; a code outside 0 .. K-1
+ * is a zero vector and its (non-existent) table row receives nothing.  Sums are fixed-order fp64 over fp32 products; the
+ * table gradient is accumulated in 64-bit fixed point (2^-30 resolution, |entry| < 8.6e9) with integer atomics.  All outputs
+ * are bit-identical between two calls on the same inputs.
+ * Errors, all before any HIP call: null c / codes / mask / grads / stats / loss / workspace, a bad idx_dtype, h < 1 or
+ * w < 1, batch < 0, a negative or non-finite pos_weight, a reduction other than 0 or 1 -> VQAE_ERR_INVALID; n_out != 1,
+ * batch > 65535 -> VQAE_ERR_UNSUPPORTED.  batch == 0 -> VQAE_OK with zero gradients and a zero loss. */
+int vqae_classifier_loss_grad(vqae_classifier* c, const void* codes_dev, int idx_dtype, int batch, int h, int w,
+                              const uint8_t* mask_dev, const float* target_dev, float pos_weight, int reduction,
+                              double* grads_dev, double* stats_dev, double* loss_dev, void* workspace_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
