@@ -334,13 +334,14 @@ void vq_code_stats_kernel(const float* __restrict__ z, const T* __restrict__ idx
     }
 }
 
-// EMA + Laplace smoothing (vq.py:60-74); single block.
+// EMA + Laplace smoothing (vq.py:60-74); single block.  decay, omd = 1 - decay, alpha and k_alpha = K * alpha are the
+// reference's Python doubles, each rounded to fp32 once by the host (torch rounds a Python scalar when it meets the
+// fp32 tensor); forming 1 - decay or K * alpha from already-rounded fp32 values gives other scalars.
 __global__ __launch_bounds__(1024)
 void vq_ema_update_kernel(float* __restrict__ embed, float* __restrict__ embed_avg, float* __restrict__ cluster_size,
                           const float* __restrict__ counts, const float* __restrict__ dw, int K, int D,
-                          float decay, float alpha) {
+                          float decay, float omd, float alpha, float k_alpha) {
     __shared__ float red[1024];
-    const float omd = 1.f - decay;
     float s = 0.f;
     for (int k = threadIdx.x; k < K; k += 1024) {
         const float cs = cluster_size[k] * decay + counts[k] * omd;   // mul_(decay).add_(new, alpha=1-decay)
@@ -354,7 +355,7 @@ void vq_ema_update_kernel(float* __restrict__ embed, float* __restrict__ embed_a
         __syncthreads();
     }
     const float n = red[0];
-    const float denom = n + (float)K * alpha;
+    const float denom = n + k_alpha;
     for (int64_t i = threadIdx.x; i < (int64_t)K * D; i += 1024) {
         const int k = (int)(i / D);
         const float ea = embed_avg[i] * decay + dw[i] * omd;
@@ -582,7 +583,9 @@ extern "C" int vqae_embed_code_f32(const void* idx, int idx_dtype, const float* 
 extern "C" int vqae_vq_code_stats_f32(const float* z, const void* idx, int idx_dtype, int64_t N, int K, int D,
                                       float* counts, float* dw, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    VQAE_REQUIRE(z && idx && counts && dw, VQAE_ERR_INVALID, "code_stats: null pointer");
+    VQAE_REQUIRE(N >= 0 && K >= 1, VQAE_ERR_INVALID, "code_stats: n_rows %lld, n_codes %d", (long long)N, K);
+    // an empty shard (N == 0: no z, no idx) still zero-fills counts / dw for the all-reduce that follows
+    VQAE_REQUIRE(counts && dw && (N == 0 || (z && idx)), VQAE_ERR_INVALID, "code_stats: null pointer");
     VQAE_REQUIRE(D >= 1 && D <= 512, VQAE_ERR_UNSUPPORTED, "code_stats: dim %d unsupported (<= 512)", D);
     const size_t lds = (size_t)16 * (D + 1) * sizeof(float);
     switch (idx_dtype) {
@@ -597,12 +600,14 @@ extern "C" int vqae_vq_code_stats_f32(const float* z, const void* idx, int idx_d
 }
 
 extern "C" int vqae_vq_ema_update_f32(float* embed, float* embed_avg, float* cluster_size, const float* counts,
-                                      const float* dw, int K, int D, float decay, float alpha, void* ws,
+                                      const float* dw, int K, int D, double decay, double alpha, void* ws,
                                       void* stream_) {
     (void)ws;
     hipStream_t stream = (hipStream_t)stream_;
     VQAE_REQUIRE(embed && embed_avg && cluster_size && counts && dw, VQAE_ERR_INVALID, "ema_update: null pointer");
-    vq_ema_update_kernel<<<1, 1024, 0, stream>>>(embed, embed_avg, cluster_size, counts, dw, K, D, decay, alpha);
+    VQAE_REQUIRE(K >= 1 && D >= 1, VQAE_ERR_INVALID, "ema_update: n_codes %d, dim %d", K, D);
+    vq_ema_update_kernel<<<1, 1024, 0, stream>>>(embed, embed_avg, cluster_size, counts, dw, K, D, (float)decay,
+                                                 (float)(1.0 - decay), (float)alpha, (float)((double)K * alpha));
     VQAE_LAUNCH_CHECK();
     return VQAE_OK;
 }

@@ -245,6 +245,7 @@ def embed_code(idx, embed):
 
 
 def vq_code_stats(z_flat, idx, n_codes):
+    """z_flat [N, D], idx [N] -> (counts [K], dw [K, D]) of _update_ema (vq.py:49-54); N = 0 gives zeros."""
     _need_gpu(z_flat, idx)
     z_flat = z_flat.contiguous()
     idx = idx.contiguous()
@@ -257,6 +258,8 @@ def vq_code_stats(z_flat, idx, n_codes):
 
 
 def vq_ema_update(embed, embed_avg, cluster_size, counts, dw, decay, laplace_alpha):
+    """The EMA + Laplace step of _update_ema, in place.  decay / laplace_alpha go down as doubles: 1 - decay and K * laplace_alpha
+    are formed from them and rounded to fp32 once, the scalars torch's fp32 tensors see (vq.py:60-71)."""
     _need_gpu(embed, embed_avg, cluster_size, counts, dw)
     K, D = embed.shape
     ws = torch.empty(16, dtype=torch.uint8, device=embed.device)

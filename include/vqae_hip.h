@@ -110,13 +110,16 @@ int vqae_embed_code_f32(const void* idx_dev, int idx_dtype, const float* embed_d
                         int dim, float* out_dev, void* stream);
 
 /* Training-mode bookkeeping (vq.py:47-74 `_update_ema`): counts n_k and sums dw_k of the rows
- * assigned to each code.  counts_dev [n_codes] fp32, dw_dev [n_codes][dim] fp32 (both overwritten). */
+ * assigned to each code.  counts_dev [n_codes] fp32, dw_dev [n_codes][dim] fp32 (both overwritten).
+ * n_rows == 0 (a rank's empty shard; z_dev / idx_dev may be NULL) zero-fills both.  dim <= 512. */
 int vqae_vq_code_stats_f32(const float* z_dev, const void* idx_dev, int idx_dtype, int64_t n_rows, int n_codes,
                            int dim, float* counts_dev, float* dw_dev, void* stream);
 /* EMA + Laplace smoothing step of `_update_ema` (vq.py:60-74), after the caller all-reduced
- * counts/dw over ranks (vq.py:57-58): updates cluster_size, embed_avg, embed in place. */
+ * counts/dw over ranks (vq.py:57-58): updates cluster_size, embed_avg, embed in place.
+ * decay and laplace_alpha are the module's Python doubles: decay, 1 - decay, laplace_alpha and
+ * n_codes * laplace_alpha are formed in double and rounded to fp32 once, as torch does. */
 int vqae_vq_ema_update_f32(float* embed_dev, float* embed_avg_dev, float* cluster_size_dev, const float* counts_dev,
-                           const float* dw_dev, int n_codes, int dim, float decay, float laplace_alpha,
+                           const float* dw_dev, int n_codes, int dim, double decay, double laplace_alpha,
                            void* workspace_dev /* >= 16 bytes */, void* stream);
 
 /* ---------------------------------------------------------------------------------------------

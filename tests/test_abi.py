@@ -49,6 +49,10 @@ def test_error_convention_without_gpu(amd):
         L.check(lib.vqae_vq_forward_f32(one, one, 16, 4, 5000, 1.0, one, 0, None, None, None, one, None))
     with pytest.raises(NotImplementedError):      # n_codes out of range
         L.check(lib.vqae_vq_forward_f32(one, one, 16, 70000, 8, 1.0, one, 0, None, None, None, one, None))
+    with pytest.raises(NotImplementedError):      # code_stats: dim above the kernel's 8 channel slots per lane
+        L.check(lib.vqae_vq_code_stats_f32(one, one, 0, 4, 3, 513, one, one, None))
+    with pytest.raises(AssertionError):           # code_stats: rows without z / idx (only an empty shard may pass NULL)
+        L.check(lib.vqae_vq_code_stats_f32(None, None, 0, 4, 3, 8, one, one, None))
 
 
 def test_ops_refuse_cpu_tensors(amd):

@@ -205,6 +205,60 @@ def test_ema_fixture(oracle):
         np.testing.assert_allclose(cs.numpy(), g[f"cluster_size{step}"], rtol=1e-6, atol=1e-7)
 
 
+def _ema_step_case(K, D, seed, zero_start):
+    """Rows with small integer channels (any fp32 summation of them is exact, so torch's fp32 one_hot.T @ flat hands the
+    step the same dw as the fp64 scatter-add and the comparison is of the step alone), K + 7 uniformly drawn codes
+    (about a third unused once K >= 32), a normal embed_avg, cluster_size at zero or at positive values."""
+    g = torch.Generator().manual_seed(seed)
+    N = K + 7
+    flat = torch.randint(-64, 65, (N, D), generator=g).float()
+    idx = torch.randint(0, K, (N,), generator=g)
+    ea = torch.randn(K, D, generator=g)
+    cs = torch.zeros(K) if zero_start else torch.rand(K, generator=g) * 20 + 0.5
+    return flat, idx, ea, cs
+
+
+def test_update_ema_exact_bounds_the_fp32_step(oracle):
+    """update_ema_exact (fp64, on the scalars the reference's fp32 tensors see) against the plain-torch fp32 update_ema --
+    the reference's own arithmetic -- inside the a-priori bounds an fp32 evaluation of the step is held to
+    (oracle.update_ema_bounds: 4u M_cs, 4u M_ea, (4u M_ea + c u |ea|) / sm), for every decay, start, K and D the HIP kernel
+    is tested at.  Then the restatement replays the reference-recorded `ema` fixture: there dw is torch's fp32 matmul of
+    normal rows, so embed_avg gets (1 - d) (n_k - 1) u sum|z| more, the any-order bound of an n_k-term fp32 sum."""
+    u = 2.0 ** -24
+    worst = [0.0, 0.0, 0.0]
+    for decay in (0.5, 0.9, 0.99, 0.999):
+        for zero_start in (True, False):
+            for K in (1, 5, 32, 1000, 1025, 3000):
+                for D in (1, 8, 130):
+                    flat, idx, ea, cs = _ema_step_case(K, D, 1000 * K + D, zero_start)
+                    got = oracle.update_ema(flat, idx, ea, cs, decay, 1e-5)
+                    ref = oracle.update_ema_exact(flat, idx, ea, cs, decay, 1e-5)
+                    assert float(ref[2].sum()) > 0
+                    b_cs, b_ea, b_e = oracle.update_ema_bounds(ref)
+                    for j, (x, r, b) in enumerate(((got[2], ref[2], b_cs), (got[1], ref[1], b_ea), (got[0], ref[0], b_e))):
+                        err = (x.double() - r).abs()
+                        assert bool((err <= b).all()), (decay, zero_start, K, D, j, float((err / b.clamp_min(1e-300)).max()))
+                        worst[j] = max(worst[j], float((err[b > 0] / b[b > 0]).max()))
+    print("torch fp32 step, worst distance / bound (cluster_size, embed_avg, embed):", worst)
+    assert min(worst) > 0.01                       # the bounds are of the size of fp32's error, not far above it
+
+    g = load_golden("ema")
+    D, K = int(g["D"]), int(g["K"])
+    z0, embed = oracle.make_vq_case(D, K, 1024, seed=3, adversarial=False)
+    z1, _ = oracle.make_vq_case(D, K, 1024, seed=4, adversarial=False)
+    e, ea, cs = oracle.init_ema(z0 * 1.7 + 0.3, embed, embed.clone(), torch.zeros(K))
+    for step, z in enumerate((z0 * 1.7 + 0.3, z1 * 1.7 + 0.3)):
+        idx, _, _ = oracle.vq_argmin_p4(z, e)
+        ref = oracle.update_ema_exact(z, idx, ea, cs, 0.99, 1e-5)
+        counts, _, dw_abs = oracle.code_stats_exact(z, idx, K)
+        extra = float(np.float32(1 - 0.99)) * (counts - 1).clamp_min(0).unsqueeze(-1) * u * dw_abs
+        b_cs, b_ea, b_e = oracle.update_ema_bounds(ref, extra)
+        for name, r, b in (("cluster_size", ref[2], b_cs), ("embed_avg", ref[1], b_ea), ("embed", ref[0], b_e)):
+            err = (torch.from_numpy(g[f"{name}{step}"]).double() - r).abs()
+            assert bool((err <= b).all()), (step, name, float((err / b).max()))
+        e, ea, cs = oracle.update_ema(z, idx, ea, cs, 0.99, 1e-5)
+
+
 def test_label_maxpool_matches_torch(oracle):
     lab = (torch.rand(3, 64, 64) > 0.97).to(torch.uint8)
     ref = torch.nn.functional.adaptive_max_pool2d(lab[:, None].half().float(), 32)[:, 0].to(torch.uint8)
