@@ -144,6 +144,9 @@ SYMBOLS = {
     "vqae_classifier_train_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
     "vqae_classifier_loss_grad": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_int,
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vqae_code_histogram_workspace_bytes": (c_size_t, [c_int, c_int64, c_int, c_int]),
+    "vqae_code_histogram": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                    c_void_p, c_void_p]),
     "vqae_flops_per_patch": (c_double, [c_void_p, c_int, c_int, c_int, c_int]),
     "vqae_prof_begin": (c_int, [c_int, c_int]),
     "vqae_prof_end": (c_int, [POINTER(c_double), POINTER(c_int), POINTER(c_double)]),

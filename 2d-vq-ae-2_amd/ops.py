@@ -401,3 +401,40 @@ def classifier_loss_grad(handle, codes, mask, target=None, pos_weight=1.0, reduc
                                           float(pos_weight), 1 if reduction == "mean" else 0, _p(grads), _p(stats), _p(loss),
                                           _p(ws), _stream()))
     return loss, grads, stats
+
+
+def code_histogram(codes, mask=None, *, num_embeddings, n_labels=None, pooled=False, out=None, bad=None):
+    """vqae_code_histogram on codes [B, ...] (uint8 / uint16 / int32 / int64 as stored, in HBM; B equally sized grids, any
+    contiguous view) and mask uint8 of the same shape or None -> (hist int64 [B or 1, n_labels, num_embeddings],
+    bad int64 [B or 1, 2]): hist[b, l, k] = positions of grid b with mask == l and code == k, exact; bad[:, 0] = codes outside
+    the table, bad[:, 1] = labels >= n_labels (neither is counted in hist).  pooled=True sums the batch into one table.
+    out= / bad= given: the counts are ADDED to them (a driver pools a split on the device and downloads once); a call that
+    passes only one of the two starts the other at zero.  n_labels defaults to 3 with a mask and 1 without."""
+    _need_gpu(codes, mask, out, bad)
+    assert codes.dim() >= 2, f"codes [B, ...] expected, got {tuple(codes.shape)}"
+    codes = codes.contiguous()
+    B = codes.shape[0]
+    n = codes.numel() // B if B else int(torch.Size(codes.shape[1:]).numel())
+    dev = codes.device
+    if n_labels is None:
+        n_labels = 3 if mask is not None else 1
+    if mask is not None:
+        assert mask.dtype == torch.uint8 and tuple(mask.shape) == tuple(codes.shape), (mask.dtype, mask.shape)
+        mask = mask.contiguous()
+    rows = 1 if pooled else B
+    K = int(num_embeddings)
+    for t, shape, what in ((out, (rows, int(n_labels), K), "out"), (bad, (rows, 2), "bad")):
+        assert t is None or (t.dtype == torch.int64 and tuple(t.shape) == shape and t.is_contiguous()), \
+            f"code_histogram: {what} must be a contiguous int64 tensor of shape {shape}"
+    accumulate = out is not None or bad is not None
+    if out is None:
+        out = (torch.zeros if accumulate else torch.empty)((rows, max(int(n_labels), 0), max(K, 0)), dtype=torch.int64, device=dev)
+    if bad is None:
+        bad = (torch.zeros if accumulate else torch.empty)((rows, 2), dtype=torch.int64, device=dev)
+    lib = L.lib()
+    if B == 0:                                                     # nothing to count (and no pointer to pass): zeros, or out as it is
+        return (out.zero_(), bad.zero_()) if not accumulate else (out, bad)
+    ws = torch.empty(max(8, lib.vqae_code_histogram_workspace_bytes(B, n, K, int(n_labels))), dtype=torch.uint8, device=dev)
+    L.check(lib.vqae_code_histogram(_p(codes), idx_code(codes.dtype), _p(mask), B, n, K, int(n_labels), int(bool(pooled)),
+                                    int(accumulate), _p(out), _p(bad), _p(ws), _stream()))
+    return out, bad

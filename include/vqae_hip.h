@@ -509,6 +509,38 @@ int vqae_classifier_loss_grad(vqae_classifier* c, const void* codes_dev, int idx
                               const uint8_t* mask_dev, const float* target_dev, float pos_weight, int reduction,
                               double* grads_dev, double* stats_dev, double* loss_dev, void* workspace_dev, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * 7. Counts of stored code grids -- produces what the reference commits as data under scripts/create_wsi_histograms/
+ *    (embedding_idx_histogram_{K}_{split}.npy, histogram_{split}.npy; it ships no program for them) and reads its loss
+ *    weights from (conf/model/optional_overrides/loss_f/bce_with_logits_loss_camelyon16_embeddings.yaml: "values taken
+ *    from validation marginal"): the joint (label x code) histogram of a batch of equally sized grids, in exact integers.
+ *      hist[b][l][k] = number of positions of grid b with mask == l and code == k.
+ *    No float appears anywhere: the result does not depend on summation order, partition or batch position, and a bin may
+ *    exceed 2^24 (vqae_vq_code_stats_f32, the training bookkeeping of section 1, counts in fp32).
+ * ------------------------------------------------------------------------------------------- */
+enum { VQAE_HIST_MAX_LABELS = 8 };
+/* Bytes of scratch vqae_code_histogram needs (0 for an empty batch or a bad shape; grows with batch). */
+size_t vqae_code_histogram_workspace_bytes(int batch, int64_t n_per_grid, int n_codes, int n_labels);
+/*   codes_dev  [B][n_per_grid] of idx_dtype (VQAE_IDX_*, as stored), any alignment the element type allows (a contiguous
+ *              view into a larger tensor; a uint8 grid may start at an odd address);
+ *   mask_dev   uint8 [B][n_per_grid] (any address), or NULL: every position then has label 0 and n_labels must be 1;
+ *   hist_dev   int64 [B][n_labels][n_codes], or [1][n_labels][n_codes] with pooled != 0 (the sum over the batch);
+ *   bad_dev    int64 [B or 1][2] or NULL: bad[0] = positions whose code lies outside 0 .. n_codes-1 (negative codes of the
+ *              signed widths included, whatever their label), bad[1] = positions with a code in range and a label >=
+ *              n_labels.  Neither kind is counted in hist or used as an index: hist.sum() + bad[0] + bad[1] == n_per_grid
+ *              per grid;
+ *   accumulate != 0: the counts are ADDED to what hist_dev and bad_dev hold (pool a whole split on the device, download
+ *              once); otherwise both are overwritten, every zero bin included;
+ *   workspace_dev  vqae_code_histogram_workspace_bytes(...) bytes, 8-byte aligned.
+ * Tables of n_labels * n_codes + 2 <= 32768 bins are counted in LDS (every shipped K = 128 .. 1024 with 3 labels, and
+ * K = 8192 with 3); larger ones, up to K = 65536 with 8 labels, with 64-bit integer atomics straight into hist_dev.
+ * Errors, all before any HIP call: null codes / hist / workspace, n_labels > 1 without a mask, a bad idx_dtype,
+ * n_per_grid < 1, batch < 0 -> VQAE_ERR_INVALID; n_codes outside 1 .. 65536, n_labels outside 1 .. VQAE_HIST_MAX_LABELS,
+ * batch > 65535 -> VQAE_ERR_UNSUPPORTED.  batch == 0 -> VQAE_OK (without accumulate a pooled table is zeroed). */
+int vqae_code_histogram(const void* codes_dev, int idx_dtype, const uint8_t* mask_dev, int batch, int64_t n_per_grid,
+                        int n_codes, int n_labels, int pooled, int accumulate, int64_t* hist_dev, int64_t* bad_dev,
+                        void* workspace_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
