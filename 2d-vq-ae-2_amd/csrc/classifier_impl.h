@@ -39,16 +39,7 @@ __device__ __forceinline__ int64_t load_code(const void* __restrict__ p, int dt,
 
 __device__ __forceinline__ float softplus(float x) { return fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x))); }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
+using vqae::wave_sum;                   // double / int shuffle sums (common.h)
 
 inline bool idx_dtype_ok(int dt) { return dt == VQAE_IDX_I64 || dt == VQAE_IDX_U8 || dt == VQAE_IDX_U16 || dt == VQAE_IDX_I32; }
 

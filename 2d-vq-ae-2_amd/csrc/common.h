@@ -99,6 +99,28 @@ __device__ __forceinline__ void lds_barrier() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
+// Wave-wide reductions by shuffle (64 lanes): lane 0 holds the result.
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_down(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_down(v, o, 64));
+    return v;
+}
+
 // Environment switches (DESIGN.md lists them): the integer value of `name`, `dflt` where it is unset.  A VQAE_NO_* switch is
 // `env_int(name, 0) != 0` (off unless set non-zero); VQAE_WINO43 / VQAE_W43_SPLIT are `env_int(name, 1) != 0` (on unless =0).
 // When a switch is read -- per handle, per process (`static const`) or per call -- is the caller's choice and part of its contract.

@@ -18,11 +18,11 @@
 // reads 4 consecutive k at 8u + 4h and feeds them to 4 consecutive MFMAs; A and B use the same k
 // permutation, which the sum over k does not see.
 #include "kernels.h"
+#include "mfma.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace vqae;
 
 struct ConvK {
     const float* __restrict__ x;
@@ -37,7 +37,7 @@ struct ConvK {
     int has_scale, has_bias_s, has_act;
     float scale, bias_s, act_a, act_b;
     // fused tail (trunk, C = 128): conv3 of this block [+ conv1 of the next block], see TAIL below
-    const float* __restrict__ w3;        // [C][C] in MFMA fragment order for this engine (vqae::wino_frag_weight, k-slice SK)
+    const float* __restrict__ w3;        // [C][C] in MFMA fragment order for this engine (vqae::frag_weight, k-slice SK)
     const float* __restrict__ w1n;       // same, the NEXT block's conv1 (TAIL == 2)
     float* y2;                           // [M][128]: next block's t1 (TAIL == 2)
     float t_scale, t_b4, n_b1a, n_b1b, n_b2a, n_b2b;
@@ -64,11 +64,6 @@ using vqae::elu_act;                     // ELU(alpha = 1), branch-free (common.
 // ---- matrix-engine policy: exact-fp32 MFMA (32x32x2, 4 per 8-deep k-slice) or 16-bit MFMA (32x32x16, one per
 // 16-deep k-slice; autocast modes only).  Both use the same 32x32 C/D layout and the same LDS image idea:
 // [row][KC + PAD] elements, lane (i = l&31, h = l>>5) reads SK/2 consecutive k at SK*u + (SK/2)*h.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
 template <int DT, bool M16> struct MP {               // fp32 engine (any DT: DT only adds rounding points)
     using elem = float;
     using frag = f32x4;
@@ -81,41 +76,21 @@ template <int DT, bool M16> struct MP {               // fp32 engine (any DT: DT
     static __device__ __forceinline__ frag load_b(const float* q) { return *reinterpret_cast<const f32x4*>(q); }
     static __device__ __forceinline__ elem cvt(float v) { return v; }
 };
-template <> struct MP<VQAE_DT_BF16, true> {
-    using elem = __bf16;
-    using frag = bf16x8;
+template <int DT> struct MP<DT, true> {               // 16-bit engine: Mfma16<DT>
+    using M = Mfma16<DT>;
+    using elem = typename M::elem;
+    using frag = typename M::x8;
+    using x4 = typename M::x4;
     static constexpr int SK = 16, PAD = 8;
-    static __device__ __forceinline__ void mma(f32x16& acc, const frag& a, const frag& b) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
-    }
-    static __device__ __forceinline__ void store4(elem* d, f32x4 v) { *reinterpret_cast<bf16x4*>(d) = __builtin_convertvector(v, bf16x4); }
+    static __device__ __forceinline__ void mma(f32x16& acc, const frag& a, const frag& b) { acc = M::mma(a, b, acc); }
+    static __device__ __forceinline__ void store4(elem* d, f32x4 v) { *reinterpret_cast<x4*>(d) = __builtin_convertvector(v, x4); }
     static __device__ __forceinline__ frag load_b(const float* q) {
-        const bf16x4 lo = __builtin_convertvector(*reinterpret_cast<const f32x4*>(q), bf16x4);
-        const bf16x4 hi = __builtin_convertvector(*reinterpret_cast<const f32x4*>(q + 4), bf16x4);
+        const x4 lo = __builtin_convertvector(*reinterpret_cast<const f32x4*>(q), x4);
+        const x4 hi = __builtin_convertvector(*reinterpret_cast<const f32x4*>(q + 4), x4);
         return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
     }
-    static __device__ __forceinline__ elem cvt(float v) { return (__bf16)v; }
+    static __device__ __forceinline__ elem cvt(float v) { return (elem)v; }
 };
-template <> struct MP<VQAE_DT_F16, true> {
-    using elem = _Float16;
-    using frag = f16x8;
-    static constexpr int SK = 16, PAD = 8;
-    static __device__ __forceinline__ void mma(f32x16& acc, const frag& a, const frag& b) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc, 0, 0, 0);
-    }
-    static __device__ __forceinline__ void store4(elem* d, f32x4 v) { *reinterpret_cast<f16x4*>(d) = __builtin_convertvector(v, f16x4); }
-    static __device__ __forceinline__ frag load_b(const float* q) {
-        const f16x4 lo = __builtin_convertvector(*reinterpret_cast<const f32x4*>(q), f16x4);
-        const f16x4 hi = __builtin_convertvector(*reinterpret_cast<const f32x4*>(q + 4), f16x4);
-        return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    }
-    static __device__ __forceinline__ elem cvt(float v) { return (_Float16)v; }
-};
-template <int DT> __device__ __forceinline__ float round_ct(float v) {
-    if (DT == VQAE_DT_BF16) return (float)(__bf16)v;
-    if (DT == VQAE_DT_F16) return (float)(_Float16)v;
-    return v;
-}
 
 // TAIL (KC = 32, Cin = Cout = NT in {64, 128}): after the 3x3 conv2 of a trunk Fixup block the same
 // workgroup also runs   TAIL >= 1: conv3 (1x1) + scale/bias4 + residual  -> block output (in place over x)
@@ -131,7 +106,7 @@ void conv_mfma_kernel(const ConvK p) {
     using elem = typename P::elem;
     using frag = typename P::frag;
     constexpr bool R16 = DT != VQAE_DT_F32;
-    auto rnd = [&](float v) { return round_ct<DT>(v); };
+    auto rnd = [&](float v) { return round_to<DT>(v); };
     constexpr int SK = P::SK;                        // k-slice per fragment read
     constexpr int LDR = KC + P::PAD;                 // LDS row stride (elements)
     constexpr int WN = (NT == 128) ? 2 : 1;          // waves along N

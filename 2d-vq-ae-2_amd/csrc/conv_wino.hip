@@ -31,12 +31,11 @@
 // per tile, two take 260 k for two.  The same stamps placed the cost of this kernel's first version in the L1 tag pipe
 // (row-major weight fragments), not in HBM or the MFMAs.  DESIGN.md section 4 has the roofline numbers, section 8 what would move them.
 #include "kernels.h"
+#include "mfma.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-using vqae::elu_act;
+using namespace vqae;
 
 struct WinoK {
     const float* __restrict__ t1;        // [M][C] conv2 input (= ELU(conv1(.) + b2a) + b2b)
@@ -72,13 +71,6 @@ template <int C> struct WinoCfg {
     // takes HBM time PLUS matrix time (round 3).  At C = 128 the same prefetch measured slower (section 4, negative results).
     static constexpr int PREF = C <= 64 ? 1 : 0;
 };
-
-// Fragment order of a [C n][C k] matrix: element (n, k) of the 32-row tile n >> 5 and 8-wide k-slice k >> 3 goes to
-// lane (k >> 2 & 1) * 32 + (n & 31), component k & 3 -- what lane (li = n & 31, hh) feeds to MFMA number k & 3 of the slice.
-__device__ __forceinline__ int frag_offset(int n, int k, int c, int sk = 8) {   // sk: k-slice width (16 for 16-bit MFMA)
-    const int h = sk / 2;
-    return (((n >> 5) * (c / sk) + k / sk) * 64 + ((k / h) & 1) * 32 + (n & 31)) * h + k % h;
-}
 
 // DT: autocast rounding points compiled in (16-bit modes, C = 32 only: every conv operand and conv output is rounded
 // to bf16 / f16, the arithmetic stays fp32 -- conv(x16, w16) accumulated in fp32 is what torch.autocast computes, and its
@@ -605,11 +597,11 @@ __global__ void wino_weight_kernel(const float* __restrict__ w, int c, int dt, f
     }
 }
 
-// packed [c n][c k] (vqae_conv_pack_weight_f32) -> fragment order
-__global__ void frag_weight_kernel(const float* __restrict__ w, int c, int sk, float* __restrict__ out) {
+// packed [n_rows][K] (vqae_conv_pack_weight_f32: K = taps * cin, tap-major) -> fragment order (frag_offset, k-slice sk)
+__global__ void frag_weight_kernel(const float* __restrict__ w, int n_rows, int K, int sk, float* __restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= c * c) return;
-    out[frag_offset(i / c, i % c, c, sk)] = w[i];
+    if (i >= n_rows * K) return;
+    out[frag_offset(i / K, i % K, K, sk)] = w[i];
 }
 
 template <int C, int DT, bool WIDE>
@@ -694,8 +686,9 @@ int fixup_conv1(const float* x, const float* w1f, float pa, float pb, float aa, 
     return launch_conv1<32>(x, w1f, pa, pb, aa, ab, y, m, stream);
 }
 
-int wino_frag_weight(const float* w_packed_dev, int c, int sk, float* out_dev, hipStream_t stream) {
-    frag_weight_kernel<<<(unsigned)ceil_div(c * c, 256), 256, 0, stream>>>(w_packed_dev, c, sk, out_dev);
+int frag_weight(const float* w_packed_dev, int n_rows, int K, int sk, float* out_dev, hipStream_t stream) {
+    VQAE_REQUIRE(n_rows % 32 == 0 && (sk == 8 || sk == 16) && K % sk == 0, VQAE_ERR_INVALID, "frag_weight: %d x %d, k-slice %d", n_rows, K, sk);
+    frag_weight_kernel<<<(unsigned)ceil_div((int64_t)n_rows * K, 256), 256, 0, stream>>>(w_packed_dev, n_rows, K, sk, out_dev);
     VQAE_LAUNCH_CHECK();
     return VQAE_OK;
 }

@@ -28,20 +28,16 @@
 // The same kernel serves the level above the trunk (C = 64 on the 64-wide grid: 2 slices x 2 tile groups) and C = 256 on the code
 // grid (8 slices, 512 threads, one workgroup per CU).
 #include "kernels.h"
+#include "mfma.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-using vqae::elu_act;
-using vqae::lds_barrier;
+using namespace vqae;
 
 struct W43K {
     const float* __restrict__ t1;        // [M][C] conv2 input
     const float* __restrict__ U;         // G g G^T, [36 pos][C / 32 slices][C / 16 k-groups][2 blocks][64 lanes][4]
-    const float* __restrict__ w3;        // [C][C], fragment order of conv_wino.hip (k-slice 8)
+    const float* __restrict__ w3;        // [C][C], fragment order (frag_offset, k-slice 8)
     const float* __restrict__ w1n;       // same, the next block's conv1 (TAIL == 2)
     float* xio;                          // [M][C] residual stream, updated in place
     float* y2;                           // [M][C] next block's t1 (TAIL == 2)

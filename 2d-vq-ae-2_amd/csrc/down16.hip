@@ -19,34 +19,16 @@
 //   phase 2  conv2 from T1 (K = 4 CO); skip_conv from global (L2 hits, requested before conv2) -> T2[out pixel][c]
 //   phase 3  conv3 from T2, epilogue, fp32 store.
 #include "kernels.h"
+#include "mfma.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-using vqae::elu_act;
-using vqae::lds_barrier;
+using namespace vqae;
 
-template <int DT> struct D16;
-template <> struct D16<VQAE_DT_BF16> {
-    using x8 = bf16x8; using x4 = bf16x4;
-    static __device__ __forceinline__ f32x16 mma(const x8& a, const x8& b, const f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ float rnd(float v) { return (float)(__bf16)v; }
-};
-template <> struct D16<VQAE_DT_F16> {
-    using x8 = f16x8; using x4 = f16x4;
-    static __device__ __forceinline__ f32x16 mma(const x8& a, const x8& b, const f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ float rnd(float v) { return (float)(_Float16)v; }
-};
+// MFMA rows of a CO-channel output (CI = 8: 16 channels + 16 zero rows of the packed weights), and the output rows
+// (of 32 pixels) a workgroup owns: 4096 / rows pixels
+constexpr int d16_mfma_rows(int co) { return co < 32 ? 32 : co; }
+constexpr int d16_tile_rows(int cin) { return 4096 / d16_mfma_rows(2 * cin) / 32; }
 
 struct Down16K {
     const float* __restrict__ x;         // [B][H][W][CI] fp32
@@ -57,19 +39,19 @@ struct Down16K {
     float* __restrict__ y;               // [B][H/2][W/2][CO] fp32
     int H, W;                            // input size; W / 2 is a multiple of 32
     int tiles_x, tiles_y;                // tiles of ROWS x 32 output pixels
-    float b1a, b1b, b2a, b2b, b3a, b3b, b4, scale, b1c, b1d;
+    FixupScalars s;                      // the block's ten Fixup scalars
 };
 
 template <int CI, int DT>
 __global__ __launch_bounds__(256, 2)
 void down16_kernel(const Down16K p) {
-    using E = D16<DT>;
+    using E = Mfma16<DT>;
     using x8 = typename E::x8;
     using x4 = typename E::x4;
     constexpr int CO = 2 * CI;
-    constexpr int COP = CO < 32 ? 32 : CO;            // MFMA rows (CI = 8: 16 channels + 16 zero rows of the packed weights)
-    constexpr int TPX = 4096 / COP;                   // output pixels per workgroup
-    constexpr int ROWS = TPX / 32;                    // output rows per workgroup
+    constexpr int COP = d16_mfma_rows(CO);            // MFMA rows
+    constexpr int ROWS = d16_tile_rows(CI);           // output rows per workgroup
+    constexpr int TPX = 32 * ROWS;                    // output pixels per workgroup
     constexpr int NT = COP / 32;                      // 32-channel output tiles
     constexpr int NQ = CO >= 32 ? 4 : CO / 8;         // register quads of a lane that hold real channels (8 g + 4 hh ..)
     constexpr int PS1 = 4 * CO * 2 + 16;              // T1 bytes per output pixel (odd number of 16-B slots: conflict-free b128 reads)
@@ -129,8 +111,8 @@ void down16_kernel(const Down16K p) {
         for (int u = 0; u < KU; ++u) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                xin[i][u][0][e] = elu_act(xin[i][u][0][e] + p.b1a) + p.b1b;
-                xin[i][u][1][e] = elu_act(xin[i][u][1][e] + p.b1a) + p.b1b;
+                xin[i][u][0][e] = elu_act(xin[i][u][0][e] + p.s.b1a) + p.s.b1b;
+                xin[i][u][1][e] = elu_act(xin[i][u][1][e] + p.s.b1a) + p.s.b1b;
             }
             xa[u] = cvt8(xin[i][u][0], xin[i][u][1]);                                      // conv1 input cast
         }
@@ -146,7 +128,7 @@ void down16_kernel(const Down16K p) {
             for (int g = 0; g < NQ; ++g) {
                 f32x4 o;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = elu_act(E::rnd(acc[4 * g + e]) + p.b2a) + p.b2b;   // conv1 output cast
+                for (int e = 0; e < 4; ++e) o[e] = elu_act(E::rnd(acc[4 * g + e]) + p.s.b2a) + p.s.b2b;   // conv1 output cast
                 *reinterpret_cast<x4*>(dst + (32 * ct + 8 * g) * 2) = __builtin_convertvector(o, x4);  // conv2 input cast
             }
         }
@@ -196,7 +178,7 @@ void down16_kernel(const Down16K p) {
         for (int g = 0; g < NQ; ++g) {
             f32x4 o;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = elu_act(E::rnd(acc2[4 * g + e]) + p.b3a) + p.b3b;     // conv2 output cast
+            for (int e = 0; e < 4; ++e) o[e] = elu_act(E::rnd(acc2[4 * g + e]) + p.s.b3a) + p.s.b3b;     // conv2 output cast
             *reinterpret_cast<x4*>(dst + 16 * g) = __builtin_convertvector(o, x4);                    // conv3 input cast
         }
     }
@@ -215,8 +197,8 @@ void down16_kernel(const Down16K p) {
             xs[u % SKB][1] = *reinterpret_cast<const f32x4*>(sk_addr(u + SKB) + 4);
         }
         const x8 wv = wfrag(p.wsk, KSK, ct, u);
-        v0 = v0 + p.b1c;
-        v1 = v1 + p.b1c;
+        v0 = v0 + p.s.b1c;
+        v1 = v1 + p.s.b1c;
         accs = E::mma(wv, cvt8(v0, v1), accs);                                                         // skip_conv input cast
     }
     lds_barrier();                                      // T2 complete
@@ -236,19 +218,20 @@ void down16_kernel(const Down16K p) {
         f32x4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            float t = E::rnd(acc3[4 * g + e]) * p.scale;   // branch: conv3 * scale + bias4
-            t = t + p.b4;
-            o[e] = t + (E::rnd(accs[4 * g + e]) + p.b1d);  // + skip_conv(x + b1c) + b1d
+            float t = E::rnd(acc3[4 * g + e]) * p.s.scale;   // branch: conv3 * scale + bias4
+            t = t + p.s.b4;
+            o[e] = t + (E::rnd(accs[4 * g + e]) + p.s.b1d);  // + skip_conv(x + b1c) + b1d
         }
         *reinterpret_cast<f32x4*>(out + 8 * g) = o;
     }
 }
 
-// packed fp32 [>= n_rows][k_src] (vqae_conv_pack_weight_f32: rows beyond cout are zero; already rounded to the 16-bit
-// type) -> fragment order [n_rows/32][K/16][64 lanes][8], K = k_src rounded up to 16 with zeros:
-// lane (r, h) of k-step ks holds w[32 nt + r][16 ks + 8 h + j], j = 0..7
+// The 16-bit fragment order, for every kernel that reads 16-bit weights as the MFMA row operand (this file, trunk16.hip,
+// same8_16.hip, up16.hip): packed fp32 [>= n_rows][k_src] (vqae_conv_pack_weight_f32: k = tap * cin + c, rows beyond cout are
+// zero; already rounded to the 16-bit type) -> [n_rows/32][K/16][64 lanes][8], K = k_src rounded up to 16 with zeros:
+// lane (r, h) of k-step ks holds w[32 nt + r][16 ks + 8 h + j], j = 0..7 -- the MFMA row-operand fragment of that step
 template <typename EL>
-__global__ void pack16_rect_kernel(const float* __restrict__ w, int n_rows, int k_src, int K, EL* __restrict__ out) {
+__global__ void pack16_weight_kernel(const float* __restrict__ w, int n_rows, int k_src, int K, EL* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)n_rows * K) return;
     const int j = (int)(i & 7), lane = (int)((i >> 3) & 63);
@@ -260,7 +243,7 @@ __global__ void pack16_rect_kernel(const float* __restrict__ w, int n_rows, int 
 
 template <int CI, int DT>
 int launch_down16(const Down16K& k, int64_t n_tiles, hipStream_t stream) {
-    constexpr int CO = 2 * CI, TPX = 4096 / (CO < 32 ? 32 : CO);
+    constexpr int CO = 2 * CI, TPX = 32 * d16_tile_rows(CI);
     constexpr int lds_bytes = TPX * ((4 * CO * 2 + 16) + (CO * 2 + 16));
     if (int rc = vqae::set_max_dynamic_lds((const void*)down16_kernel<CI, DT>, lds_bytes)) return rc;
     down16_kernel<CI, DT><<<(unsigned)n_tiles, 256, lds_bytes, stream>>>(k);
@@ -276,22 +259,20 @@ bool down16_channels(int cin) { return cin == 8 || cin == 16 || cin == 32 || cin
 
 bool down16_supported(int cin, int h, int w) {
     if (!down16_channels(cin)) return false;
-    const int rows = (4096 / (2 * cin < 32 ? 32 : 2 * cin)) / 32;
-    return h % 2 == 0 && w % 64 == 0 && (h / 2) % rows == 0;
+    return h % 2 == 0 && w % 64 == 0 && (h / 2) % d16_tile_rows(cin) == 0;
 }
 
-static int pad_rows(int n) { return n < 32 ? 32 : n; }
 static int pad_k(int k) { return (k + 15) / 16 * 16; }
 
-size_t down16_weight_bytes(int n_rows, int K) { return (size_t)pad_rows(n_rows) * pad_k(K) * 2; }
+size_t down16_weight_bytes(int n_rows, int K) { return (size_t)d16_mfma_rows(n_rows) * pad_k(K) * 2; }
 
-int down16_pack_weight(const float* w_packed_dev, int n_rows, int K, int dtype, void* out_dev, hipStream_t stream) {
-    VQAE_REQUIRE((n_rows % 32 == 0 || n_rows == 16 || n_rows == 8) && K % 8 == 0, VQAE_ERR_INVALID, "down16_pack_weight: %d x %d", n_rows, K);
-    VQAE_REQUIRE(dtype == VQAE_DT_BF16 || dtype == VQAE_DT_F16, VQAE_ERR_INVALID, "down16_pack_weight: dtype %d", dtype);
-    const int nr = pad_rows(n_rows), kp = pad_k(K);
+int pack16_weight(const float* w_packed_dev, int n_rows, int K, int dtype, void* out_dev, hipStream_t stream) {
+    VQAE_REQUIRE((n_rows % 32 == 0 || n_rows == 16 || n_rows == 8) && K % 8 == 0, VQAE_ERR_INVALID, "pack16_weight: %d x %d", n_rows, K);
+    VQAE_REQUIRE(dtype == VQAE_DT_BF16 || dtype == VQAE_DT_F16, VQAE_ERR_INVALID, "pack16_weight: dtype %d", dtype);
+    const int nr = d16_mfma_rows(n_rows), kp = pad_k(K);
     const int64_t n = (int64_t)nr * kp;
-    if (dtype == VQAE_DT_BF16) pack16_rect_kernel<__bf16><<<(unsigned)ceil_div(n, 256), 256, 0, stream>>>(w_packed_dev, nr, K, kp, (__bf16*)out_dev);
-    else pack16_rect_kernel<_Float16><<<(unsigned)ceil_div(n, 256), 256, 0, stream>>>(w_packed_dev, nr, K, kp, (_Float16*)out_dev);
+    if (dtype == VQAE_DT_BF16) pack16_weight_kernel<__bf16><<<(unsigned)ceil_div(n, 256), 256, 0, stream>>>(w_packed_dev, nr, K, kp, (__bf16*)out_dev);
+    else pack16_weight_kernel<_Float16><<<(unsigned)ceil_div(n, 256), 256, 0, stream>>>(w_packed_dev, nr, K, kp, (_Float16*)out_dev);
     VQAE_LAUNCH_CHECK();
     return VQAE_OK;
 }
@@ -305,10 +286,8 @@ int down16_block(const float* x, const void* w1h, const void* w2h, const void* w
     Down16K k;
     k.x = x; k.w1 = w1h; k.w2 = w2h; k.w3 = w3h; k.wsk = wskh; k.y = y;
     k.H = H; k.W = W;
-    const int rows = (4096 / (2 * cin < 32 ? 32 : 2 * cin)) / 32;
-    k.tiles_x = (W / 2) / 32; k.tiles_y = (H / 2) / rows;
-    k.b1a = s.b1a; k.b1b = s.b1b; k.b2a = s.b2a; k.b2b = s.b2b; k.b3a = s.b3a;
-    k.b3b = s.b3b; k.b4 = s.b4; k.scale = s.scale; k.b1c = s.b1c; k.b1d = s.b1d;
+    k.tiles_x = (W / 2) / 32; k.tiles_y = (H / 2) / d16_tile_rows(cin);
+    k.s = s;
     const int64_t n_tiles = (int64_t)B * k.tiles_x * k.tiles_y;
     VQAE_REQUIRE(n_tiles < (1ll << 31), VQAE_ERR_UNSUPPORTED, "down16_block: too many tiles");
 #define VQAE_D16(CI_) (dtype == VQAE_DT_BF16 ? launch_down16<CI_, VQAE_DT_BF16>(k, n_tiles, stream) : launch_down16<CI_, VQAE_DT_F16>(k, n_tiles, stream))

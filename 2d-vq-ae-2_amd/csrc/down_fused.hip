@@ -12,14 +12,16 @@
 //            layout T1[out pixel][tap * CO + c]
 //   phase 2  conv2 from T1 (K = 4 CO)                              -> t2 into LDS T2[out pixel][c] (over T1)
 //   phase 3  conv3 from T2 and skip_conv from global, epilogue, store.
-// Weight matrices are read from L2 in MFMA fragment order (contiguous wave-wide loads, see conv_wino.hip).
+// Weight matrices are read from L2 in MFMA fragment order (contiguous wave-wide loads; frag_offset, mfma.h).
 #include "kernels.h"
+#include "mfma.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-using vqae::elu_act;
+using namespace vqae;
+
+// output rows (of 32 pixels) a workgroup owns: 4096 / CO pixels
+constexpr int down_tile_rows(int cin) { return 4096 / (2 * cin) / 32; }
 
 struct DownK {
     const float* __restrict__ x;         // [B][H][W][CI]
@@ -30,7 +32,7 @@ struct DownK {
     float* __restrict__ y;               // [B][H/2][W/2][CO]
     int H, W;                            // input size; W / 2 is a multiple of 32
     int tiles_x, tiles_y;                // tiles of ROWS x 32 output pixels
-    float b1a, b1b, b2a, b2b, b3a, b3b, b4, scale, b1c, b1d;
+    FixupScalars s;                      // the block's ten Fixup scalars
 };
 
 // DT: autocast cast points compiled in (every conv operand and conv output rounded to bf16 / f16; weights arrive
@@ -44,8 +46,8 @@ void down_block_kernel(const DownK p) {
         return v;
     };
     constexpr int CO = 2 * CI;
-    constexpr int TPX = 4096 / CO;                    // output pixels per workgroup
-    constexpr int ROWS = TPX / 32;                    // output rows per workgroup
+    constexpr int ROWS = down_tile_rows(CI);          // output rows per workgroup
+    constexpr int TPX = 32 * ROWS;                    // output pixels per workgroup
     constexpr int NT = CO / 32;                       // 32-channel output tiles
     constexpr int LD1 = 4 * CO + 4;                   // T1 row stride (floats)
     constexpr int LD2 = CO + 4;                       // T2 row stride
@@ -92,7 +94,7 @@ void down_block_kernel(const DownK p) {
 #pragma unroll
         for (int u = 0; u < KU; ++u)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) xin[i][u][e] = rnd(elu_act(xin[i][u][e] + p.b1a) + p.b1b);   // conv1 input cast
+            for (int e = 0; e < 4; ++e) xin[i][u][e] = rnd(elu_act(xin[i][u][e] + p.s.b1a) + p.s.b1b);   // conv1 input cast
 #pragma unroll
     for (int ct = 0; ct < NT; ++ct) {
         if (ct + 1 < NT) {
@@ -115,7 +117,7 @@ void down_block_kernel(const DownK p) {
             for (int g = 0; g < 4; ++g) {
                 f32x4 o;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = rnd(elu_act(rnd(acc[4 * g + e]) + p.b2a) + p.b2b);   // conv1 output / conv2 input casts
+                for (int e = 0; e < 4; ++e) o[e] = rnd(elu_act(rnd(acc[4 * g + e]) + p.s.b2a) + p.s.b2b);   // conv1 output / conv2 input casts
                 *reinterpret_cast<f32x4*>(dst + 8 * g) = o;
             }
         }
@@ -167,7 +169,7 @@ void down_block_kernel(const DownK p) {
             f32x4 v = xs[u % SKB];
             if (u + SKB < KSK) xs[u % SKB] = *reinterpret_cast<const f32x4*>(sk_addr(u + SKB));
             const f32x4 wv = wfrag(p.wsk, KSK, ct, u);
-            v = v + p.b1c;
+            v = v + p.s.b1c;
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = rnd(v[e]);                                   // skip_conv input cast
 #pragma unroll
@@ -182,7 +184,7 @@ void down_block_kernel(const DownK p) {
         for (int g = 0; g < 4; ++g) {
             f32x4 o;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = rnd(elu_act(rnd(acc2[4 * g + e]) + p.b3a) + p.b3b);  // conv2 output / conv3 input casts
+            for (int e = 0; e < 4; ++e) o[e] = rnd(elu_act(rnd(acc2[4 * g + e]) + p.s.b3a) + p.s.b3b);  // conv2 output / conv3 input casts
             *reinterpret_cast<f32x4*>(dst + 8 * g) = o;
         }
     }
@@ -209,25 +211,17 @@ void down_block_kernel(const DownK p) {
         f32x4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            float t = rnd(acc3[4 * g + e]) * p.scale;   // branch: conv3 * scale + bias4
-            t = t + p.b4;
-            o[e] = t + (rnd(accs[4 * g + e]) + p.b1d);  // + skip_conv(x + b1c) + b1d
+            float t = rnd(acc3[4 * g + e]) * p.s.scale;   // branch: conv3 * scale + bias4
+            t = t + p.s.b4;
+            o[e] = t + (rnd(accs[4 * g + e]) + p.s.b1d);  // + skip_conv(x + b1c) + b1d
         }
         *reinterpret_cast<f32x4*>(out + 8 * g) = o;
     }
 }
 
-// packed [n][K] (vqae_conv_pack_weight_f32: K = taps * cin, tap-major) -> MFMA fragment order [n-tile][k-slice][lane][4]
-__global__ void frag_rect_kernel(const float* __restrict__ w, int n_rows, int K, float* __restrict__ out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_rows * K) return;
-    const int n = i / K, k = i % K;
-    out[(((n >> 5) * (K / 8) + (k >> 3)) * 64 + ((k >> 2) & 1) * 32 + (n & 31)) * 4 + (k & 3)] = w[i];
-}
-
 template <int CI, int DT>
 int launch_down_dt(const DownK& k, int64_t n_tiles, hipStream_t stream) {
-    constexpr int CO = 2 * CI, TPX = 4096 / CO;
+    constexpr int CO = 2 * CI, TPX = 32 * down_tile_rows(CI);
     constexpr int lds_bytes = TPX * (4 * CO + 4) * 4;
     if (int rc = vqae::set_max_dynamic_lds((const void*)down_block_kernel<CI, DT>, lds_bytes)) return rc;
     down_block_kernel<CI, DT><<<(unsigned)n_tiles, 256, lds_bytes, stream>>>(k);
@@ -250,15 +244,7 @@ bool down_block_channels(int cin) { return cin == 16 || cin == 32 || cin == 64; 
 
 bool down_block_supported(int cin, int h, int w) {
     if (!down_block_channels(cin)) return false;
-    const int rows = (4096 / (2 * cin)) / 32;
-    return h % 2 == 0 && w % 64 == 0 && (h / 2) % rows == 0;
-}
-
-int frag_weight_rect(const float* w_packed_dev, int n_rows, int K, float* out_dev, hipStream_t stream) {
-    VQAE_REQUIRE(n_rows % 32 == 0 && K % 8 == 0, VQAE_ERR_INVALID, "frag_weight_rect: %d x %d", n_rows, K);
-    frag_rect_kernel<<<(unsigned)ceil_div((int64_t)n_rows * K, 256), 256, 0, stream>>>(w_packed_dev, n_rows, K, out_dev);
-    VQAE_LAUNCH_CHECK();
-    return VQAE_OK;
+    return h % 2 == 0 && w % 64 == 0 && (h / 2) % down_tile_rows(cin) == 0;
 }
 
 int down_block(const float* x, const float* w1f, const float* w2f, const float* w3f, const float* wskf, int B, int H, int W,
@@ -270,10 +256,8 @@ int down_block(const float* x, const float* w1f, const float* w2f, const float* 
     DownK k;
     k.x = x; k.w1 = w1f; k.w2 = w2f; k.w3 = w3f; k.wsk = wskf; k.y = y;
     k.H = H; k.W = W;
-    const int rows = (4096 / (2 * cin)) / 32;
-    k.tiles_x = (W / 2) / 32; k.tiles_y = (H / 2) / rows;
-    k.b1a = s.b1a; k.b1b = s.b1b; k.b2a = s.b2a; k.b2b = s.b2b; k.b3a = s.b3a;
-    k.b3b = s.b3b; k.b4 = s.b4; k.scale = s.scale; k.b1c = s.b1c; k.b1d = s.b1d;
+    k.tiles_x = (W / 2) / 32; k.tiles_y = (H / 2) / down_tile_rows(cin);
+    k.s = s;
     const int64_t n_tiles = (int64_t)B * k.tiles_x * k.tiles_y;
     VQAE_REQUIRE(n_tiles < (1ll << 31), VQAE_ERR_UNSUPPORTED, "down_block: too many tiles");
     if (cin == 16) return launch_down<16>(k, n_tiles, dtype, stream);

@@ -11,14 +11,15 @@
 // All three weight matrices stay resident in LDS ([n][k] rows, +4 float pad: conflict-free
 // ds_read_b128 fragments); workgroups are persistent and walk tiles in an XCD-contiguous order.
 #include "common.h"
+#include "mfma.h"
 
 namespace {
+
+using namespace vqae;
 
 // autocast rounding point: compiled in only for the 16-bit instantiations (p.dt picks bf16 / f16)
 #define RND(v) (R16 ? vqae::round_dt((v), p.dt) : (v))
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct FusedP {
     const float* __restrict__ x;
@@ -32,7 +33,6 @@ struct FusedP {
     int dt;                              // VQAE_DT_*: autocast rounding points
 };
 
-using vqae::elu_act;
 
 template <int C, int TH>
 struct FusedCfg {
@@ -226,7 +226,6 @@ int launch_fused_r(FusedP& p, hipStream_t stream) {
 // MFMA sums channels {KQ*q' + k : q' = 0..3}, identically permuted for A and B.  Launched at C = 16 (the 16-bit modes
 // and VQAE_NO_WINO16); C = 8 runs on the VALU kernel below, which measured faster.
 // ------------------------------------------------------------------------------------------------
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 template <int C> struct KVec;
 template <> struct KVec<16> { typedef f32x4 type; };

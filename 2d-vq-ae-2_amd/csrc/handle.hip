@@ -281,25 +281,25 @@ int load_block(vqae_handle* h, const TensorMap& tm, const std::string& pre, int 
     }
 #undef S_
     // the packers below run on the null stream, in order; one synchronisation at the end covers them
-    auto frag_tail = [&](const float* src, float** dst) {                                // fp32 fragment order of a [cin][cin] 1x1 tail weight
-        if (int r = dev_alloc(h, (size_t)cin * cin * 4, (void**)dst)) return r;
-        return vqae::wino_frag_weight(src, cin, wino ? 8 : vqae::conv_tail_kslice(dt, cin), *dst, nullptr);
+    auto frag = [&](const float* src, int rows, int K, int sk, float** dst) {            // fp32 fragment order, [rows][K], k-slice sk
+        if (int r = dev_alloc(h, (size_t)rows * K * 4, (void**)dst)) return r;
+        return vqae::frag_weight(src, rows, K, sk, *dst, nullptr);
     };
-    auto frag_rect = [&](const float* src, int K, float** dst) {                         // fp32 fragment order, [cout][K]
-        if (int r = dev_alloc(h, (size_t)cout * K * 4, (void**)dst)) return r;
-        return vqae::frag_weight_rect(src, cout, K, *dst, nullptr);
+    auto frag_tail = [&](const float* src, float** dst) {                                // ... of a [cin][cin] 1x1 tail weight
+        return frag(src, cin, cin, wino ? 8 : vqae::conv_tail_kslice(dt, cin), dst);
     };
+    auto frag_rect = [&](const float* src, int K, float** dst) { return frag(src, cout, K, 8, dst); };   // ... [cout][K]
     auto split3 = [&](const float* src, void** dst) {                                   // 1x1 tail weight as three bf16 planes
         if (int r = dev_alloc(h, vqae::split_1x1_bytes(cin), dst)) return r;
         return vqae::split_1x1_weight(src, cin, *dst, nullptr);
     };
-    auto pack_t16 = [&](const float* src, int taps, void** dst) {                       // 16-bit fragments, [cin][taps * cin]
-        if (int r = dev_alloc(h, vqae::trunk16_weight_bytes(cin, taps), dst)) return r;
-        return vqae::trunk16_pack_weight(src, cin, taps, dt, *dst, nullptr);
+    auto pack_t16 = [&](const float* src, int taps, void** dst) {                       // 16-bit fragments, [cin][taps * cin],
+        if (int r = dev_alloc(h, vqae::trunk16_weight_bytes(cin, taps), dst)) return r;  // + trunk16_kernel's look-ahead slack
+        return vqae::pack16_weight(src, cin, taps * cin, dt, *dst, nullptr);
     };
     auto pack_r16 = [&](const float* src, int rows, int K, void** dst) {                // 16-bit fragments, [rows][K]
         if (int r = dev_alloc(h, vqae::down16_weight_bytes(rows, K), dst)) return r;
-        return vqae::down16_pack_weight(src, rows, K, dt, *dst, nullptr);
+        return vqae::pack16_weight(src, rows, K, dt, *dst, nullptr);
     };
     if (tail && ((rc = frag_tail(b->w1, &b->w1f)) || (rc = frag_tail(b->w3, &b->w3f)))) return rc;
     if (split && ((rc = split3(b->w1, &b->w1s)) || (rc = split3(b->w3, &b->w3s)))) return rc;

@@ -1,6 +1,7 @@
 // Internal interface of libvqae_hip.so: every vqae:: function that one .hip file defines and another calls, declared once
 // and grouped by defining file.  Each file that defines or calls one of them includes this header, so a changed parameter
-// list fails to compile instead of failing to link.  The C ABI is include/vqae_hip.h; shared inline helpers are in common.h.
+// list fails to compile instead of failing to link.  The C ABI is include/vqae_hip.h; shared inline helpers are in common.h (host and device)
+// and mfma.h (vector types, MFMA operands, the fragment order).
 #pragma once
 #include "common.h"
 
@@ -27,7 +28,7 @@ struct NextConv1 {
 // Channel counts conv_trunk_tail serves.
 bool conv_trunk_tail_channels(int c);
 // k-slice width of the engine conv_trunk_tail will use for this dtype / channel count (8: fp32 MFMA, 16: 16-bit MFMA);
-// w3 / next.w1 must be in fragment order (wino_frag_weight) for that width
+// w3 / next.w1 must be in fragment order (frag_weight) for that width
 int conv_tail_kslice(int dtype, int cin);
 // Trunk tail, direct form: conv2 (3x3 circular; `a` carries its geometry and its ELU epilogue) + conv3 (+ next conv1).
 // t1 [M][C] -> xio [M][C] updated in place (the block's output) and, when chained, next.t1_next [M][C].
@@ -42,8 +43,9 @@ bool wino_trunk_supported(int c, int h, int w, int dtype);
 size_t wino_weight_floats(int c);
 // w_oihw_dev [c][c][3][3] (PyTorch layout, device) -> U_dev [16][c][c] (fragment order)
 int wino_transform_weight(const float* w_oihw_dev, int c, int dtype, float* U_dev, hipStream_t stream);
-// packed [c][c] 1x1 weights (device) -> fragment order (device); sk = 8 (fp32 MFMA k-slice) or 16 (16-bit MFMA)
-int wino_frag_weight(const float* w_packed_dev, int c, int sk, float* out_dev, hipStream_t stream);
+// The fp32 fragment packer (frag_offset, mfma.h): packed [n_rows][K] weights (device; vqae_conv_pack_weight_f32) -> fragment
+// order (device); sk = 8 (fp32 MFMA k-slice) or 16 (16-bit MFMA); n_rows % 32 == 0, K % sk == 0
+int frag_weight(const float* w_packed_dev, int n_rows, int K, int sk, float* out_dev, hipStream_t stream);
 // Same contract as conv_trunk_tail: t1 -> xio in place (+ next.t1_next); U, w3, next.w1 in fragment order (k-slice 8).
 int wino_trunk_tail(const float* t1, const float* U, const float* w3, float act_a, float act_b, float t_scale, float t_b4,
                     float* xio, const NextConv1& next, int batch, int h, int w, int c, int dtype, hipStream_t stream);
@@ -75,17 +77,16 @@ int wino43_trunk_tail(const float* t1, const float* U, const float* w3, float ac
                       const void* Us, const void* w3s);
 
 // ---- trunk16.hip (16-bit modes) ----------------------------------------------------------------
-// Channel counts whose 'same' blocks take weights from trunk16_pack_weight (trunk16_block, or same16_16_block at C = 16 / 32).
+// Channel counts whose 'same' blocks take 16-bit fragments [c][taps * c] (trunk16_block, or same16_16_block at C = 16 / 32).
 bool trunk16_channels(int c);
 // (C, grid width) pairs with a kernel; off under VQAE_NO_TRUNK16 (the weights are packed regardless)
 bool trunk16_supported(int c, int h, int w, int dtype);
+// bytes of a buffer for pack16_weight(c, taps * c) that trunk16_kernel may read: the fragments + its ring's look-ahead
 size_t trunk16_weight_bytes(int c, int taps);
-// packed (vqae_conv_pack_weight_f32, rounded) fp32 weights [c][taps * c] on the device -> 16-bit fragment order
-int trunk16_pack_weight(const float* w_packed_dev, int c, int taps, int dtype, void* out_dev, hipStream_t stream);
 // fp32 [n] (n % 4 == 0) -> 16-bit, RNE: t1 of a chain head produced by the generic conv1 launch
 int trunk16_round_pack(const float* src, void* dst, int64_t n, int dtype, hipStream_t stream);
 // chain-head conv1: x fp32 [M][c] -> t1 16-bit [M][c] (out32: fp32, not rounded after the activation);
-// w1f from trunk16_pack_weight(.., taps = 1); C in {16, 32, 64, 128}, M % 32 == 0
+// w1f from pack16_weight([c][c]); C in {16, 32, 64, 128}, M % 32 == 0
 bool trunk16_head_supported(int c, int64_t m, int dtype);
 int trunk16_head(const float* x, const void* w1f, float b1a, float b1b, float b2a, float b2b, void* t1, int64_t m, int c,
                  int dtype, bool out32, hipStream_t stream);
@@ -96,10 +97,10 @@ int trunk16_block(const void* t1, const void* w2f, const void* w3f, float act_a,
 // ---- same8_16.hip (16-bit modes, whole 'same' block per launch) --------------------------------
 bool same8_16_channels(int c);          // 8
 bool same8_16_supported(int c, int h, int w, int dtype);
-// x -> y (x != y), [B][H][W][8] fp32; w1: packed fp32 (rounded) [>= 8][8]; w2h / w3h: down16_pack_weight(w2 [8][72]) / (w3 [8][8])
+// x -> y (x != y), [B][H][W][8] fp32; w1: packed fp32 (rounded) [>= 8][8]; w2h / w3h: pack16_weight(w2 [8][72]) / (w3 [8][8])
 int same8_16_block(const float* x, float* y, const float* w1_packed, const void* w2h, const void* w3h, int B, int H, int W,
                    const FixupScalars& s, int dtype, hipStream_t stream);
-// C = 16 / 32: x -> y (x != y), [B][H][W][C] fp32; w1h / w2h / w3h: trunk16_pack_weight(c = C; taps 1 / 9 / 1)
+// C = 16 / 32: x -> y (x != y), [B][H][W][C] fp32; w1h / w2h / w3h: pack16_weight([C][C]) / ([C][9 C]) / ([C][C])
 bool same16_16_supported(int c, int h, int w, int dtype);
 int same16_16_block(const float* x, float* y, const void* w1h, const void* w2h, const void* w3h, int B, int H, int W, int c,
                     const FixupScalars& s, int dtype, hipStream_t stream);
@@ -108,19 +109,18 @@ int same16_16_block(const float* x, float* y, const void* w1h, const void* w2h, 
 bool down_block_channels(int cin);      // 16, 32, 64
 // ... output width a multiple of 32, output height a multiple of the tile's rows (4, 2, 1)
 bool down_block_supported(int cin, int h, int w);
-// packed [n_rows][K] -> fragment order (n_rows % 32 == 0, K % 8 == 0)
-int frag_weight_rect(const float* w_packed_dev, int n_rows, int K, float* out_dev, hipStream_t stream);
-// x [B][H][W][cin] -> y [B][H/2][W/2][2 cin]; weights in fragment order (frag_weight_rect)
+// x [B][H][W][cin] -> y [B][H/2][W/2][2 cin]; weights in fragment order (frag_weight, k-slice 8)
 int down_block(const float* x, const float* w1f, const float* w2f, const float* w3f, const float* wskf, int B, int H, int W,
                int cin, const FixupScalars& s, int dtype, float* y, hipStream_t stream);
 bool down16_channels(int cin);          // 8, 16, 32, 64
 // ... output width a multiple of 32, output height a multiple of the tile's rows (4, 4, 2, 1)
 bool down16_supported(int cin, int h, int w);
 size_t down16_weight_bytes(int n_rows, int K);
-// packed [>= max(n_rows, 32)][K] fp32 (device; vqae_conv_pack_weight_f32 pads the rows to 128 with zeros) -> 16-bit fragment
-// order (device); n_rows % 32 == 0 or n_rows in {8, 16}; K % 8 == 0 (padded to 16 with zeros)
-int down16_pack_weight(const float* w_packed_dev, int n_rows, int K, int dtype, void* out_dev, hipStream_t stream);
-// as down_block, weights from down16_pack_weight; dtype bf16 / f16
+// The 16-bit fragment packer, for every kernel of the 16-bit modes but the stems: packed [>= max(n_rows, 32)][K] fp32 (device;
+// vqae_conv_pack_weight_f32 pads the rows to 128 with zeros; K = taps * cin, tap-major) -> 16-bit fragment order (device);
+// n_rows % 32 == 0 or n_rows in {8, 16}; K % 8 == 0 (padded to 16 with zeros); dtype bf16 / f16
+int pack16_weight(const float* w_packed_dev, int n_rows, int K, int dtype, void* out_dev, hipStream_t stream);
+// as down_block, weights from pack16_weight; dtype bf16 / f16
 int down16_block(const float* x, const void* w1h, const void* w2h, const void* w3h, const void* wskh, int B, int H, int W,
                  int cin, const FixupScalars& s, int dtype, float* y, hipStream_t stream);
 
@@ -128,7 +128,7 @@ int down16_block(const float* x, const void* w1h, const void* w2h, const void* w
 bool up16_channels(int c);              // the block's input channels: 16, 32, 64, 128
 // ... low-resolution width a multiple of 16
 bool up16_supported(int c, int h, int w, int dtype);
-// x, t1 (trunk16_head, out32): [B][H][W][c] fp32 -> y [B][2H][2W][c / 2] fp32; weights: down16_pack_weight([c][c]), ([c / 2][c]), ([c / 2][c])
+// x, t1 (trunk16_head, out32): [B][H][W][c] fp32 -> y [B][2H][2W][c / 2] fp32; weights: pack16_weight([c][c]), ([c / 2][c]), ([c / 2][c])
 int up16_block(const float* x, const float* t1, const void* w2h, const void* w3h, const void* wskh, int B, int H, int W, int c,
                const FixupScalars& s, int dtype, float* y, hipStream_t stream);
 

@@ -8,10 +8,11 @@
 // The three kernels here are byte movers: NHWC, one float4 (4 channels) per lane, consecutive lanes on consecutive
 // channel groups / pixels, so every wavefront access is a run of contiguous 16-byte words.
 #include "common.h"
+#include "mfma.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace vqae;
 
 constexpr int DW_PPS = 256;                 // output pixels per workgroup ("strip"): one partial sum row per strip
 

@@ -1,6 +1,7 @@
 // HBM-bound helper kernels of the VQ-AE hot path (gfx950): the 3-channel stems, bicubic x2,
 // boundary layout shuffles, label max-pool and slide-grid stitching.
 #include "kernels.h"
+#include "mfma.h"
 
 namespace {
 
@@ -11,7 +12,6 @@ namespace {
 // x_kind: 0 fp32 NHWC, 1 fp32 NCHW, 2 uint8 NHWC normalised on the fly
 //   ((u - mean255[c]) * inv_std255[c]: albumentations Normalize, camelyon16_transforms.yaml:15-23).
 // ------------------------------------------------------------------------------------------------
-struct Norm3 { float mean[4]; float inv[4]; };
 
 template <int CIN, int COUT>
 __global__ __launch_bounds__(256)

@@ -13,10 +13,13 @@
 // The u8 target form normalises (u - mean255[c]) * inv_std255[c] on the fly (as vqae_conv3x3_direct_f32 does), so the target
 // never exists in fp32.
 #include "common.h"
+#include "mfma.h"
 
 #include <cmath>
 
 namespace {
+
+using namespace vqae;
 
 constexpr int K = VQAE_METRICS_K;
 constexpr int NSTAT = 6;            // pass-1 partial row: sum d^2, sum huber, pmin, pmax, tmin, tmax (as double)
@@ -30,8 +33,6 @@ constexpr int IW = TW + WIN - 1;    // staged input columns
 // torchmetrics 0.8.2 `_gaussian(11, 1.5)`: exp(-(k / 1.5)^2 / 2), k = -5 .. 5, normalised to sum 1 -- its fp32 values
 __constant__ const float kG[WIN] = {0.0010283804f, 0.007598756f, 0.036000773f, 0.10936068f, 0.21300553f, 0.26601171f,
                                     0.21300553f,   0.10936068f,  0.036000773f, 0.007598756f, 0.0010283804f};
-
-struct Norm3 { float mean[4]; float inv[4]; };
 
 // target kinds: fp32 in the prediction's layout | uint8 NHWC (prediction NHWC) | uint8 NHWC (prediction NCHW)
 enum { TK_F32 = 0, TK_U8_SAME = 1, TK_U8_NCHW = 2 };
@@ -50,22 +51,6 @@ void ssim_tiles(int h, int w, int* tx, int* ty) {
 size_t stats_bytes(int batch, int64_t n) {
     int64_t chunk;
     return (size_t)vqae::round_up((int64_t)batch * stats_blocks(n, &chunk) * NSTAT * 8, 256);
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_down(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_down(v, o, 64));
-    return v;
 }
 
 // ---- pass 1 --------------------------------------------------------------------------------------------------------------

@@ -16,42 +16,17 @@
 //       4 hh .. 4 hh + 3 in its first register quad -> activation -> the two lane halves swap their 4 channels (one cross-lane
 //       read) -> conv3 (K = 8, padded) -> epilogue with the residual, both as whole 1 KiB rows per wave instruction.
 #include "kernels.h"
+#include "mfma.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-using vqae::elu_act;
-using vqae::lds_barrier;
-
-template <int DT> struct S16;
-template <> struct S16<VQAE_DT_BF16> {
-    using x8 = bf16x8; using x4 = bf16x4;
-    static __device__ __forceinline__ f32x16 mma(const x8& a, const x8& b, const f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ float rnd(float v) { return (float)(__bf16)v; }
-};
-template <> struct S16<VQAE_DT_F16> {
-    using x8 = f16x8; using x4 = f16x4;
-    static __device__ __forceinline__ f32x16 mma(const x8& a, const x8& b, const f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ float rnd(float v) { return (float)(_Float16)v; }
-};
+using namespace vqae;
 
 struct S8K {
     const float* __restrict__ x;         // [B][H][W][8] fp32
     float* __restrict__ y;               // [B][H][W][8] fp32 (not x: halo reads)
     const float* __restrict__ w1;        // packed fp32 [>= 8][8] (rounded to the 16-bit type): w1[co * 8 + k]
-    const void* __restrict__ w2f;        // 16-bit fragment order (down16_pack_weight): [32 rows (8 real)][80 (72 real)], k = tap * 8 + c
+    const void* __restrict__ w2f;        // 16-bit fragment order (pack16_weight): [32 rows (8 real)][80 (72 real)], k = tap * 8 + c
     const void* __restrict__ w3f;        //   [32 (8)][16 (8)]
     int H, W, tiles_x, tiles_y, n_tiles;
     float b1a, b1b, b2a, b2b, b3a, b3b, b4, scale;
@@ -63,7 +38,7 @@ constexpr int S8_HC = S8_TW + 2, S8_HP = (S8_TH + 2) * S8_HC;   // halo columns 
 template <int DT>
 __global__ __launch_bounds__(256, 2)
 void same8_16_kernel(const S8K p) {
-    using E = S16<DT>;
+    using E = Mfma16<DT>;
     using x8 = typename E::x8;
     using x4 = typename E::x4;
     __shared__ __attribute__((aligned(16))) char T1[S8_HP * 16];     // t1 of the halo, 8 x 16 bit per pixel
@@ -181,7 +156,7 @@ void same8_16_kernel(const S8K p) {
 struct S16K {
     const float* __restrict__ x;         // [B][H][W][C] fp32
     float* __restrict__ y;
-    const void* __restrict__ w1f;        // trunk16_pack_weight fragments: [32 rows (C real)][C]
+    const void* __restrict__ w1f;        // pack16_weight fragments: [32 rows (C real)][C]
     const void* __restrict__ w2f;        //   [32][9 * C], k = tap * C + c
     const void* __restrict__ w3f;        //   [32][C]
     int H, W, tiles_x, tiles_y, n_tiles;
@@ -192,7 +167,7 @@ struct S16K {
 template <int C, int DT>
 __global__ __launch_bounds__(256, 2)                     // 2 waves per SIMD: a 256-register budget keeps the MFMA results in VGPRs (no v_accvgpr_read)
 void same_small16_kernel(const S16K p) {
-    using E = S16<DT>;
+    using E = Mfma16<DT>;
     using x8 = typename E::x8;
     using x4 = typename E::x4;
     constexpr int KS = C / 16;                                            // k-steps of a 1x1 conv

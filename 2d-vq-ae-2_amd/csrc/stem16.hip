@@ -13,37 +13,13 @@
 // Out-of-image halo pixels are zeros (Conv2d padding = 1).  Arithmetic: bias and operands rounded to the 16-bit type, products
 // exact, fp32 accumulation (from the bias), result rounded -- conv3x3_direct_kernel's recipe; only the summation order differs.
 #include "kernels.h"
+#include "mfma.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-using vqae::lds_barrier;
-
-template <int DT> struct M16;
-template <> struct M16<VQAE_DT_BF16> {
-    using el = __bf16; using x8 = bf16x8; using x4 = bf16x4;
-    static __device__ __forceinline__ f32x16 mma(const x8& a, const x8& b, const f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ float rnd(float v) { return (float)(__bf16)v; }
-};
-template <> struct M16<VQAE_DT_F16> {
-    using el = _Float16; using x8 = f16x8; using x4 = f16x4;
-    static __device__ __forceinline__ f32x16 mma(const x8& a, const x8& b, const f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ float rnd(float v) { return (float)(_Float16)v; }
-};
+using namespace vqae;
 
 constexpr int ST_TH = 8, ST_TW = 64, ST_HC = ST_TW + 2, ST_HP = (ST_TH + 2) * ST_HC;   // tile, halo columns / pixels
-
-struct Norm3s { float mean[4]; float inv[4]; };
 
 // PyTorch [n_out][cin][3][3] fp32 -> fragment order [1 n-tile][KS][64 lanes][8] 16-bit, k = tap * cin + ci (zero beyond 9 cin),
 // rows >= n_out zero: lane (r, h) of k-step ks holds w[r][k = 16 ks + 8 h + j]
@@ -63,16 +39,16 @@ struct IStemK {
     const void* __restrict__ wf;         // fragments [2 k-steps][64][8]
     const float* __restrict__ bias;      // [C0] fp32 (rounded in the kernel)
     float* __restrict__ y;               // [B][H][W][C0] fp32
-    Norm3s nrm;
+    Norm3 nrm;
     int x_kind, H, W, tiles_x, tiles_y, n_tiles;
 };
 
 template <int C0, int DT>
 __global__ __launch_bounds__(256, 2)
 void istem16_kernel(const IStemK p) {
-    using E = M16<DT>;
+    using E = Mfma16<DT>;
     using x8 = typename E::x8;
-    using EL = typename E::el;
+    using EL = typename E::elem;
     constexpr int NQ = C0 / 8;                                            // register quads of a lane that hold real channels
     __shared__ __attribute__((aligned(16))) EL P[3 * ST_HP + 8];          // planes [c][halo pixel]; + a zero slot for k >= 27
     const int tid = threadIdx.x;
@@ -183,7 +159,7 @@ struct OStemK {
 template <int C, int DT>
 __global__ __launch_bounds__(256, 2)
 void ostem16_kernel(const OStemK p) {
-    using E = M16<DT>;
+    using E = Mfma16<DT>;
     using x8 = typename E::x8;
     using x4 = typename E::x4;
     constexpr int NS = (9 * C + 15) / 16;                                 // k-steps: 5 (C = 8, tap pairs), 9, 18

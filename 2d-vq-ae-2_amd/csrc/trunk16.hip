@@ -18,34 +18,11 @@
 // Rounding points are those of conv_mfma.hip (= torch.autocast): conv operands and conv outputs RNE to the 16-bit
 // type, fp32 accumulation, fp32 scalar bias / ELU / scale / residual arithmetic, no FMA contraction.
 #include "kernels.h"
+#include "mfma.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-using vqae::elu_act;
-
-template <int DT> struct E16;
-template <> struct E16<VQAE_DT_BF16> {
-    using elem = __bf16; using x8 = bf16x8; using x4 = bf16x4;
-    static __device__ __forceinline__ f32x16 mma(const x8& a, const x8& b, const f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ float rnd(float v) { return (float)(__bf16)v; }
-};
-template <> struct E16<VQAE_DT_F16> {
-    using elem = _Float16; using x8 = f16x8; using x4 = f16x4;
-    static __device__ __forceinline__ f32x16 mma(const x8& a, const x8& b, const f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ float rnd(float v) { return (float)(_Float16)v; }
-};
+using namespace vqae;
 
 using vqae::lds_barrier;                 // LDS-only workgroup barrier (common.h): global loads stay in flight across it
 
@@ -60,6 +37,20 @@ struct T16K {
     float act_a, act_b, t_scale, t_b4, n_b1a, n_b1b, n_b2a, n_b2b;
 };
 
+// columns a workgroup spans (W / TW column blocks per row).  C = 64 / 128 on grids >= 64 wide: 4 x 32 tiles (a 6 x 34 halo is
+// 1.6x the tile; single-row 1 x 128 tiles re-read 3x) -- with the whole-line epilogues below: -22 % at C = 64, W = 64
+constexpr int t16_tile_width(int c, int w) { return (c >= 64 && c <= 128 && w >= 64) ? 32 : (w < 128 ? w : 128); }
+
+// The (C, grid width) pairs with a kernel -- the trunk of cfg A / B (128 @ 32), cfg C (256 @ 32) and the levels above them --
+// as X(C, W, MT), MT = m-tiles per workgroup where the image rows allow it.
+// C >= 64: 4 m-tiles (128 pixels).  2 m-tiles (twice the resident workgroups) measured slower at C = 128: every weight
+// fragment then feeds 2 MFMAs instead of 4 and the kernel becomes bound by the L1 address path.
+// C <= 32: 16 m-tiles (512 pixels, 4 per wave) -- these levels are bound by the latency chain of a tile (stage -> conv2 ->
+// conv3 -> conv1'), so more pixels per wave in flight is what pays (cfg A bf16 +3.3 %, cfg B f16 encode +2.9 % over
+// 4 m-tiles; 8: +2.2 %).
+#define VQAE_T16_SHAPES(X) \
+    X(128, 32, 4) X(256, 32, 4) X(64, 64, 4) X(128, 64, 4) X(64, 128, 4) X(32, 128, 16) X(32, 256, 16) X(16, 128, 16) X(16, 256, 16)
+
 template <int C, int W, int MT> struct T16Cfg {
     static_assert(MT == 2 || MT == 4 || MT == 8 || MT == 16, "m-tiles per workgroup");
     static_assert(W == 32 || W == 64 || W == 128 || W == 256, "grid width");
@@ -69,9 +60,7 @@ template <int C, int W, int MT> struct T16Cfg {
     static constexpr int WM = C <= 32 ? (MT < 4 ? MT : 4) : 1;   // wave groups along the pixels: with one channel slice (C <= 32) every m-tile
     static constexpr int MTW = MT / WM;               //   gets its own wave (4x the waves, each 4x shorter); MTW = m-tiles per wave
     static constexpr int NT = NW * WM * 64;           // threads
-    // columns a workgroup spans (W / TW column blocks per row).  C = 64 / 128 on grids >= 64 wide: 4 x 32 tiles (a 6 x 34 halo is
-    // 1.6x the tile; single-row 1 x 128 tiles re-read 3x) -- with the whole-line epilogues below: -22 % at C = 64, W = 64
-    static constexpr int TW = (C >= 64 && C <= 128 && W >= 64) ? 32 : (W < 128 ? W : 128);
+    static constexpr int TW = t16_tile_width(C, W);   // columns a workgroup spans
     static constexpr int CB = W / TW;
     static constexpr int SEG = TW / 32;               // 32-pixel segments per tile row
     static constexpr int R = MT / SEG;                // image rows per workgroup (MT m-tiles of 32 pixels)
@@ -95,7 +84,7 @@ template <int C, int W, int MT, int DT, bool NEXT>
 __global__ __launch_bounds__((T16Cfg<C, W, MT>::NT), 2)
 void trunk16_kernel(const T16K p) {
     using K = T16Cfg<C, W, MT>;
-    using E = E16<DT>;
+    using E = Mfma16<DT>;
     using x8 = typename E::x8;
     using x4 = typename E::x4;
     constexpr int NT = K::NT, SEG = K::SEG, R = K::R, PS = K::PS, KS = K::KS, TW = K::TW, LW = K::LW, CB = K::CB, NQ = K::NQ;
@@ -364,23 +353,6 @@ void trunk16_kernel(const T16K p) {
     }
 }
 
-// ------------------------------------------------------------------------------------------------------------------
-// packed fp32 [C n][taps * C] (tap-major K, vqae_conv_pack_weight_f32; already rounded to the 16-bit type) ->
-// fragment order [C/32 n-tiles][taps * C/16 k-steps][64 lanes][8]: lane (r, h) of k-step (tap, ks) holds
-// w[n = 32 nt + r][tap][k = 16 ks + 8 h + j], j = 0..7 -- the MFMA row-operand fragment of that step.
-template <typename EL>
-__global__ void pack16_kernel(const float* __restrict__ w, int c, int taps, EL* __restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int ks_n = c / 16;
-    if (i >= (int64_t)(c < 32 ? 32 : c) * taps * c) return;
-    const int j = (int)(i & 7), lane = (int)((i >> 3) & 63);
-    const int64_t st = i >> 9;
-    const int s = (int)(st % (taps * ks_n)), nt = (int)(st / (taps * ks_n));
-    const int tap = s / ks_n, ks = s % ks_n;
-    const int n = nt * 32 + (lane & 31), k = ks * 16 + 8 * (lane >> 5) + j;
-    out[i] = (EL)w[(int64_t)n * taps * c + tap * c + k];              // rows >= c (c = 16) are the packed layout's zero padding
-}
-
 // conv1 of the block at the HEAD of a chain (the others get theirs from the previous block's launch), 16-bit modes:
 //   t1 = round16(ELU(round16(conv1x1(round16(ELU(x + b1a) + b1b))) + b2a) + b2b),   x fp32 [M][C] -> t1 16-bit [M][C]
 // A streaming launch (4 + 2 bytes per channel and pixel): no LDS tile, a wave takes G groups of 32 consecutive pixels per
@@ -393,7 +365,7 @@ template <int C, int DT, bool OUT32>
 __global__ __launch_bounds__(256, 2)
 void head16_kernel(const float* __restrict__ x, const void* __restrict__ w1f, float b1a, float b1b, float b2a, float b2b,
                    void* __restrict__ t1, int n_groups) {
-    using E = E16<DT>;
+    using E = Mfma16<DT>;
     using x8 = typename E::x8;
     using x4 = typename E::x4;
     constexpr int KU = C / 16, NT = C < 32 ? 1 : C / 32, NQ = C >= 32 ? 4 : C / 8;
@@ -493,27 +465,14 @@ int launch_t16(const T16K& k, bool next, int64_t n_px, hipStream_t stream) {
 
 template <int DT>
 int launch_t16_cw(const T16K& k, bool next, int c, int w, int64_t n_px, hipStream_t stream) {
-    const int h_rows = k.H;
-    // 4 m-tiles (128 pixels) per workgroup everywhere.  2 m-tiles (twice the resident workgroups) measured slower at
-    // C = 128: every weight fragment then feeds 2 MFMAs instead of 4 and the kernel becomes bound by the L1 address path.
-    if (c == 128 && w == 32) return launch_t16<128, 32, 4, DT>(k, next, n_px, stream);
-    if (c == 256 && w == 32) return launch_t16<256, 32, 4, DT>(k, next, n_px, stream);
-    if (c == 64 && w == 64) return launch_t16<64, 64, 4, DT>(k, next, n_px, stream);
-    if (c == 128 && w == 64) return launch_t16<128, 64, 4, DT>(k, next, n_px, stream);
-    if (c == 64 && w == 128) return launch_t16<64, 128, 4, DT>(k, next, n_px, stream);
-    // C <= 32: 16 m-tiles (512 pixels, 4 per wave) per workgroup where the rows allow it -- these levels are bound by the
-    // latency chain of a tile (stage -> conv2 -> conv3 -> conv1'), so more pixels per wave in flight is what pays
-    // (cfg A bf16 +3.3 %, cfg B f16 encode +2.9 % over 4 m-tiles; 8: +2.2 %).  4 m-tiles where the rows do not divide.
-    if (h_rows % 4 == 0) {
-        if (c == 32 && w == 128) return launch_t16<32, 128, 16, DT>(k, next, n_px, stream);
-        if (c == 32 && w == 256) return launch_t16<32, 256, 16, DT>(k, next, n_px, stream);
-        if (c == 16 && w == 128) return launch_t16<16, 128, 16, DT>(k, next, n_px, stream);
-        if (c == 16 && w == 256) return launch_t16<16, 256, 16, DT>(k, next, n_px, stream);
-    }
-    if (c == 32 && w == 128) return launch_t16<32, 128, 4, DT>(k, next, n_px, stream);
-    if (c == 32 && w == 256) return launch_t16<32, 256, 4, DT>(k, next, n_px, stream);
-    if (c == 16 && w == 128) return launch_t16<16, 128, 4, DT>(k, next, n_px, stream);
-    if (c == 16 && w == 256) return launch_t16<16, 256, 4, DT>(k, next, n_px, stream);
+    // the shape's m-tiles where its rows divide the image's, 4 m-tiles (what trunk16_supported checked) where they do not
+#define VQAE_T16_FULL(C_, W_, MT_) \
+    if (c == C_ && w == W_ && k.H % T16Cfg<C_, W_, MT_>::R == 0) return launch_t16<C_, W_, MT_, DT>(k, next, n_px, stream);
+#define VQAE_T16_FOUR(C_, W_, MT_) if (c == C_ && w == W_) return launch_t16<C_, W_, 4, DT>(k, next, n_px, stream);
+    VQAE_T16_SHAPES(VQAE_T16_FULL)
+    VQAE_T16_SHAPES(VQAE_T16_FOUR)
+#undef VQAE_T16_FULL
+#undef VQAE_T16_FOUR
     return vqae::fail(VQAE_ERR_UNSUPPORTED, "trunk16: C = %d on a %d-wide grid", c, w);
 }
 
@@ -523,27 +482,17 @@ namespace vqae {
 
 bool trunk16_channels(int c) { return c == 16 || c == 32 || c == 64 || c == 128 || c == 256; }
 
-// (C, grid width) pairs with a kernel: the trunk of cfg A / B (128 @ 32), cfg C (256 @ 32) and the levels above them
 bool trunk16_supported(int c, int h, int w, int dtype) {
     static const bool off = env_int("VQAE_NO_TRUNK16", 0) != 0;
     if (off || !trunk16_channels(c) || (dtype != VQAE_DT_BF16 && dtype != VQAE_DT_F16)) return false;
-    const bool cw = (c == 128 && w == 32) || (c == 256 && w == 32) || (c == 64 && w == 64) || (c == 128 && w == 64) ||
-                    (c == 64 && w == 128) || (c == 32 && w == 128) || (c == 32 && w == 256) || (c == 16 && w == 128) || (c == 16 && w == 256);
-    const int tw = (c >= 64 && c <= 128 && w >= 64) ? 32 : (w < 128 ? w : 128);       // T16Cfg::TW
-    return cw && h >= 1 && h % (128 / tw) == 0;
+#define VQAE_T16_IS(C_, W_, MT_) || (c == C_ && w == W_)
+    const bool cw = false VQAE_T16_SHAPES(VQAE_T16_IS);
+#undef VQAE_T16_IS
+    return cw && h >= 1 && h % (128 / t16_tile_width(c, w)) == 0;      // whole tile rows of a 4-m-tile (128-pixel) workgroup
 }
 
 // + the ring's look-ahead past the last n-tile's fragments (trunk16_kernel reads, never uses, NB KiB beyond them)
 size_t trunk16_weight_bytes(int c, int taps) { return (size_t)(c < 32 ? 32 : c) * c * taps * 2 + (size_t)(NB_MAX + 1) * 1024; }
-
-int trunk16_pack_weight(const float* w_packed_dev, int c, int taps, int dtype, void* out_dev, hipStream_t stream) {
-    VQAE_REQUIRE(c % 16 == 0 && (taps == 1 || taps == 9), VQAE_ERR_INVALID, "trunk16_pack_weight: c %d taps %d", c, taps);
-    const int64_t n = (int64_t)(c < 32 ? 32 : c) * c * taps;
-    if (dtype == VQAE_DT_BF16) pack16_kernel<__bf16><<<(unsigned)ceil_div(n, 256), 256, 0, stream>>>(w_packed_dev, c, taps, (__bf16*)out_dev);
-    else pack16_kernel<_Float16><<<(unsigned)ceil_div(n, 256), 256, 0, stream>>>(w_packed_dev, c, taps, (_Float16*)out_dev);
-    VQAE_LAUNCH_CHECK();
-    return VQAE_OK;
-}
 
 // chain-head conv1 (head16_kernel)
 bool trunk16_head_supported(int c, int64_t m, int dtype) {

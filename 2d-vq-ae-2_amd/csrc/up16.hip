@@ -18,38 +18,18 @@
 //   convs    v_mfma_f32_32x32x16_{bf16,f16}, weights (fragment order, from L2) as the row operand: conv2 from U -> t2 (16-bit,
 //            over U) -> conv3 from t2 and skip_conv from S -> epilogue, fp32 store.
 #include "kernels.h"
+#include "mfma.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-using vqae::elu_act;
-using vqae::lds_barrier;
+using namespace vqae;
 
-template <int DT> struct U16;
-template <> struct U16<VQAE_DT_BF16> {
-    using x8 = bf16x8; using x4 = bf16x4;
-    static __device__ __forceinline__ f32x16 mma(const x8& a, const x8& b, const f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ float rnd(float v) { return (float)(__bf16)v; }
-};
-template <> struct U16<VQAE_DT_F16> {
-    using x8 = f16x8; using x4 = f16x4;
-    static __device__ __forceinline__ f32x16 mma(const x8& a, const x8& b, const f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ float rnd(float v) { return (float)(_Float16)v; }
-};
+constexpr int up16_rows(int c) { return c == 128 ? 2 : 4; }   // output rows (of 32 pixels) a workgroup owns
 
 struct Up16K {
     const float* __restrict__ x;         // [B][H][W][C] fp32: the block's input
     const float* __restrict__ t1;        // [B][H][W][C] fp32: ELU(round16(conv1(.)) + b2a) + b2b
-    const void* __restrict__ w2;         // 16-bit fragment order (down16_pack_weight): [C][C]
+    const void* __restrict__ w2;         // 16-bit fragment order (pack16_weight): [C][C]
     const void* __restrict__ w3;         //   [C / 2][C]   (rows padded to 32)
     const void* __restrict__ wsk;        //   [C / 2][C]
     float* __restrict__ y;               // [B][2H][2W][C / 2] fp32
@@ -61,7 +41,7 @@ struct Up16K {
 template <int C, int DT, int ROWS>
 __global__ __launch_bounds__(256, 2)
 void up16_kernel(const Up16K p) {
-    using E = U16<DT>;
+    using E = Mfma16<DT>;
     using x8 = typename E::x8;
     using x4 = typename E::x4;
     constexpr int CO = C / 2;
@@ -259,16 +239,16 @@ int up16_block(const float* x, const float* t1, const void* w2h, const void* w3h
     Up16K k;
     k.x = x; k.t1 = t1; k.w2 = w2h; k.w3 = w3h; k.wsk = wskh; k.y = y;
     k.H = H; k.W = W;
-    const int rows = c == 128 ? 2 : 4;
+    const int rows = up16_rows(c);
     k.tiles_x = 2 * W / 32; k.tiles_y = 2 * H / rows;
     k.b3a = s.b3a; k.b3b = s.b3b; k.scale = s.scale; k.b4 = s.b4; k.b1c = s.b1c; k.b1d = s.b1d;
     const int64_t n_tiles = (int64_t)B * k.tiles_x * k.tiles_y;
     VQAE_REQUIRE(n_tiles < (1ll << 31) && 2 * H % rows == 0, VQAE_ERR_UNSUPPORTED, "up16_block: tiling");
-#define VQAE_U16(C_, R_) (dtype == VQAE_DT_BF16 ? launch_up16<C_, VQAE_DT_BF16, R_>(k, n_tiles, stream) : launch_up16<C_, VQAE_DT_F16, R_>(k, n_tiles, stream))
-    if (c == 16) return VQAE_U16(16, 4);
-    if (c == 32) return VQAE_U16(32, 4);
-    if (c == 64) return VQAE_U16(64, 4);
-    return VQAE_U16(128, 2);
+#define VQAE_U16(C_) (dtype == VQAE_DT_BF16 ? launch_up16<C_, VQAE_DT_BF16, up16_rows(C_)>(k, n_tiles, stream) : launch_up16<C_, VQAE_DT_F16, up16_rows(C_)>(k, n_tiles, stream))
+    if (c == 16) return VQAE_U16(16);
+    if (c == 32) return VQAE_U16(32);
+    if (c == 64) return VQAE_U16(64);
+    return VQAE_U16(128);
 #undef VQAE_U16
 }
 

@@ -23,14 +23,11 @@
 // pairs per group in flight) and two rounds of 64-bit LDS atomic minima (distance bits << 32 | code) leave the best and the
 // second best pair of every row.
 #include "kernels.h"
+#include "mfma.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-using vqae::lds_barrier;
+using namespace vqae;
 
 constexpr int VF_PCAP = 1024;                            // (row, survivor) pairs kept per workgroup tile
 typedef unsigned long long u64;

@@ -22,11 +22,12 @@
 // 16-bit autocast modes (DT): proj_in / proj_out are convolutions, so their operands and results are rounded to the
 // 16-bit type exactly as vqae_conv2d_f32 does (weights / biases arrive pre-rounded); the distance, q and the loss stay fp32.
 #include "kernels.h"
+#include "mfma.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+using namespace vqae;
+
 constexpr int PD = 8;                                    // projection_dim
 
 struct VqProjK {
@@ -46,12 +47,6 @@ struct VqProjK {
     int C, K;
     float thr;
 };
-
-template <int DT> __device__ __forceinline__ float rnd16(float v) {
-    if (DT == VQAE_DT_BF16) return (float)(__bf16)v;
-    if (DT == VQAE_DT_F16) return (float)(_Float16)v;
-    return v;
-}
 
 constexpr int VP_THREADS = 128;
 
@@ -92,7 +87,7 @@ void vq_proj_fused_kernel(const VqProjK p) {
         const f32x4 xv = *reinterpret_cast<const f32x4*>(xr + c);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const float xe = rnd16<DT>(xv[e]);
+            const float xe = round_to<DT>(xv[e]);
             const f32x4 w0 = *reinterpret_cast<const f32x4*>(s_win + (c + e) * PD);         // broadcast reads
             const f32x4 w1 = *reinterpret_cast<const f32x4*>(s_win + (c + e) * PD + 4);
 #pragma unroll
@@ -100,7 +95,7 @@ void vq_proj_fused_kernel(const VqProjK p) {
         }
     }
 #pragma unroll
-    for (int j = 0; j < PD; ++j) z[j] = rnd16<DT>(z[j] + s_bin[j]);
+    for (int j = 0; j < PD; ++j) z[j] = round_to<DT>(z[j] + s_bin[j]);
     if (live) {
         *reinterpret_cast<f32x4*>(p.z + row * PD) = (f32x4){z[0], z[1], z[2], z[3]};
         *reinterpret_cast<f32x4*>(p.z + row * PD + 4) = (f32x4){z[4], z[5], z[6], z[7]};
@@ -151,7 +146,7 @@ void vq_proj_fused_kernel(const VqProjK p) {
 #pragma unroll
         for (int j = 0; j < PD; ++j) {
             const float ev = j < 4 ? e0[j] : e1[j - 4];
-            qr[j] = rnd16<DT>(z[j] + (ev - z[j]));
+            qr[j] = round_to<DT>(z[j] + (ev - z[j]));
         }
     }
     // Output rows: computed 2 rows per wave instruction, lane L -> row 2 i + (L >> 5), channels 4 (L & 31) .. + 3 of a 128-channel
@@ -185,7 +180,7 @@ void vq_proj_fused_kernel(const VqProjK p) {
                 for (int j = 0; j < 4; ++j) a = __builtin_fmaf(qs[j], wv0[e][j], a);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) a = __builtin_fmaf(qs[j + 4], wv1[e][j], a);
-                o[e] = rnd16<DT>(a + bo[e]);
+                o[e] = round_to<DT>(a + bo[e]);
             }
             if (cvalid && row_w0 + src < p.N) *reinterpret_cast<f32x4*>(p.out + (row_w0 + src) * p.C + cl) = o;
         }
@@ -299,14 +294,14 @@ void vq_proj16_kernel(const VqProjK p, const int n_units, const int use_filter) 
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float w = wa[(16 * s_ + e) * 17];
-                const float xe = rnd16<DT>(xv[s_][e]);
+                const float xe = round_to<DT>(xv[s_][e]);
                 if ((s_ & 1) == 0) a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w, xe, a0, 0, 0, 0);
                 else a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w, xe, a1, 0, 0, 0);
             }
         f32x4 zc;
         const f32x4 bi = *reinterpret_cast<const f32x4*>(s_bin + 4 * g);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) zc[i] = rnd16<DT>((a0[i] + a1[i]) + bi[i]);
+        for (int i = 0; i < 4; ++i) zc[i] = round_to<DT>((a0[i] + a1[i]) + bi[i]);
         return zc;
     };
     auto wave_lds_sync = [] { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); };   // a wave's LDS accesses complete in order
@@ -377,7 +372,6 @@ void vq_proj16_kernel(const VqProjK p, const int n_units, const int use_filter) 
             // window w of the best satisfies  S_k - eta A_k <= T + w.  Two passes over the code blocks (an MFMA is 16 cycles; keeping
             // the scores would cost 128 registers).
             constexpr float ETA = 1.02f / 1024.f;
-            typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
             auto absf16 = [](const f16x8& v) -> f16x8 {
                 u32x4 b = __builtin_bit_cast(u32x4, v);
                 b &= 0x7FFF7FFFu;
@@ -508,7 +502,7 @@ void vq_proj16_kernel(const VqProjK p, const int n_units, const int use_filter) 
         const float zl = g == 0 ? z[0] : (g == 1 ? z[1] : (g == 2 ? z[2] : z[3]));
         const float zh = g == 0 ? z[4] : (g == 1 ? z[5] : (g == 2 ? z[6] : z[7]));
         const float el = s_emb[i1 * PD + g], eh = s_emb[i1 * PD + 4 + g];
-        const float ql = rnd16<DT>(zl + (el - zl)), qh = rnd16<DT>(zh + (eh - zh));
+        const float ql = round_to<DT>(zl + (el - zl)), qh = round_to<DT>(zh + (eh - zh));
         float* __restrict__ orow = p.out + row * C + 4 * g;
 #pragma unroll
         for (int b = 0; b < NS; ++b) {
@@ -517,7 +511,7 @@ void vq_proj16_kernel(const VqProjK p, const int n_units, const int use_filter) 
             acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wo_p[16 * b * 9 + 4], qh, acc, 0, 0, 0);
             if (DT != VQAE_DT_F32) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) acc[i] = rnd16<DT>(acc[i]);
+                for (int i = 0; i < 4; ++i) acc[i] = round_to<DT>(acc[i]);
             }
             if (live) *reinterpret_cast<f32x4*>(orow + 16 * b) = acc;
         }
@@ -557,13 +551,13 @@ void vq_proj_patch_kernel(const VqProjK p) {
         for (int j = 0; j < PD; ++j) q[j] = zr[j] + (eb[j] - zr[j]);
         float qr[PD];
 #pragma unroll
-        for (int j = 0; j < PD; ++j) qr[j] = rnd16<DT>(q[j]);
+        for (int j = 0; j < PD; ++j) qr[j] = round_to<DT>(q[j]);
         float* __restrict__ orow = p.out + (int64_t)row * p.C;
         for (int c = 0; c < p.C; ++c) {                                      // divergent lanes: plain vector loads
             float a = 0.f;
 #pragma unroll
             for (int j = 0; j < PD; ++j) a = __builtin_fmaf(qr[j], p.w_out[c * PD + j], a);
-            orow[c] = rnd16<DT>(a + p.b_out[c]);
+            orow[c] = round_to<DT>(a + p.b_out[c]);
         }
     }
 }
