@@ -66,6 +66,14 @@ class Tensor(Structure):
     _fields_ = [("name", c_char_p), ("data", c_void_p), ("numel", c_int64)]
 
 
+OPTIM_KINDS = {"adam": 0, "adamw": 1, "lamb": 2}          # VQAE_OPTIM_*
+
+
+class ClassifierOptimConfig(Structure):
+    _fields_ = [("kind", c_int), ("lr", c_double), ("beta1", c_double), ("beta2", c_double), ("eps", c_double),
+                ("weight_decay", c_double), ("sam_rho", c_double), ("sam_adaptive", c_int)]
+
+
 # name -> (restype, argtypes); every symbol include/vqae_hip.h declares
 SYMBOLS = {
     "vqae_last_error": (c_char_p, []),
@@ -144,6 +152,16 @@ SYMBOLS = {
     "vqae_classifier_train_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
     "vqae_classifier_loss_grad": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_int,
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vqae_classifier_optim_create": (c_int, [c_void_p, POINTER(ClassifierOptimConfig), POINTER(c_void_p)]),
+    "vqae_classifier_optim_destroy": (None, [c_void_p]),
+    "vqae_classifier_optim_set": (c_int, [c_void_p, POINTER(ClassifierOptimConfig)]),
+    "vqae_classifier_optim_step": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "vqae_classifier_optim_sam_first": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "vqae_classifier_download": (c_int, [c_void_p, POINTER(c_void_p), c_void_p]),
+    "vqae_classifier_image_floats": (c_size_t, [c_void_p]),
+    "vqae_classifier_image": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "vqae_classifier_optim_export": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_void_p]),
+    "vqae_classifier_optim_import": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "vqae_code_histogram_workspace_bytes": (c_size_t, [c_int, c_int64, c_int, c_int]),
     "vqae_code_histogram": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                     c_void_p, c_void_p]),

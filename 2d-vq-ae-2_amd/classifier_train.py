@@ -11,7 +11,8 @@ reference's recorded gradients.  `CNNClassifier.train()` and autograd through `C
 `train_hdf5` walks an archive like the reference's datamodule: `embeddings_split` is CAMELYON16EmbeddingsDataset's choice
 and interleaving of the sorted normal* / tumor* / test* slides (datamodules/camelyon16.py:230-246, 287-329),
 `collate_random_crop` its collate_unequal_sized_slides (camelyon16.py:381-413), `smooth_targets` the soft targets of the
-loss's label smoothing (train_helpers.py:133-135).  The SAM and LAMB optimisers of the reference are not provided.
+loss's label smoothing (train_helpers.py:133-135).  The reference's LAMB and SAM optimisers, and the training step that
+keeps gradients, optimiser state and weights on the device (ClassifierTrainer), are in optim.py; train_hdf5 takes either.
 """
 from itertools import chain, zip_longest
 
@@ -203,6 +204,11 @@ def train_hdf5(clf, path, optimizer, *, epochs, batch_size, pos_weight, seed, tr
     seed seeds the crops (numpy RandomState) and the label-smoothing noise (a torch.Generator on the codes' device).
     The batches run on the GPU; grad_fn / forward_fn replace the HIP paths (see loss_and_grads, classify_slide) and keep the
     tensors on the host.
+    optimizer may also be the SAM mirror (optim.SAM): each batch is then loss_and_grads, first_step, loss_and_grads again
+    (with label smoothing on newly drawn targets, as the reference's loss draws new noise on its second call), second_step,
+    and the step's record is the first pass's.  Or a ClassifierTrainer made from `clf` (optim.py): its step runs each batch
+    without the host in between (on the CPU when the trainer was built with device='cpu'), losses and stats are read back
+    once per epoch, and `clf` receives the weights (sync_to_module) before each epoch's validation.
     -> [{'epoch', 'steps': [{'stems', 'shape', loss_and_grads' dict ...}], 'train': pooled scores of the epoch's steps,
          'val': pooled scores of the validation slides}, ...]   (loss = summed loss / summed n_valid, precision, recall)"""
     r = hdf5.H5Reader(path)
@@ -214,7 +220,17 @@ def train_hdf5(clf, path, optimizer, *, epochs, batch_size, pos_weight, seed, tr
     for s in train_stems + val_stems:
         if s + "_mask" not in masks:
             raise KeyError(f"no masks/{s}_mask in {path}")
-    on_gpu = grad_fn is None
+    from .optim import SAM, ClassifierTrainer                       # (optim.py imports this module)
+    trainer = optimizer if isinstance(optimizer, ClassifierTrainer) else None
+    sam = isinstance(optimizer, SAM)
+    if trainer is not None:
+        if trainer.clf is not clf:
+            raise ValueError("train_hdf5: the ClassifierTrainer was made from another classifier")
+        if grad_fn is not None:
+            raise ValueError("train_hdf5: a ClassifierTrainer computes its own gradients; grad_fn does not apply")
+        if trainer.device is None:
+            trainer._ensure("cuda")
+    on_gpu = grad_fn is None if trainer is None else trainer.device == "cuda"
     rng = np.random.RandomState(seed)
     gen = None
     if label_smoothing:
@@ -237,12 +253,34 @@ def train_hdf5(clf, path, optimizer, *, epochs, batch_size, pos_weight, seed, tr
             if on_gpu:
                 codes, mask = codes.cuda(), mask.cuda()
             target = smooth_targets(mask, label_smoothing, gen) if label_smoothing else None
+            if trainer is not None:
+                target2 = smooth_targets(mask, label_smoothing, gen) if label_smoothing and trainer.sam_rho is not None else None
+                steps.append((trainer.step(codes, mask, pos_weight=pos_weight, reduction=reduction, target=target,
+                                           target2=target2), list(stems), tuple(codes.shape)))
+                continue
             optimizer.zero_grad(set_to_none=True)
             res = loss_and_grads(clf, codes, mask, pos_weight=pos_weight, reduction=reduction, target=target, grad_fn=grad_fn)
-            optimizer.step()
+            if sam:
+                optimizer.first_step(zero_grad=True)
+                target = smooth_targets(mask, label_smoothing, gen) if label_smoothing else None
+                loss_and_grads(clf, codes, mask, pos_weight=pos_weight, reduction=reduction, target=target, grad_fn=grad_fn)
+                optimizer.second_step(zero_grad=True)
+            else:
+                optimizer.step()
             steps.append(dict(res, stems=list(stems), shape=tuple(codes.shape)))
             for j, k in enumerate(("tp", "fp", "fn", "tn", "loss_sum")):
                 tot[j] += res[k]
+        if trainer is not None:
+            if steps:                                              # the epoch's one read-back: every step's pooled stats row
+                rows = torch.stack([st.sum(0) for (_, st), _, _ in steps]).cpu().tolist()
+                for n, r in enumerate(rows):
+                    res = _summary(int(r[0]), int(r[1]), int(r[2]), int(r[3]), r[5])
+                    if reduction == "sum":
+                        res["loss"] = res["loss_sum"]
+                    for j, k in enumerate(("tp", "fp", "fn", "tn", "loss_sum")):
+                        tot[j] += res[k]
+                    steps[n] = dict(res, stems=steps[n][1], shape=steps[n][2])
+            trainer.sync_to_module()
         vtot = [0, 0, 0, 0, 0.0]
         for s in val_stems:
             img, msk = _load_slide(images, masks, s)

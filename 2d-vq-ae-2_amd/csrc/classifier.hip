@@ -347,7 +347,9 @@ int vqae_cls::ensure_device(vqae_classifier* c, hipStream_t st) {
     int dev = 0;
     VQAE_HIP_CHECK(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lock(c->mu);
-    if (c->dev && c->dev_id == dev && !c->dev_stale) return VQAE_OK;
+    if (c->dev && c->dev_id == dev && !c->host_newer) return VQAE_OK;
+    VQAE_REQUIRE(!(c->dev_newer && !c->host_newer), VQAE_ERR_INVALID,
+                 "classifier: the weights were stepped on device %d and not downloaded; device %d cannot take them", c->dev_id, dev);
     if (c->dev && c->dev_id != dev) {
         (void)hipFree(c->dev);
         c->dev = nullptr;
@@ -356,7 +358,8 @@ int vqae_cls::ensure_device(vqae_classifier* c, hipStream_t st) {
     c->dev_id = dev;
     VQAE_HIP_CHECK(hipMemcpyAsync(c->dev, c->host.data(), c->host.size() * sizeof(float), hipMemcpyHostToDevice, st));
     VQAE_HIP_CHECK(hipStreamSynchronize(st));     // once per upload: the host image may be pageable
-    c->dev_stale = false;
+    c->host_newer = false;
+    c->dev_newer = false;
     return VQAE_OK;
 }
 
@@ -428,7 +431,66 @@ extern "C" int vqae_classifier_update(vqae_classifier* c, const vqae_tensor* ten
     if (int rc = find_weights("classifier_update", c->K, c->E, c->C, c->NO, tensors, n_tensors, t)) return rc;
     std::lock_guard<std::mutex> lock(c->mu);
     pack_weights(c, t);
-    c->dev_stale = true;              // the next call uploads on its own stream, behind the launches that read the old image
+    c->host_newer = true;             // the next call uploads on its own stream, behind the launches that read the old image
+    c->dev_newer = false;             // ... also over a device image an optimiser stepped: the host weights win
+    return VQAE_OK;
+}
+
+vqae_cls::ParamMap vqae_cls::param_map(const vqae_classifier* c) {
+    const int K = c->K, E = c->E, C = c->C, NO = c->NO;
+    const int numel[7] = {K * E, C * E * 9, C, C * C * 9, C, NO * C * 9, NO};
+    const size_t off[7] = {c->o_table, c->o_w1, c->o_b1, c->o_w2, c->o_b2, c->o_w3, c->o_b3};
+    const int cout[7] = {0, C, 0, C, 0, NO, 0}, cin9[7] = {0, E * 9, 0, C * 9, 0, C * 9, 0};
+    ParamMap m;
+    m.start[0] = 0;
+    for (int i = 0; i < 7; ++i) {
+        m.start[i + 1] = m.start[i] + numel[i];
+        m.off[i] = (int)off[i]; m.cout[i] = cout[i]; m.cin9[i] = cin9[i];
+    }
+    return m;
+}
+
+extern "C" int vqae_classifier_download(vqae_classifier* c, float* const tensors[7], void* stream) {
+    VQAE_REQUIRE(c && tensors, VQAE_ERR_INVALID, "classifier_download: null pointer");
+    for (int i = 0; i < 7; ++i) VQAE_REQUIRE(tensors[i], VQAE_ERR_INVALID, "classifier_download: tensor %d is null", i);
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (c->dev && c->dev_newer && !c->host_newer) {       // the device image is the truth: fetch it, the host copy follows
+        int dev = 0;
+        VQAE_HIP_CHECK(hipGetDevice(&dev));
+        VQAE_REQUIRE(dev == c->dev_id, VQAE_ERR_INVALID, "classifier_download: the weights live on device %d, current is %d",
+                     c->dev_id, dev);
+        hipStream_t st = (hipStream_t)stream;
+        VQAE_HIP_CHECK(hipMemcpyAsync(c->host.data(), c->dev, c->host.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+        VQAE_HIP_CHECK(hipStreamSynchronize(st));
+        c->dev_newer = false;
+    }
+    const ParamMap m = param_map(c);
+    const float* h = c->host.data();
+    for (int i = 0; i < 7; ++i) {
+        const int n = m.start[i + 1] - m.start[i];
+        for (int l = 0; l < n; ++l) {                      // pack_conv's permutation, read backwards
+            const int co = m.cout[i] ? l / m.cin9[i] : 0, r = m.cout[i] ? l - co * m.cin9[i] : 0;
+            tensors[i][l] = h[m.off[i] + (m.cout[i] ? r * m.cout[i] + co : l)];
+        }
+    }
+    return VQAE_OK;
+}
+
+extern "C" size_t vqae_classifier_image_floats(const vqae_classifier* c) { return c ? c->host.size() : 0; }
+
+extern "C" int vqae_classifier_image(vqae_classifier* c, float* image_host, void* stream) {
+    VQAE_REQUIRE(c && image_host, VQAE_ERR_INVALID, "classifier_image: null pointer");
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (c->dev && !c->host_newer) {
+        int dev = 0;
+        VQAE_HIP_CHECK(hipGetDevice(&dev));
+        VQAE_REQUIRE(dev == c->dev_id, VQAE_ERR_INVALID, "classifier_image: the weights live on device %d, current is %d", c->dev_id, dev);
+        hipStream_t st = (hipStream_t)stream;
+        VQAE_HIP_CHECK(hipMemcpyAsync(image_host, c->dev, c->host.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+        VQAE_HIP_CHECK(hipStreamSynchronize(st));
+    } else {
+        std::memcpy(image_host, c->host.data(), c->host.size() * sizeof(float));
+    }
     return VQAE_OK;
 }
 

@@ -1,6 +1,6 @@
-// What classifier.hip (the fused forward) and classifier_train.hip (loss and gradients) share: the tile constants, the
-// device arithmetic both must spell identically (ELU, softplus, code loads, the shuffle sums), the handle and its host
-// helpers.  Private to csrc/.
+// What classifier.hip (the fused forward), classifier_train.hip (loss and gradients) and classifier_optim.hip (the
+// optimiser step on the device image) share: the tile constants, the device arithmetic the first two must spell identically
+// (ELU, softplus, code loads, the shuffle sums), the handle and its host helpers.  Private to csrc/.
 #pragma once
 #include "common.h"
 
@@ -48,22 +48,34 @@ inline bool idx_dtype_ok(int dt) { return dt == VQAE_IDX_I64 || dt == VQAE_IDX_U
 struct vqae_classifier {
     int K = 0, E = 0, C = 0, NO = 0;
     int tw = 0;                       // tile width of the geometry this (E, C) runs on: 62 or 30
-    // one packed host image, uploaded on the first call on a device and after vqae_classifier_update: table [K][E],
-    // w1 [E][9][C], b1 [C], w2 [C][9][C], b2 [C], w3 [C][9][NO], b3 [NO]  (conv weights repacked from PyTorch's
-    // [cout][cin][3][3] to [cin][tap][cout])
+    // one packed image, on the host and on the device: table [K][E], w1 [E][9][C], b1 [C], w2 [C][9][C], b2 [C],
+    // w3 [C][9][NO], b3 [NO]  (conv weights repacked from PyTorch's [cout][cin][3][3] to [cin][tap][cout]; every block
+    // starts on a multiple of 16 floats and the padding is 0).  Either copy can be the newer one, never both:
+    //   host_newer  vqae_classifier_create / _update wrote the host image; ensure_device uploads it before the next launch;
+    //   dev_newer   a vqae_classifier_optim step rewrote the device image in place; ensure_device must NOT upload, and the
+    //               host image is brought up to date only by vqae_classifier_download.
+    // vqae_classifier_update sets host_newer and clears dev_newer (the host weights win); a step uploads a pending host
+    // image first, then sets dev_newer.
     std::vector<float> host;
     size_t o_table = 0, o_w1 = 0, o_b1 = 0, o_w2 = 0, o_b2 = 0, o_w3 = 0, o_b3 = 0;
     float* dev = nullptr;
     int dev_id = -1;
-    bool dev_stale = false;           // the host image changed after the upload
+    bool host_newer = false;          // the host image changed after the upload
+    bool dev_newer = false;           // an optimiser step changed the device image after the upload
     std::mutex mu;
 };
 
 namespace vqae_cls {
 
 int64_t tile_count(const vqae_classifier* c, int h, int w, int* tiles_x);
-// the device image of the weights on the current device, uploaded (again) on `st` where it is missing or stale
+// the device image of the weights on the current device, uploaded (again) on `st` where it is missing or the host image is
+// the newer one; never uploaded over a device image that holds optimiser steps (VQAE_ERR_INVALID where those steps were made
+// on another device: download them there first)
 int ensure_device(vqae_classifier* c, hipStream_t st);
+// PyTorch parameter order: the dense start of tensor i in the packed gradient (start[7] = the total), its offset in the
+// image, and for the conv weights cout and cin * 9 (cout = 0 for the table and the biases, which are stored as they are)
+struct ParamMap { int start[8]; int off[7]; int cout[7]; int cin9[7]; };
+ParamMap param_map(const vqae_classifier* c);
 // The forward launch (and, with stats_dev, its stats reduction) after validation, batch >= 1.  target_dev (fp32 [B][h][w],
 // optional) replaces the hard target mask - 1 in the loss sum; grad_logit_dev (fp32 [B][h][w], optional; needs the mask)
 // receives dL/dlogit of the summed loss: sigmoid(x) * (1 - t + pos_weight * t) - pos_weight * t where mask != 0, 0 elsewhere.

@@ -476,6 +476,10 @@ int vqae_classifier_forward(vqae_classifier* c, const void* codes_dev, int idx_d
 /* Replaces the weights of an existing classifier: the same names, shapes and checks as vqae_classifier_create (dimensions are
  * those the handle was created with).  The host copy changes at once; the device copy is refreshed by the next call that
  * uses the handle, on that call's stream.  No HIP call is made here, so an optimiser step does not rebuild the handle.
+ * The handle keeps the weights twice, a host image and a device image, and either can be the newer one: after this call (and
+ * after create) it is the host image, which the next forward / loss_grad / optimiser step uploads first; after a
+ * vqae_classifier_optim step it is the device image, which no later call overwrites with the older host copy.  An update
+ * after such a step wins: the stepped weights are dropped, the optimiser's moments and step count stay.
  * Errors: null pointers, a tensor of another size -> VQAE_ERR_INVALID; a missing tensor -> VQAE_ERR_NOT_FOUND. */
 int vqae_classifier_update(vqae_classifier* c, const vqae_tensor* tensors, int n_tensors);
 /* Length of the packed gradient vector of vqae_classifier_loss_grad (0 for a null handle): the seven tensors, dense, in
@@ -508,6 +512,69 @@ size_t vqae_classifier_train_workspace_bytes(const vqae_classifier* c, int batch
 int vqae_classifier_loss_grad(vqae_classifier* c, const void* codes_dev, int idx_dtype, int batch, int h, int w,
                               const uint8_t* mask_dev, const float* target_dev, float pos_weight, int reduction,
                               double* grads_dev, double* stats_dev, double* loss_dev, void* workspace_dev, void* stream);
+
+/* ---- Optimiser: replaces the optimizer.step() Lightning runs after CNNClassifier.step's backward with the three optimisers
+ * of conf/model/optim/ -- torch.optim.Adam / AdamW (adam.yaml, adamw.yaml), vq_ae/optim/lamb.py (lamb.yaml) and, around
+ * either, vq_ae/optim/sam.py (sam.yaml; CNNClassifier.sam_step_and_update, validation_nn/model.py:115-129) -- on the handle's
+ * own device weights.  The step reads the packed gradient vqae_classifier_loss_grad left in HBM and rewrites the packed
+ * weight image the forward and backward kernels read: no tensor crosses PCIe and nothing blocks between two steps. ---- */
+enum { VQAE_OPTIM_ADAM = 0, VQAE_OPTIM_ADAMW = 1, VQAE_OPTIM_LAMB = 2 };
+typedef struct vqae_classifier_optim_config {
+    int kind;                 /* VQAE_OPTIM_*; amsgrad / maximize are not provided */
+    double lr, beta1, beta2, eps, weight_decay;
+    double sam_rho;           /* < 0: no SAM; otherwise sam.py's rho */
+    int sam_adaptive;         /* sam.py's adaptive */
+} vqae_classifier_optim_config;
+typedef struct vqae_classifier_optim vqae_classifier_optim;
+
+/* An optimiser over the seven tensors of `c` (which must outlive it), with exp_avg = exp_avg_sq = 0 and step = 0
+ * (lamb.py:69-76; torch.optim.Adam's lazy state).  Uploads c's weights to the current device, where the state is allocated;
+ * every later call must run on that device.
+ * Errors, before any HIP call: null pointers, an unknown kind, lr < 0, eps < 0, a beta outside [0, 1), weight_decay < 0 (the
+ * ValueErrors of lamb.py:34-41 and torch.optim.Adam), a nan sam_rho -> VQAE_ERR_INVALID; n_out != 1 -> VQAE_ERR_UNSUPPORTED. */
+int vqae_classifier_optim_create(vqae_classifier* c, const vqae_classifier_optim_config* cfg, vqae_classifier_optim** out);
+void vqae_classifier_optim_destroy(vqae_classifier_optim* opt);
+/* New hyper-parameters from the next step on (param_groups[0]['lr'] = ... of an lr schedule).  The same checks as create; the
+ * kind, and whether SAM is on, cannot change -> VQAE_ERR_INVALID.  No HIP call. */
+int vqae_classifier_optim_set(vqae_classifier_optim* opt, const vqae_classifier_optim_config* cfg);
+/* One optimizer.step() with grads_dev = double [vqae_classifier_grad_floats(c)], exactly vqae_classifier_loss_grad's output,
+ * stream-ordered behind it.  Each gradient is rounded to fp32 once (as `.grad` of an fp32 parameter holds it); moments and
+ * weights are fp32; bias corrections and scalar factors are formed in double on the host; step counts from 1.
+ *   AdamW (torch.optim.adam._single_tensor_adam): p *= 1 - lr * wd (wd != 0);  m += (g - m) * (1 - b1);
+ *          v = b2 * v + (1 - b2) * g * g;  p += (-lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
+ *   Adam:  the same with g += wd * p in place of the decay
+ *   LAMB (lamb.py:78-114): m = b1 * m + (1 - b1) * g;  v likewise;  u = (m / bc1) / (sqrt(v / bc2) + eps) + wd * p;
+ *          per tensor r = ||p|| / ||u|| where both are > 0, else 1;  p -= lr * r * u.  The embedding table is one tensor.
+ * After vqae_classifier_optim_sam_first this is SAM.second_step (sam.py:49-60): the weights saved there come back first.
+ * Norms are fixed-order fp64 sums of fp32 squares (no atomics): weights and moments are bit-identical between two runs on the
+ * same inputs.  Up to 4096 parameters the step is one launch of one workgroup, beyond that two launches (one for Adam /
+ * AdamW at any size).  No host synchronisation, no copy and no allocation; a pending vqae_classifier_update is uploaded
+ * first (that one upload synchronises).  A non-finite gradient is not an error: it propagates as in torch.
+ * Errors: null pointers -> VQAE_ERR_INVALID, before any HIP call; another device than create's -> VQAE_ERR_INVALID. */
+int vqae_classifier_optim_step(vqae_classifier_optim* opt, const double* grads_dev, void* stream);
+/* SAM.first_step (sam.py:31-46) with _grad_norm (sam.py:96-111): n = sqrt(sum over all seven tensors of (a * g)^2), a = |p|
+ * if sam_adaptive else 1; the weights are saved and p += (p * p if sam_adaptive else 1) * g * rho / (n + 1e-12).  The caller
+ * then evaluates vqae_classifier_loss_grad at the climbed weights and hands those gradients to vqae_classifier_optim_step.
+ * Errors, before any HIP call: null pointers, an optimiser created with sam_rho < 0, a second first step without a step in
+ * between -> VQAE_ERR_INVALID. */
+int vqae_classifier_optim_sam_first(vqae_classifier_optim* opt, const double* grads_dev, void* stream);
+/* The current weights as the seven PyTorch-shaped fp32 host tensors, in parameter order (the order and shapes of
+ * vqae_classifier_grad_floats): the inverse of create's repacking.  Where an optimiser stepped the device image it is
+ * fetched on `stream` (one synchronising copy) and becomes the host image too; otherwise no HIP call is made.
+ * Errors: null pointers -> VQAE_ERR_INVALID. */
+int vqae_classifier_download(vqae_classifier* c, float* const tensors[7], void* stream);
+/* The packed weight image as the kernels read it, for checks of the layout: vqae_classifier_image_floats(c) floats (0 for a
+ * null handle) -- table [K][E], in_conv [E][9][C], its bias, hidden_conv1 [C][9][C], its bias, out_conv [C][9][n_out], its
+ * bias, each block padded with zeros to a multiple of 16 floats.  The device copy where one exists (one synchronising copy on
+ * `stream`), the host copy otherwise; nothing else changes.  Errors: null pointers -> VQAE_ERR_INVALID. */
+size_t vqae_classifier_image_floats(const vqae_classifier* c);
+int vqae_classifier_image(vqae_classifier* c, float* image_host, void* stream);
+/* state[p]['exp_avg'], ['exp_avg_sq'] and ['step'] of torch.optim's state_dict: two host arrays of
+ * vqae_classifier_grad_floats(c) floats, the seven tensors dense in parameter order, and the one step count.  Both
+ * synchronise `stream`.  Import with a SAM first step pending, step < 0, null pointers -> VQAE_ERR_INVALID. */
+int vqae_classifier_optim_export(vqae_classifier_optim* opt, float* exp_avg, float* exp_avg_sq, int64_t* step, void* stream);
+int vqae_classifier_optim_import(vqae_classifier_optim* opt, const float* exp_avg, const float* exp_avg_sq, int64_t step,
+                                 void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * 7. Counts of stored code grids -- produces what the reference commits as data under scripts/create_wsi_histograms/
