@@ -14,8 +14,8 @@ the loss weights read off them), dist.py (one-process-per-GPU sharding over RCCL
 """
 from . import _lib, classifier, classifier_train, code_stats, ops, optim, reconstruct, spec  # noqa: F401
 from .classifier import CNNClassifier, classify_hdf5, classify_slide  # noqa: F401
-from .classifier_train import (collate_random_crop, embeddings_split, loss_and_grads, smooth_targets,  # noqa: F401
-                               train_hdf5)
+from .classifier_train import (ce_loss_and_grads, collate_random_crop, embeddings_split, loss_and_grads,  # noqa: F401
+                               smooth_targets, train_hdf5)
 from .code_stats import (class_weights, code_histogram, histogram_hdf5, label_histogram_hdf5, perplexity,  # noqa: F401
                          pos_weight_hdf5)
 from .native import NativeVQAE  # noqa: F401

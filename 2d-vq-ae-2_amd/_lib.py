@@ -26,6 +26,8 @@ MAX_PIXEL_LEVEL = 6                     # VQAE_MAX_PIXEL_LEVEL: overview levels 
 METRIC_NAMES = ("mse", "huber", "psnr", "ssim", "pred_min", "pred_max", "target_min", "target_max")
 # VQAE_CLS_*: columns of the vqae_classifier_forward stats rows
 CLS_STATS_NAMES = ("tp", "fp", "fn", "tn", "n_valid", "loss_sum")
+# VQAE_CE_*: a cross-entropy stats row is 16 confusion counts at [label * 4 + prediction], then these four columns
+CE_STATS_K, CE_WEIGHT_SUM, CE_NLL_SUM, CE_SMOOTH_SUM, CE_N_BAD = 20, 16, 17, 18, 19
 DTYPES = {"f32": DT_F32, "fp32": DT_F32, "float32": DT_F32, "bf16": DT_BF16, "bfloat16": DT_BF16,
           "f16": DT_F16, "fp16": DT_F16, "float16": DT_F16, "half": DT_F16}
 
@@ -162,6 +164,13 @@ SYMBOLS = {
     "vqae_classifier_image": (c_int, [c_void_p, c_void_p, c_void_p]),
     "vqae_classifier_optim_export": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_void_p]),
     "vqae_classifier_optim_import": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "vqae_classifier_ce_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "vqae_classifier_forward_ce": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           POINTER(c_float), c_float, c_void_p, c_void_p, c_void_p]),
+    "vqae_classifier_ce_train_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "vqae_classifier_loss_grad_ce": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, POINTER(c_float), c_float,
+                                             c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vqae_classifier_optim_create_ce": (c_int, [c_void_p, POINTER(ClassifierOptimConfig), POINTER(c_void_p)]),
     "vqae_code_histogram_workspace_bytes": (c_size_t, [c_int, c_int64, c_int, c_int]),
     "vqae_code_histogram": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                     c_void_p, c_void_p]),

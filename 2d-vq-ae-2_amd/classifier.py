@@ -76,6 +76,16 @@ class NativeClassifier:
         """codes [B,H,W] in HBM -> (logits | None, heat | None, stats | None), see ops.classifier_forward"""
         return ops.classifier_forward(self._h, codes, self.n_out, logits=logits, heat=heat, mask=mask, pos_weight=pos_weight)
 
+    def forward_ce(self, codes, logits=False, prob=False, cls=True, labels=None, weight=None, label_smoothing=0.0):
+        """codes [B,H,W] in HBM -> (logits | None, prob | None, class | None, stats [B,20] | None), see ops.classifier_forward_ce"""
+        return ops.classifier_forward_ce(self._h, codes, self.n_out, logits=logits, prob=prob, cls=cls, labels=labels,
+                                         weight=weight, label_smoothing=label_smoothing)
+
+    def loss_grad_ce(self, codes, labels, weight=None, label_smoothing=0.0, reduction="mean"):
+        """codes, labels [B,H,W] in HBM -> (loss [1], packed grads, stats [B,20]) in fp64, see ops.classifier_loss_grad_ce"""
+        return ops.classifier_loss_grad_ce(self._h, codes, labels, self.n_out, weight=weight, label_smoothing=label_smoothing,
+                                           reduction=reduction)
+
     def close(self):
         if getattr(self, "_h", None):
             L.lib().vqae_classifier_destroy(self._h)
@@ -294,6 +304,118 @@ def _score_host(logit, mask, pos_weight):
     return heat, (int((pr & t).sum()), int((pr & ~t).sum()), int((~pr & t).sum()), int((~pr & ~t).sum()), float(loss))
 
 
+# ---- multi-class scoring: nn.CrossEntropyLoss and the confusion matrix ---------------------------------------------------
+def ce_arguments(n_out, class_weight, label_smoothing):
+    """(class_weight as a list of n_out floats or None, label_smoothing as a float), checked as nn.CrossEntropyLoss and the
+    library check them.  ValueError: n_out == 1, a weight vector of another length, a negative or non-finite weight,
+    label_smoothing outside [0, 1]."""
+    if not 2 <= n_out <= 4:
+        raise ValueError(f"the cross-entropy loss is defined for n_out = 2 .. 4, this classifier has {n_out}")
+    w = None
+    if class_weight is not None:
+        w = [float(v) for v in (class_weight.tolist() if hasattr(class_weight, "tolist") else class_weight)]
+        if len(w) != n_out:
+            raise ValueError(f"class_weight has {len(w)} entries, the classifier {n_out} outputs")
+        if not all(np.isfinite(v) and v >= 0 for v in w):
+            raise ValueError(f"class weights must be finite and >= 0, got {w}")
+    eps = float(label_smoothing)
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError(f"label_smoothing must lie in [0, 1], got {label_smoothing}")
+    return w, eps
+
+
+def apply_background_hack(confusion):
+    """`out[:, 0][labels == 0] = inf` (validation_nn/model.py:103) on raw counts [label, prediction]: every position labelled
+    0 is predicted 0, so row 0 collapses into column 0.  -> a new int64 array"""
+    c = np.array(confusion, dtype=np.int64)
+    c[0, 0] = c[0].sum()
+    c[0, 1:] = 0
+    return c
+
+
+def ce_summary(confusion, weight_sum, nll_sum, smooth_sum, n_bad, label_smoothing, hack=True):
+    """Scores from raw counts [n_out, n_out] at [label, prediction] and the loss sums of a VQAE_CE_* stats row (or of several
+    rows added up): 'confusion' (after apply_background_hack when hack), per-class 'precision' = diag / column sum and 'recall' =
+    diag / row sum (nan on an empty denominator), 'loss_sum' = (1 - eps) * nll + (eps / n_out) * smooth, 'weight_sum',
+    'loss' = loss_sum / weight_sum (nan for a zero weight sum) and 'n_bad' (labels >= n_out, counted nowhere else)."""
+    c = apply_background_hack(confusion) if hack else np.array(confusion, dtype=np.int64)
+    no = c.shape[0]
+    nan = float("nan")
+    col, row = c.sum(0), c.sum(1)
+    loss_sum = (1.0 - label_smoothing) * float(nll_sum) + (label_smoothing / no) * float(smooth_sum)
+    return {"confusion": c, "precision": [int(c[k, k]) / int(col[k]) if col[k] else nan for k in range(no)],
+            "recall": [int(c[k, k]) / int(row[k]) if row[k] else nan for k in range(no)],
+            "loss_sum": loss_sum, "weight_sum": float(weight_sum), "loss": loss_sum / float(weight_sum) if weight_sum else nan,
+            "n_bad": int(n_bad)}
+
+
+def ce_pooled(confusion, weight_sum, loss_sum, n_bad):
+    """ce_summary's dict for scores that are already summaries -- counts after the hack, loss sums already mixed -- added up
+    over slides or steps: loss = summed loss / summed weight."""
+    return ce_summary(confusion, weight_sum, loss_sum, 0.0, n_bad, 0.0, hack=False)
+
+
+def ce_stats_rows(stats, n_out):
+    """VQAE_CE_* rows (tensor or array [B, 20]) summed over the batch -> (confusion [n_out, n_out], weight_sum, nll_sum,
+    smooth_sum, n_bad)"""
+    r = np.asarray(stats.detach().cpu().numpy() if isinstance(stats, torch.Tensor) else stats, dtype=np.float64).reshape(-1, L.CE_STATS_K)
+    conf = np.rint(r[:, :16]).astype(np.int64).sum(0).reshape(4, 4)[:n_out, :n_out]
+    return conf, float(r[:, L.CE_WEIGHT_SUM].sum()), float(r[:, L.CE_NLL_SUM].sum()), float(r[:, L.CE_SMOOTH_SUM].sum()), \
+        int(np.rint(r[:, L.CE_N_BAD]).sum())
+
+
+def ce_stats_host(logits, labels, weight, n_out):
+    """The same five numbers from logits [B,n_out,H,W] and labels [B,H,W] with torch, in fp64, on the tensors' device."""
+    x = logits.double()
+    lp = F.log_softmax(x, dim=1)
+    pred = x.argmax(dim=1)
+    lab = labels.long()
+    ok = lab < n_out
+    w = torch.ones(n_out, dtype=torch.float64, device=x.device) if weight is None else \
+        torch.as_tensor(weight, dtype=torch.float64, device=x.device)
+    conf = torch.bincount(lab[ok] * n_out + pred[ok], minlength=n_out * n_out).reshape(n_out, n_out).cpu().numpy().astype(np.int64)
+    lpo = lp.movedim(1, -1)[ok]                                    # [n, n_out]
+    y = lab[ok]
+    wy = w[y]
+    nll = -(wy * lpo.gather(1, y[:, None])[:, 0]).sum()
+    smooth = -(lpo * w).sum()
+    return conf, float(wy.sum()), float(nll), float(smooth), int((~ok).sum())
+
+
+def _classify_slide_ce(clf, g, m, logits, prob, class_weight, label_smoothing, hack, forward_fn):
+    no = clf.n_out
+    w, eps = ce_arguments(no, class_weight, label_smoothing)
+    if m is not None and m.numel() and int(m.max()) >= no:
+        raise ValueError(f"labels are class indices 0 .. {no - 1}, got {int(m.max())}")
+    out = {}
+    if forward_fn is not None:
+        _check_codes(g, clf.num_embeddings)
+        lg = forward_fn(g[None, None])
+        if tuple(lg.shape) != (1, no) + tuple(g.shape):
+            raise ValueError(f"forward_fn returned {tuple(lg.shape)}")
+        lg = lg.cpu()
+        if logits:
+            out["logits"] = lg[0].float().numpy()
+        out["class"] = lg[0].double().argmax(0).to(torch.uint8).numpy()
+        if prob:
+            out["prob"] = torch.round(255.0 * torch.softmax(lg[0].double(), 0)).to(torch.uint8).numpy()
+        if m is not None:
+            out.update(ce_summary(*ce_stats_host(lg, m[None], w, no), eps, hack))
+        return out
+    g = g.to("cuda")                                               # raises without a GPU: there is no CPU fallback
+    _check_codes(g, clf.num_embeddings)
+    lg, pr, cl, st = clf.native().forward_ce(g[None], logits=logits, prob=prob, cls=True,
+                                             labels=m.to("cuda")[None] if m is not None else None, weight=w, label_smoothing=eps)
+    if logits:
+        out["logits"] = lg[0].cpu().numpy()
+    if prob:
+        out["prob"] = pr[0].cpu().numpy()
+    out["class"] = cl[0].cpu().numpy()
+    if st is not None:
+        out.update(ce_summary(*ce_stats_rows(st, no), eps, hack))
+    return out
+
+
 def _grid_tensor(a, what):
     if isinstance(a, torch.Tensor):
         t = a
@@ -312,7 +434,8 @@ def _grid_tensor(a, what):
 
 
 @torch.no_grad()
-def classify_slide(clf, grid, mask=None, *, heat=True, logits=False, pos_weight=1.0, forward_fn=None):
+def classify_slide(clf, grid, mask=None, *, heat=True, logits=False, pos_weight=1.0, forward_fn=None, loss="bce",
+                   class_weight=None, label_smoothing=0.0, background_hack=True, prob=False):
     """One stored code grid [H,W] (array as stored, or a tensor) -> dict of host arrays and scores:
       'heat'   uint8 [H,W] = rint(255 * sigmoid(logit)), the tumour probability per code (n_out == 1), when heat=True;
       'logits' fp32 [n_out,H,W], when logits=True;
@@ -323,13 +446,28 @@ def classify_slide(clf, grid, mask=None, *, heat=True, logits=False, pos_weight=
     The grid goes to the GPU once and one fused launch produces everything asked for.  forward_fn(codes [1,1,H,W]) ->
     logits [1,n_out,H,W] replaces the HIP path (CPU tests of the host logic, like run_eval's encode_fn): heat and scores
     are then formed from its logits on the host in fp64.
-    IndexError: a code outside the embedding table.  ValueError: shapes that do not match, labels outside 0 .. 2."""
+    loss='ce' (n_out = 2 .. 4) scores with nn.CrossEntropyLoss(weight=class_weight, label_smoothing) instead, the mask
+    bytes being the class indices (conf/model/loss_f/cross_entropy.yaml): 'class' uint8 [H,W] = argmax over the classes
+    (always), 'prob' uint8 [n_out,H,W] = rint(255 * softmax) with prob=True, 'logits' as above, and with `mask` the scores
+    of ce_summary: the n_out x n_out 'confusion' at [label, prediction], per-class 'precision' and 'recall', 'loss_sum',
+    'weight_sum', 'loss' (the 'mean' reduction) and 'n_bad'.  background_hack (default on) applies the
+    `out[:, 0][labels == 0] = inf` of validation_nn/model.py:103 to the counts; heat and pos_weight are not used.
+    IndexError: a code outside the embedding table.  ValueError: shapes that do not match, labels outside 0 .. 2 (loss='ce':
+    a label >= n_out), an unknown loss, loss='ce' with n_out == 1."""
+    if loss not in ("bce", "ce"):
+        raise ValueError(f"loss must be 'bce' or 'ce', got {loss!r}")
     g = _grid_tensor(grid, "code grid")
     m = None
     if mask is not None:
         m = _grid_tensor(mask, "mask")
         if tuple(m.shape) != tuple(g.shape):
             raise ValueError(f"mask {tuple(m.shape)} does not match the code grid {tuple(g.shape)}")
+    if loss == "ce":
+        if m is not None and m.numel() and (int(m.min()) < 0 or int(m.max()) > 255):
+            raise ValueError("labels are class indices stored as bytes")
+        return _classify_slide_ce(clf, g, None if m is None else m.to(torch.uint8), logits, prob, class_weight, label_smoothing,
+                                  background_hack, forward_fn)
+    if m is not None:
         if m.numel() and (int(m.min()) < 0 or int(m.max()) > 2):
             raise ValueError("Camelyon16 labels are 0 (background), 1 (tissue) and 2 (cancer)")
         m = m.to(torch.uint8)
@@ -366,13 +504,22 @@ def classify_slide(clf, grid, mask=None, *, heat=True, logits=False, pos_weight=
     return out
 
 
-def classify_hdf5(clf, path, out_path=None, *, names=None, forward_fn=None, pos_weight=1.0):
+def classify_hdf5(clf, path, out_path=None, *, names=None, forward_fn=None, pos_weight=1.0, loss="bce", class_weight=None,
+                  label_smoothing=0.0, background_hack=True):
     """Every slide of an archive written by save_encodings_hdf5 / convert_npy_to_hdf5: `images/<stem>` with
     `masks/<stem>_mask` where present, in sorted key order (the order of the reference's dataset,
     datamodules/camelyon16.py:226-235).  names: the stems to take (default: all).  out_path: an HDF5 file that receives the
     uint8 probability maps as `predictions/<stem>`.
     -> {'slides': {stem: classify_slide's scores, {} for a slide without a mask}, 'pooled': the scores of the summed counts
-    (loss = summed loss / summed n_valid), 'out_path': out_path or None}"""
+    (loss = summed loss / summed n_valid), 'out_path': out_path or None}
+    loss='ce': `predictions/<stem>` receives the uint8 class map, the slides' scores are classify_slide(loss='ce')'s and
+    'pooled' is ce_summary of the summed counts and sums (loss = summed loss / summed weight)."""
+    if loss not in ("bce", "ce"):
+        raise ValueError(f"loss must be 'bce' or 'ce', got {loss!r}")
+    ce = loss == "ce"
+    if ce:
+        _, eps = ce_arguments(clf.n_out, class_weight, label_smoothing)
+        pool = [np.zeros((clf.n_out, clf.n_out), np.int64), 0.0, 0.0, 0]      # raw-equivalent counts, weight, loss, n_bad
     r = hdf5.H5Reader(path)
     images = r["images"]
     masks = r["masks"] if "masks" in r.keys() else None
@@ -389,6 +536,19 @@ def classify_hdf5(clf, path, out_path=None, *, names=None, forward_fn=None, pos_
         for stem in stems:
             mname = stem + "_mask"
             mask = masks[mname] if masks is not None and mname in masks else None
+            if ce:
+                res = classify_slide(clf, images[stem], mask, forward_fn=forward_fn, loss="ce", class_weight=class_weight,
+                                     label_smoothing=label_smoothing, background_hack=background_hack)
+                if writer is not None:
+                    writer.create_dataset("predictions", stem, res["class"])
+                res.pop("class")
+                slides[stem] = res
+                if res:
+                    pool[0] += res["confusion"]
+                    pool[1] += res["weight_sum"]
+                    pool[2] += res["loss_sum"]
+                    pool[3] += res["n_bad"]
+                continue
             res = classify_slide(clf, images[stem], mask, heat=True, pos_weight=pos_weight, forward_fn=forward_fn)
             if writer is not None:
                 writer.create_dataset("predictions", stem, res["heat"])
@@ -401,4 +561,6 @@ def classify_hdf5(clf, path, out_path=None, *, names=None, forward_fn=None, pos_
     finally:
         if writer is not None:
             writer.close()
+    if ce:
+        return {"slides": slides, "pooled": ce_pooled(*pool), "out_path": str(out_path) if out_path is not None else None}
     return {"slides": slides, "pooled": _summary(*tot), "out_path": str(out_path) if out_path is not None else None}

@@ -21,7 +21,8 @@ import torch
 import torch.nn.functional as F
 
 from . import hdf5, ops
-from .classifier import _as_codes, _check_codes, _summary, classify_slide
+from .classifier import (_as_codes, _check_codes, _summary, ce_arguments, ce_pooled, ce_stats_host, ce_stats_rows, ce_summary,
+                         classify_slide)
 
 PARAM_NAMES = ("embedding.weight", "in_conv.weight", "in_conv.bias", "hidden_conv1.weight", "hidden_conv1.bias",
                "out_conv.weight", "out_conv.bias")
@@ -131,6 +132,96 @@ def loss_and_grads(clf, codes, mask, *, pos_weight=1.0, reduction="sum", target=
     return out
 
 
+# ---- multi-class: nn.CrossEntropyLoss ------------------------------------------------------------------------------------
+def torch_ce_loss_grad(clf, codes, labels, class_weight=None, label_smoothing=0.0, reduction="mean"):
+    """The torch restatement on the codes' device: the layers of `clf` under autograd and F.cross_entropy(logits [B,NO,H,W],
+    labels [B,H,W], weight, label_smoothing, reduction) in the parameters' dtype, as CNNClassifier.step applies
+    nn.CrossEntropyLoss (validation_nn/model.py:131-139).
+    -> ([7 gradients in PARAM_NAMES order], (confusion [NO,NO] raw counts at [label, prediction], weight_sum, nll_sum,
+        smooth_sum, n_bad), loss float)"""
+    params = _params(clf)
+    dtype = params[0].dtype
+    no = clf.n_out
+    w = None if class_weight is None else torch.as_tensor(class_weight, dtype=dtype, device=codes.device)
+    with torch.enable_grad():
+        x = clf.reference_forward(codes)
+        loss = F.cross_entropy(x, labels.long(), weight=w, label_smoothing=float(label_smoothing), reduction=reduction)
+        grads = torch.autograd.grad(loss, params, allow_unused=True) if labels.numel() else [None] * 7
+    grads = [torch.zeros_like(p) if g is None else g for g, p in zip(grads, params)]
+    return grads, ce_stats_host(x.detach(), labels, class_weight, no), float(loss.detach().double())
+
+
+def _device_ce_loss_grad(clf, codes, labels, class_weight, label_smoothing, reduction):
+    """The fused HIP path: packed fp64 gradients split into the seven shapes."""
+    loss, packed, stats = clf.native().loss_grad_ce(codes, labels, weight=class_weight, label_smoothing=label_smoothing,
+                                                    reduction=reduction)
+    grads, o = [], 0
+    for p in _params(clf):
+        grads.append(packed[o:o + p.numel()].view(p.shape))
+        o += p.numel()
+    assert o == packed.numel(), (o, packed.numel())
+    return grads, ce_stats_rows(stats, clf.n_out), float(loss)
+
+
+def _as_labels(labels, codes):
+    if labels.dim() == 4 and labels.shape[1] == 1:
+        labels = labels[:, 0]
+    elif labels.dim() == 2:
+        labels = labels[None]
+    if tuple(labels.shape) != tuple(codes.shape):
+        raise ValueError(f"labels {tuple(labels.shape)} do not match the codes {tuple(codes.shape)}")
+    if labels.dtype.is_floating_point:
+        raise TypeError(f"the labels are integer class indices, got {labels.dtype}")
+    return labels
+
+
+def ce_weight_sum(labels, class_weight, n_out):
+    """sum of w[y] over the batch (the 'mean' reduction's divisor), on the host"""
+    cnt = torch.bincount(labels.reshape(-1).long(), minlength=n_out)[:n_out].double().cpu()
+    return float(cnt.sum()) if class_weight is None else float((cnt * torch.as_tensor(class_weight, dtype=torch.float64)).sum())
+
+
+@torch.no_grad()
+def ce_loss_and_grads(clf, codes, labels, *, class_weight=None, label_smoothing=0.0, reduction="mean", accumulate=False,
+                      grad_fn=None, background_hack=True):
+    """loss_and_grads for a classifier with n_out = 2 .. 4 and nn.CrossEntropyLoss(weight=class_weight, label_smoothing,
+    reduction) (conf/model/loss_f/cross_entropy.yaml): `labels` (the codes' grid, integers) are the stored mask bytes used as
+    class indices, and there is no ignore_index -- a position labelled 0 with class_weight[0] == 0 still contributes through
+    the smoothing term, as in torch.  Per position with label y and p = softmax(logits):
+
+      loss_sum = (1 - eps) * sum w[y] * -log p_y + (eps / n_out) * sum_c w[c] * -log p_c;  'mean' divides by sum w[y].
+
+    Writes `.grad` as loss_and_grads does (accumulate=True adds).  On tensors in HBM this is the fused HIP path
+    (vqae_classifier_loss_grad_ce), on CPU tensors the torch restatement (torch_ce_loss_grad); grad_fn(clf, codes, labels,
+    class_weight, label_smoothing, reduction) -> torch_ce_loss_grad's triple replaces either.
+    -> {'loss', 'weight_sum', 'confusion', 'precision', 'recall', 'n_bad'} and 'loss_sum': ce_summary's scores, 'loss' being
+       the reduction's; background_hack as in classify_slide.
+    ValueError: n_out == 1, shapes that do not match, a label >= n_out, a bad class_weight or label_smoothing, reduction=
+    'mean' over a zero weight sum.  IndexError: a code outside the embedding table."""
+    w, eps = ce_arguments(clf.n_out, class_weight, label_smoothing)
+    if reduction not in ("sum", "mean"):
+        raise ValueError(f"reduction must be 'sum' or 'mean', got {reduction!r}")
+    codes = _as_codes(codes)
+    labels = _as_labels(labels, codes)
+    if labels.numel() and (int(labels.min()) < 0 or int(labels.max()) >= clf.n_out):
+        raise ValueError(f"labels are class indices 0 .. {clf.n_out - 1}")
+    labels = labels.to(device=codes.device, dtype=torch.uint8)
+    _check_codes(codes, clf.num_embeddings)
+    if reduction == "mean" and not ce_weight_sum(labels, w, clf.n_out) > 0:
+        raise ValueError("reduction='mean' over a batch whose class weights sum to zero")
+    fn_ = grad_fn if grad_fn is not None else (_device_ce_loss_grad if codes.is_cuda else torch_ce_loss_grad)
+    grads, st, loss = fn_(clf, codes, labels, w, eps, reduction)
+    for p, g in zip(_params(clf), grads):
+        g = g.detach().to(device=p.device, dtype=p.dtype)
+        if accumulate and p.grad is not None:
+            p.grad.add_(g)
+        else:
+            p.grad = g.clone()
+    out = ce_summary(*st, eps, background_hack)
+    out["loss"] = float(loss)
+    return out
+
+
 def smooth_targets(mask, label_smoothing, generator=None):
     """The soft targets of Camelyon16BCELoss's label smoothing (train_helpers.py:133-135) for a whole mask grid:
     |1 - ((1 + t + N(0, 1) * label_smoothing) mod 2)| with t = mask - 1, fp32, on the mask's device, one normal draw per
@@ -194,8 +285,9 @@ def _load_slide(images, masks, stem):
     return img, msk
 
 
-def train_hdf5(clf, path, optimizer, *, epochs, batch_size, pos_weight, seed, train_frac=0.9, label_smoothing=0.0,
-               reduction="sum", shuffle=False, drop_last=False, aligned_crops=False, grad_fn=None, forward_fn=None):
+def train_hdf5(clf, path, optimizer, *, epochs, batch_size, seed, pos_weight=None, train_frac=0.9, label_smoothing=0.0,
+               reduction="sum", shuffle=False, drop_last=False, aligned_crops=False, grad_fn=None, forward_fn=None,
+               class_weight=None):
     """Train `clf` on an archive written by save_encodings_hdf5 (`images/<stem>`, `masks/<stem>_mask`) the way the
     reference's datamodule walks it: the training slides of embeddings_split(keys, 'train', train_frac) in that order
     (shuffle=True permutes them per epoch with the seeded RandomState, as the reference's DataLoader shuffles with torch's),
@@ -210,7 +302,18 @@ def train_hdf5(clf, path, optimizer, *, epochs, batch_size, pos_weight, seed, tr
     without the host in between (on the CPU when the trainer was built with device='cpu'), losses and stats are read back
     once per epoch, and `clf` receives the weights (sync_to_module) before each epoch's validation.
     -> [{'epoch', 'steps': [{'stems', 'shape', loss_and_grads' dict ...}], 'train': pooled scores of the epoch's steps,
-         'val': pooled scores of the validation slides}, ...]   (loss = summed loss / summed n_valid, precision, recall)"""
+         'val': pooled scores of the validation slides}, ...]   (loss = summed loss / summed n_valid, precision, recall)
+    A classifier with n_out > 1 trains with nn.CrossEntropyLoss(weight=class_weight, label_smoothing) instead: the masks go
+    in as class indices, label_smoothing is the loss's deterministic eps (no noise is drawn), pos_weight is not used, each
+    step is ce_loss_and_grads (or the step of a ClassifierTrainer built with loss='ce', whose class_weight and
+    label_smoothing then apply), validation is classify_slide(loss='ce'), and the pooled scores are ce_summary's.
+    ValueError: n_out == 1 without pos_weight."""
+    if clf.n_out > 1:
+        return _train_hdf5_ce(clf, path, optimizer, epochs=epochs, batch_size=batch_size, seed=seed, train_frac=train_frac,
+                              label_smoothing=label_smoothing, reduction=reduction, shuffle=shuffle, drop_last=drop_last,
+                              aligned_crops=aligned_crops, grad_fn=grad_fn, forward_fn=forward_fn, class_weight=class_weight)
+    if pos_weight is None:
+        raise ValueError("train_hdf5: pos_weight is required for n_out == 1")
     r = hdf5.H5Reader(path)
     if "images" not in r.keys() or "masks" not in r.keys():
         raise KeyError(f"{path} needs the groups images/ and masks/")
@@ -288,4 +391,86 @@ def train_hdf5(clf, path, optimizer, *, epochs, batch_size, pos_weight, seed, tr
             for j, k in enumerate(("tp", "fp", "fn", "tn", "loss_sum")):
                 vtot[j] += res[k]
         history.append({"epoch": epoch, "steps": steps, "train": _summary(*tot), "val": _summary(*vtot)})
+    return history
+
+
+def _train_hdf5_ce(clf, path, optimizer, *, epochs, batch_size, seed, train_frac, label_smoothing, reduction, shuffle, drop_last,
+                   aligned_crops, grad_fn, forward_fn, class_weight):
+    """train_hdf5 for n_out > 1 (see there)"""
+    r = hdf5.H5Reader(path)
+    if "images" not in r.keys() or "masks" not in r.keys():
+        raise KeyError(f"{path} needs the groups images/ and masks/")
+    images, masks = r["images"], r["masks"]
+    train_stems = embeddings_split(images.keys(), "train", train_frac)
+    val_stems = embeddings_split(images.keys(), "validation", train_frac)
+    for s in train_stems + val_stems:
+        if s + "_mask" not in masks:
+            raise KeyError(f"no masks/{s}_mask in {path}")
+    from .optim import SAM, ClassifierTrainer                       # (optim.py imports this module)
+    trainer = optimizer if isinstance(optimizer, ClassifierTrainer) else None
+    sam = isinstance(optimizer, SAM)
+    if trainer is not None:
+        if trainer.clf is not clf:
+            raise ValueError("train_hdf5: the ClassifierTrainer was made from another classifier")
+        if trainer.loss != "ce":
+            raise ValueError("train_hdf5: a classifier with n_out > 1 needs a ClassifierTrainer built with loss='ce'")
+        if grad_fn is not None:
+            raise ValueError("train_hdf5: a ClassifierTrainer computes its own gradients; grad_fn does not apply")
+        if trainer.device is None:
+            trainer._ensure("cuda")
+        class_weight, label_smoothing = trainer.class_weight, trainer.label_smoothing
+    w, eps = ce_arguments(clf.n_out, class_weight, label_smoothing)
+    no = clf.n_out
+    on_gpu = grad_fn is None if trainer is None else trainer.device == "cuda"
+    rng = np.random.RandomState(seed)
+    kw = dict(class_weight=w, label_smoothing=eps)
+
+    history = []
+    for epoch in range(int(epochs)):
+        order = list(train_stems)
+        if shuffle:
+            order = [order[i] for i in rng.permutation(len(order))]
+        steps, tot = [], [np.zeros((no, no), np.int64), 0.0, 0.0, 0]
+        for i in range(0, len(order), batch_size):
+            stems = order[i:i + batch_size]
+            if drop_last and len(stems) < batch_size:
+                break
+            codes, labels = collate_random_crop([_load_slide(images, masks, s) for s in stems], rng, aligned=aligned_crops)
+            if codes.dtype not in ops._IDX_DTYPES:
+                codes = codes.to(torch.int32)
+            labels = labels.to(torch.uint8)
+            if on_gpu:
+                codes, labels = codes.cuda(), labels.cuda()
+            if trainer is not None:
+                steps.append((trainer.step(codes, labels, reduction=reduction), list(stems), tuple(codes.shape)))
+                continue
+            optimizer.zero_grad(set_to_none=True)
+            res = ce_loss_and_grads(clf, codes, labels, reduction=reduction, grad_fn=grad_fn, **kw)
+            if sam:
+                optimizer.first_step(zero_grad=True)
+                ce_loss_and_grads(clf, codes, labels, reduction=reduction, grad_fn=grad_fn, **kw)
+                optimizer.second_step(zero_grad=True)
+            else:
+                optimizer.step()
+            steps.append(dict(res, stems=list(stems), shape=tuple(codes.shape)))
+        if trainer is not None:
+            for n, ((loss, st), stems, shape) in enumerate(steps):  # read back after the epoch's last step was queued
+                res = ce_summary(*ce_stats_rows(st, no), eps)
+                res["loss"] = float(loss)
+                steps[n] = dict(res, stems=stems, shape=shape)
+            trainer.sync_to_module()
+        for res in steps:
+            tot[0] += res["confusion"]
+            tot[1] += res["weight_sum"]
+            tot[2] += res["loss_sum"]
+            tot[3] += res["n_bad"]
+        vtot = [np.zeros((no, no), np.int64), 0.0, 0.0, 0]
+        for s in val_stems:
+            img, msk = _load_slide(images, masks, s)
+            res = classify_slide(clf, img, msk, loss="ce", forward_fn=forward_fn, **kw)
+            vtot[0] += res["confusion"]
+            vtot[1] += res["weight_sum"]
+            vtot[2] += res["loss_sum"]
+            vtot[3] += res["n_bad"]
+        history.append({"epoch": epoch, "steps": steps, "train": ce_pooled(*tot), "val": ce_pooled(*vtot)})
     return history

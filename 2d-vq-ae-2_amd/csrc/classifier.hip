@@ -51,7 +51,7 @@ void classifier_kernel(const void* __restrict__ codes, int idx_dtype, int H, int
                        const float* __restrict__ b2, const float* __restrict__ w3, const float* __restrict__ b3,
                        float* __restrict__ logits, uint8_t* __restrict__ heat, const uint8_t* __restrict__ mask,
                        const float* __restrict__ target, float pos_weight, float* __restrict__ glogit,
-                       double* __restrict__ part) {
+                       double* __restrict__ part, CeArgs ce) {
     using G = Geo<TW>;
     constexpr int EN = G::EH * G::EW, AN = G::AH * G::AW, BN = G::BH * G::BW;
     static_assert(BN / P == NT && G::BH % P == 0, "stage 3: one column strip per thread");
@@ -150,6 +150,12 @@ void classifier_kernel(const void* __restrict__ codes, int idx_dtype, int H, int
     // ---- stage 4: out_conv on the tile, strips of two rows; logits / heat / stats ---------------------------------------
     int n_tp = 0, n_fp = 0, n_fn = 0, n_tn = 0;
     double loss = 0.0;
+    int conf[NO][NO], n_bad = 0;                                  // cross-entropy (NO > 1): counts at [label][prediction]
+    double s_w = 0.0, s_nll = 0.0, s_sm = 0.0;
+#pragma unroll
+    for (int l = 0; l < NO; ++l)
+#pragma unroll
+        for (int q = 0; q < NO; ++q) conf[l][q] = 0;
     for (int it = tid; it < (TH / 2) * TW; it += NT) {
         const int s = it / TW, lx = it - s * TW, ly0 = 2 * s;
         float acc[2][NO];
@@ -212,7 +218,92 @@ void classifier_kernel(const void* __restrict__ codes, int idx_dtype, int H, int
                         }
                         if (glogit) glogit[(int64_t)b * hw + pos] = g;
                     }
+                } else {
+                    // nn.CrossEntropyLoss(weight, label_smoothing) on the NO logits of this position: a log-softmax on
+                    // the max-subtracted logits in fp32, the loss terms summed in fp64.  -log p_c = lse - (x_c - max).
+                    float mx = acc[p][0];
+                    int am = 0;
+#pragma unroll
+                    for (int o = 1; o < NO; ++o)
+                        if (acc[p][o] > mx) { mx = acc[p][o]; am = o; }   // strict: the lowest index wins a tie
+                    if (ce.cls) ce.cls[(int64_t)b * hw + pos] = (uint8_t)am;
+                    if (ce.prob || mask) {
+                        float ex[NO], se = 0.0f;
+#pragma unroll
+                        for (int o = 0; o < NO; ++o) { ex[o] = expf(acc[p][o] - mx); se += ex[o]; }
+                        const float inv = 1.0f / se;
+                        if (ce.prob) {
+#pragma unroll
+                            for (int o = 0; o < NO; ++o)
+                                ce.prob[((int64_t)b * NO + o) * hw + pos] = (uint8_t)rintf(255.0f * (ex[o] * inv));
+                        }
+                        if (mask) {
+                            const int y = mask[(int64_t)b * hw + pos];
+                            float g[NO];
+#pragma unroll
+                            for (int o = 0; o < NO; ++o) g[o] = 0.0f;
+                            if (y < NO) {
+                                const float lse = logf(se);
+                                float wy = 0.0f, nly = 0.0f, wsum = 0.0f;
+                                double sm = 0.0;
+#pragma unroll
+                                for (int o = 0; o < NO; ++o) {
+                                    const float nl = lse - (acc[p][o] - mx);
+                                    wsum += ce.w[o];
+                                    sm += (double)ce.w[o] * (double)nl;
+                                    if (o == y) { wy = ce.w[o]; nly = nl; }
+#pragma unroll
+                                    for (int q = 0; q < NO; ++q) conf[o][q] += (o == y && q == am);
+                                }
+                                s_w += (double)wy;
+                                s_nll += (double)wy * (double)nly;
+                                s_sm += sm;
+                                if (glogit) {
+                                    // p_y - 1 = -(sum of the other classes' p): no cancellation where p_y is close to 1
+                                    float others = 0.0f;
+#pragma unroll
+                                    for (int o = 0; o < NO; ++o) others += o == y ? 0.0f : ex[o];
+#pragma unroll
+                                    for (int o = 0; o < NO; ++o) {
+                                        const float po = ex[o] * inv;
+                                        g[o] = ce.keep * wy * (o == y ? -(others * inv) : po) + ce.smooth * (wsum * po - ce.w[o]);
+                                    }
+                                }
+                            } else {
+                                ++n_bad;                           // counted aside, never indexed; its gradient is 0
+                            }
+                            if (glogit) {
+#pragma unroll
+                                for (int o = 0; o < NO; ++o) glogit[((int64_t)b * NO + o) * hw + pos] = g[o];
+                            }
+                        }
+                    }
                 }
+            }
+        }
+    }
+    if constexpr (NO > 1) {
+        if (part) {                                               // (workgroup-uniform)
+            __shared__ double red[NT / 64][CEK];
+            double v[CEK];
+#pragma unroll
+            for (int k = 0; k < CEK; ++k) v[k] = 0.0;
+#pragma unroll
+            for (int l = 0; l < NO; ++l)
+#pragma unroll
+                for (int q = 0; q < NO; ++q) v[l * 4 + q] = conf[l][q];
+            v[VQAE_CE_WEIGHT_SUM] = s_w; v[VQAE_CE_NLL_SUM] = s_nll; v[VQAE_CE_SMOOTH_SUM] = s_sm; v[VQAE_CE_N_BAD] = n_bad;
+#pragma unroll
+            for (int k = 0; k < CEK; ++k) v[k] = wave_sum(v[k]);
+            const int wv = tid >> 6;
+            if ((tid & 63) == 0)
+#pragma unroll
+                for (int k = 0; k < CEK; ++k) red[wv][k] = v[k];
+            __syncthreads();
+            if (tid < CEK) {
+                double r = red[0][tid];
+                for (int w = 1; w < NT / 64; ++w) r += red[w][tid];
+                part[((int64_t)b * gridDim.x + tile) * CEK + tid] = r;
             }
         }
     }
@@ -237,27 +328,29 @@ void classifier_kernel(const void* __restrict__ codes, int idx_dtype, int H, int
     }
 }
 
-// One workgroup per slide: thread j sums rows j, j + 256, ... in order, then the fixed shuffle / LDS order above.
+// One workgroup per slide (NK columns: the BCE rows or the cross-entropy rows): thread j sums rows j, j + 256, ... in
+// order, then the fixed shuffle / LDS order above.
+template <int NK>
 __global__ __launch_bounds__(NT) void classifier_stats_final(const double* __restrict__ part, int ntiles, double* __restrict__ out) {
     const int b = blockIdx.x, tid = threadIdx.x;
-    const double* q = part + (int64_t)b * ntiles * SK;
-    double r[SK];
+    const double* q = part + (int64_t)b * ntiles * NK;
+    double r[NK];
 #pragma unroll
-    for (int k = 0; k < SK; ++k) r[k] = 0.0;
+    for (int k = 0; k < NK; ++k) r[k] = 0.0;
     for (int j = tid; j < ntiles; j += NT)
 #pragma unroll
-        for (int k = 0; k < SK; ++k) r[k] += q[(int64_t)j * SK + k];
-    __shared__ double red[NT / 64][SK];
+        for (int k = 0; k < NK; ++k) r[k] += q[(int64_t)j * NK + k];
+    __shared__ double red[NT / 64][NK];
 #pragma unroll
-    for (int k = 0; k < SK; ++k) r[k] = wave_sum(r[k]);
+    for (int k = 0; k < NK; ++k) r[k] = wave_sum(r[k]);
     if ((tid & 63) == 0)
 #pragma unroll
-        for (int k = 0; k < SK; ++k) red[tid >> 6][k] = r[k];
+        for (int k = 0; k < NK; ++k) red[tid >> 6][k] = r[k];
     __syncthreads();
-    if (tid < SK) {
+    if (tid < NK) {
         double s = red[0][tid];
         for (int w = 1; w < NT / 64; ++w) s += red[w][tid];
-        out[(int64_t)b * SK + tid] = s;
+        out[(int64_t)b * NK + tid] = s;
     }
 }
 
@@ -311,6 +404,7 @@ struct Launch {
     const float* table; int K, E, table_lds;
     const float *w1, *b1, *w2, *b2, *w3, *b3;
     float* logits; uint8_t* heat; const uint8_t* mask; const float* target; float pos_weight; float* glogit; double* part;
+    CeArgs ce;
     dim3 grid; int lds_bytes; hipStream_t st;
 };
 
@@ -320,7 +414,7 @@ int launch(const Launch& a) {
     if (int rc = vqae::set_max_dynamic_lds((const void*)kern, LDS_PER_WG)) return rc;
     kern<<<a.grid, NT, a.lds_bytes, a.st>>>(a.codes, a.idx_dtype, a.H, a.W, a.tiles_x, a.table, a.K, a.E, a.table_lds, a.w1,
                                            a.b1, a.w2, a.b2, a.w3, a.b3, a.logits, a.heat, a.mask, a.target, a.pos_weight,
-                                           a.glogit, a.part);
+                                           a.glogit, a.part, a.ce);
     VQAE_LAUNCH_CHECK();
     return VQAE_OK;
 }
@@ -365,12 +459,13 @@ int vqae_cls::ensure_device(vqae_classifier* c, hipStream_t st) {
 
 int vqae_cls::forward_launch(vqae_classifier* c, const void* codes_dev, int idx_dtype, int batch, int h, int w, float* logits_dev,
                              uint8_t* heat_u8_dev, const uint8_t* mask_dev, const float* target_dev, float pos_weight,
-                             float* grad_logit_dev, double* stats_dev, void* workspace_dev, hipStream_t st) {
+                             float* grad_logit_dev, double* stats_dev, void* workspace_dev, hipStream_t st, const CeArgs* ce) {
     int tiles_x = 0;
     const int64_t ntiles = tile_count(c, h, w, &tiles_x);
     if (int rc = ensure_device(c, st)) return rc;
     const int planes = plane_floats(c->tw, c->E, c->C) * 4, table = c->K * c->E * 4;
-    const bool table_lds = planes + table + 256 <= LDS_PER_WG;     // (256: the kernel's static reduction scratch)
+    // (the kernel's static reduction scratch: 4 x 6 doubles, 4 x 20 in the cross-entropy instantiations)
+    const bool table_lds = planes + table + (c->NO == 1 ? 256 : 768) <= LDS_PER_WG;
     Launch a;
     a.codes = codes_dev; a.idx_dtype = idx_dtype; a.H = h; a.W = w; a.tiles_x = tiles_x;
     a.table = c->dev + c->o_table; a.K = c->K; a.E = c->E; a.table_lds = table_lds;
@@ -379,6 +474,7 @@ int vqae_cls::forward_launch(vqae_classifier* c, const void* codes_dev, int idx_
     a.logits = logits_dev; a.heat = heat_u8_dev; a.mask = (stats_dev || grad_logit_dev) ? mask_dev : nullptr;
     a.target = target_dev; a.pos_weight = pos_weight; a.glogit = grad_logit_dev;
     a.part = stats_dev ? (double*)workspace_dev : nullptr;
+    if (ce) a.ce = *ce;
     a.grid = dim3((unsigned)ntiles, (unsigned)batch);
     a.lds_bytes = planes + (table_lds ? table : 0);
     a.st = st;
@@ -388,7 +484,8 @@ int vqae_cls::forward_launch(vqae_classifier* c, const void* codes_dev, int idx_
     else rc = launch_no<16, 30, 2>(c->NO, a);
     if (rc) return rc;
     if (stats_dev) {
-        classifier_stats_final<<<(unsigned)batch, NT, 0, st>>>((const double*)workspace_dev, (int)ntiles, stats_dev);
+        if (ce) classifier_stats_final<CEK><<<(unsigned)batch, NT, 0, st>>>((const double*)workspace_dev, (int)ntiles, stats_dev);
+        else classifier_stats_final<SK><<<(unsigned)batch, NT, 0, st>>>((const double*)workspace_dev, (int)ntiles, stats_dev);
         VQAE_LAUNCH_CHECK();
     }
     return VQAE_OK;
@@ -523,4 +620,46 @@ extern "C" int vqae_classifier_forward(vqae_classifier* c, const void* codes_dev
     if (batch == 0) return VQAE_OK;
     return forward_launch(c, codes_dev, idx_dtype, batch, h, w, logits_dev, heat_u8_dev, mask_dev, nullptr, pos_weight, nullptr,
                           stats_dev, workspace_dev, (hipStream_t)stream);
+}
+
+// ---- Multi-class: nn.CrossEntropyLoss scores from the same launch ---------------------------------------------------------
+int vqae_cls::ce_args(const char* who, const vqae_classifier* c, const float* weight, float label_smoothing, CeArgs* out) {
+    VQAE_REQUIRE(label_smoothing >= 0.f && label_smoothing <= 1.f, VQAE_ERR_INVALID, "%s: label_smoothing %g is outside [0, 1]", who,
+                 (double)label_smoothing);
+    CeArgs a;
+    for (int o = 0; o < c->NO && weight; ++o) {
+        VQAE_REQUIRE(std::isfinite(weight[o]) && weight[o] >= 0.f, VQAE_ERR_INVALID, "%s: weight[%d] must be finite and >= 0", who, o);
+        a.w[o] = weight[o];
+    }
+    a.keep = (float)(1.0 - (double)label_smoothing);
+    a.smooth = (float)((double)label_smoothing / c->NO);
+    *out = a;
+    return VQAE_OK;
+}
+
+extern "C" size_t vqae_classifier_ce_workspace_bytes(const vqae_classifier* c, int batch, int h, int w) {
+    if (!c || c->NO == 1 || batch <= 0 || h < 1 || w < 1) return 0;
+    return (size_t)vqae::round_up((int64_t)batch * tile_count(c, h, w, nullptr) * CEK * 8, 256);
+}
+
+extern "C" int vqae_classifier_forward_ce(vqae_classifier* c, const void* codes_dev, int idx_dtype, int batch, int h, int w,
+                                          float* logits_dev, uint8_t* prob_u8_dev, uint8_t* class_u8_dev, const uint8_t* labels_dev,
+                                          const float* weight, float label_smoothing, double* stats_dev, void* workspace_dev,
+                                          void* stream) {
+    VQAE_REQUIRE(c && codes_dev, VQAE_ERR_INVALID, "classifier_forward_ce: null pointer");
+    VQAE_REQUIRE(logits_dev || prob_u8_dev || class_u8_dev || stats_dev, VQAE_ERR_INVALID, "classifier_forward_ce: no output requested");
+    VQAE_REQUIRE(!stats_dev || labels_dev, VQAE_ERR_INVALID, "classifier_forward_ce: stats need labels");
+    VQAE_REQUIRE(!stats_dev || workspace_dev, VQAE_ERR_INVALID, "classifier_forward_ce: stats need the workspace");
+    VQAE_REQUIRE(idx_dtype_ok(idx_dtype), VQAE_ERR_INVALID, "classifier_forward_ce: bad index dtype %d", idx_dtype);
+    VQAE_REQUIRE(batch >= 0 && h >= 1 && w >= 1, VQAE_ERR_INVALID, "classifier_forward_ce: bad shape batch=%d h=%d w=%d", batch, h, w);
+    CeArgs ce;
+    if (int rc = ce_args("classifier_forward_ce", c, weight, label_smoothing, &ce)) return rc;
+    VQAE_REQUIRE(c->NO > 1, VQAE_ERR_UNSUPPORTED,
+                 "classifier_forward_ce: cross-entropy needs n_out >= 2; vqae_classifier_forward scores n_out == 1");
+    VQAE_REQUIRE(batch <= 65535, VQAE_ERR_UNSUPPORTED, "classifier_forward_ce: batch %d > 65535", batch);
+    VQAE_REQUIRE(tile_count(c, h, w, nullptr) < (1ll << 31), VQAE_ERR_UNSUPPORTED, "classifier_forward_ce: a grid of %d x %d codes", h, w);
+    if (batch == 0) return VQAE_OK;
+    ce.prob = prob_u8_dev; ce.cls = class_u8_dev;
+    return forward_launch(c, codes_dev, idx_dtype, batch, h, w, logits_dev, nullptr, stats_dev ? labels_dev : nullptr, nullptr, 1.0f,
+                          nullptr, stats_dev, workspace_dev, (hipStream_t)stream, &ce);
 }

@@ -12,6 +12,7 @@ namespace vqae_cls {
 constexpr int NT = 256;                 // threads per workgroup
 constexpr int TH = 14;                  // output rows per tile
 constexpr int SK = VQAE_CLS_STATS_K;
+constexpr int CEK = VQAE_CE_STATS_K;    // columns of a cross-entropy stats row
 
 // ELU(alpha = 1) with the negative side to <= 3 ulp of expm1: the degree-7 Taylor series for v > -0.3 (next term
 // 0.3^7 / 40320 = 5e-9 relative), the hardware exponential minus one beyond (no cancellation there: |result| >= 0.26).
@@ -79,8 +80,18 @@ ParamMap param_map(const vqae_classifier* c);
 // The forward launch (and, with stats_dev, its stats reduction) after validation, batch >= 1.  target_dev (fp32 [B][h][w],
 // optional) replaces the hard target mask - 1 in the loss sum; grad_logit_dev (fp32 [B][h][w], optional; needs the mask)
 // receives dL/dlogit of the summed loss: sigmoid(x) * (1 - t + pos_weight * t) - pos_weight * t where mask != 0, 0 elsewhere.
+// With `ce` (n_out > 1) the epilogue is the cross-entropy one instead: mask_dev holds the class indices, the stats rows have
+// CEK columns (VQAE_CE_*), grad_logit_dev is fp32 [B][n_out][h][w] and heat / target / pos_weight are not read.
+struct CeArgs {
+    uint8_t* prob = nullptr;          // uint8 [B][n_out][h][w] = rintf(255 * softmax), optional
+    uint8_t* cls = nullptr;           // uint8 [B][h][w] = argmax, lowest index on ties, optional
+    float w[4] = {1.0f, 1.0f, 1.0f, 1.0f};   // class weights (entries >= n_out are not read)
+    float keep = 1.0f, smooth = 0.0f; // 1 - label_smoothing and label_smoothing / n_out, rounded once from double
+};
 int forward_launch(vqae_classifier* c, const void* codes_dev, int idx_dtype, int batch, int h, int w, float* logits_dev,
                    uint8_t* heat_u8_dev, const uint8_t* mask_dev, const float* target_dev, float pos_weight,
-                   float* grad_logit_dev, double* stats_dev, void* workspace_dev, hipStream_t st);
+                   float* grad_logit_dev, double* stats_dev, void* workspace_dev, hipStream_t st, const CeArgs* ce = nullptr);
+// What the cross-entropy entry points share: weight (host [n_out] or null = ones) and label_smoothing checked and rounded.
+int ce_args(const char* who, const vqae_classifier* c, const float* weight, float label_smoothing, CeArgs* out);
 
 }  // namespace vqae_cls

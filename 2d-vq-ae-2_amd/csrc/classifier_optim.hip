@@ -237,14 +237,16 @@ struct vqae_classifier_optim {
     double* partial = nullptr;
 };
 
-extern "C" int vqae_classifier_optim_create(vqae_classifier* c, const vqae_classifier_optim_config* cfg,
-                                            vqae_classifier_optim** out) {
-    VQAE_REQUIRE(out, VQAE_ERR_INVALID, "classifier_optim_create: null out");
+// The step kernels walk the packed gradient and the image through param_map, which follows n_out (out_conv's [NO][C][9] and
+// [NO] are tensors 5 and 6, each with its own LAMB norms): the two entry points differ in the n_out they accept only.
+static int optim_create(const char* who, bool ce, vqae_classifier* c, const vqae_classifier_optim_config* cfg,
+                        vqae_classifier_optim** out) {
+    VQAE_REQUIRE(out, VQAE_ERR_INVALID, "%s: null out", who);
     *out = nullptr;
-    VQAE_REQUIRE(c, VQAE_ERR_INVALID, "classifier_optim_create: null classifier");
-    if (int rc = check_config("classifier_optim_create", cfg)) return rc;
-    VQAE_REQUIRE(c->NO == 1, VQAE_ERR_UNSUPPORTED, "classifier_optim_create: the loss is defined for n_out == 1, this classifier has %d",
-                 c->NO);
+    VQAE_REQUIRE(c, VQAE_ERR_INVALID, "%s: null classifier", who);
+    if (int rc = check_config(who, cfg)) return rc;
+    if (ce) VQAE_REQUIRE(c->NO > 1, VQAE_ERR_UNSUPPORTED, "%s: cross-entropy needs n_out >= 2; vqae_classifier_optim_create trains n_out == 1", who);
+    else VQAE_REQUIRE(c->NO == 1, VQAE_ERR_UNSUPPORTED, "%s: the loss is defined for n_out == 1, this classifier has %d", who, c->NO);
     if (int rc = ensure_device(c, nullptr)) return rc;             // the image this optimiser steps, on the current device
     vqae_classifier_optim* o = new vqae_classifier_optim;
     o->c = c; o->cfg = *cfg; o->dev_id = c->dev_id;
@@ -257,11 +259,21 @@ extern "C" int vqae_classifier_optim_create(vqae_classifier* c, const vqae_class
     if (e != hipSuccess) {
         if (o->state) (void)hipFree(o->state);
         delete o;
-        return vqae::fail(VQAE_ERR_HIP, "classifier_optim_create: %s", hipGetErrorString(e));
+        return vqae::fail(VQAE_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     }
     o->m = o->state; o->v = o->m + gpad; o->saved = o->v + gpad; o->partial = (double*)(o->saved + gpad);
     *out = o;
     return VQAE_OK;
+}
+
+extern "C" int vqae_classifier_optim_create(vqae_classifier* c, const vqae_classifier_optim_config* cfg,
+                                            vqae_classifier_optim** out) {
+    return optim_create("classifier_optim_create", false, c, cfg, out);
+}
+
+extern "C" int vqae_classifier_optim_create_ce(vqae_classifier* c, const vqae_classifier_optim_config* cfg,
+                                               vqae_classifier_optim** out) {
+    return optim_create("classifier_optim_create_ce", true, c, cfg, out);
 }
 
 extern "C" void vqae_classifier_optim_destroy(vqae_classifier_optim* o) {

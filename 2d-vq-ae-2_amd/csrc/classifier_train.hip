@@ -99,7 +99,7 @@ __device__ __forceinline__ void reduce_slices(double* red, const double acc[10],
     }
 }
 
-template <int C, int TW>
+template <int C, int NO, int TW>
 __global__ __launch_bounds__(NT)
 void classifier_backward_kernel(const void* __restrict__ codes, int idx_dtype, int H, int W, int tiles_x, int ntiles, int64_t total,
                                 const float* __restrict__ table, int K, int E,
@@ -116,15 +116,15 @@ void classifier_backward_kernel(const void* __restrict__ codes, int idx_dtype, i
     unsigned long long* const pfix = (unsigned long long*)lds_d;              // [K][E] fixed-point table gradient when emb_lds
     float* const pa = (float*)(lds_d + (emb_lds ? K * E : 0));   // A [C][AH][AW], then dA on its tile + 1
     float* const pb = pa + C * AN;                                // B [C][BH][BW], then dB
-    float* const pg = pb + C * BN;                                // g [AH][AW]
-    float* const pe = pg + AN;                                    // E0 [E][EH][EW]
+    float* const pg = pb + C * BN;                                // g [NO][AH][AW]
+    float* const pe = pg + NO * AN;                               // E0 [E][EH][EW]
     const int tid = threadIdx.x;
     const int64_t hw = (int64_t)H * W;
 
     if (emb_lds)
         for (int i = tid; i < K * E; i += NT) pfix[i] = 0ull;
 
-    const Slice s3 = make_slice<TW>(tid, C, 1), s2 = make_slice<TW>(tid, C, C), s1 = make_slice<TW>(tid, E, C);
+    const Slice s3 = make_slice<TW>(tid, C, NO), s2 = make_slice<TW>(tid, C, C), s1 = make_slice<TW>(tid, E, C);
     double acc3[10], acc2[10], acc1[10];
 #pragma unroll
     for (int t = 0; t < 10; ++t) acc3[t] = acc2[t] = acc1[t] = 0.0;
@@ -148,7 +148,16 @@ void classifier_backward_kernel(const void* __restrict__ codes, int idx_dtype, i
         for (int i = tid; i < AN; i += NT) {
             const int ly = i / AW, lx = i - ly * AW;
             const int gy = y0 - 3 + ly, gx = x0 - 3 + lx;
-            pg[i] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? glogit[(int64_t)b * hw + (int64_t)gy * W + gx] : 0.0f;
+            if constexpr (NO == 1) {                               // (spelled as before NO existed, here and in the out-conv
+                                                                  //  correlation's plane stride: the n_out = 1 kernels
+                                                                  //  compile to the instruction stream they had)
+                pg[i] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? glogit[(int64_t)b * hw + (int64_t)gy * W + gx] : 0.0f;
+            } else {
+                const bool inside = gy >= 0 && gy < H && gx >= 0 && gx < W;
+#pragma unroll
+                for (int o = 0; o < NO; ++o)
+                    pg[o * AN + i] = inside ? glogit[((int64_t)b * NO + o) * hw + (int64_t)gy * W + gx] : 0.0f;
+            }
         }
         __syncthreads();
 
@@ -203,22 +212,26 @@ void classifier_backward_kernel(const void* __restrict__ codes, int idx_dtype, i
         __syncthreads();
 
         // ---- out_conv: dW3 = g (*) B, db3 = sum g ------------------------------------------------------------------------
-        correlate<TW>(s3, pg, 0, AW, 3 * AW + 3, pb, BN, BW, 1 * BW + 1, acc3);
+        correlate<TW>(s3, pg, NO == 1 ? 0 : AN, AW, 3 * AW + 3, pb, BN, BW, 1 * BW + 1, acc3);
         __syncthreads();
 
-        // ---- dB = elu'(B) * sum_t w3[c][t] g[q - t] on tile + 2, over B ---------------------------------------------------
+        // ---- dB = elu'(B) * sum_{o,t} w3[c][t][o] g[o][q - t] on tile + 2, over B ----------------------------------------
         for (int i = tid; i < BN; i += NT) {
             const int ly = i / BW, lx = i - ly * BW;
             const int gy = y0 - 2 + ly, gx = x0 - 2 + lx;
             const bool inside = gy >= 0 && gy < H && gx >= 0 && gx < W;
-            float gv[9];
+            float gv[NO][9];
 #pragma unroll
-            for (int t = 0; t < 9; ++t) gv[t] = pg[(ly + 2 - t / 3) * AW + (lx + 2 - t % 3)];
+            for (int o = 0; o < NO; ++o)
+#pragma unroll
+                for (int t = 0; t < 9; ++t) gv[o][t] = pg[o * AN + (ly + 2 - t / 3) * AW + (lx + 2 - t % 3)];
 #pragma unroll
             for (int c = 0; c < C; ++c) {
                 float s = 0.0f;
 #pragma unroll
-                for (int t = 0; t < 9; ++t) s = fmaf(w3[c * 9 + t], gv[t], s);
+                for (int o = 0; o < NO; ++o)
+#pragma unroll
+                    for (int t = 0; t < 9; ++t) s = fmaf(w3[(c * 9 + t) * NO + o], gv[o][t], s);
                 const float act = pb[c * BN + i];
                 pb[c * BN + i] = inside ? (act > 0.0f ? s : s * (act + 1.0f)) : 0.0f;
             }
@@ -289,13 +302,13 @@ void classifier_backward_kernel(const void* __restrict__ codes, int idx_dtype, i
     }
 
     // ---- one row per workgroup -----------------------------------------------------------------------------------------------
-    // row: in_conv.weight [C][E][9], in_conv.bias [C], hidden_conv1.weight [C][C][9], .bias [C], out_conv.weight [1][C][9], .bias [1]
+    // row: in_conv.weight [C][E][9], in_conv.bias [C], hidden_conv1.weight [C][C][9], .bias [C], out_conv.weight [NO][C][9], .bias [NO]
     double* const row = rows + (int64_t)blockIdx.x * row_len;
     double* const red = (double*)pa;
-    double* r1 = row, *rb1 = r1 + C * E * 9, *r2 = rb1 + C, *rb2 = r2 + C * C * 9, *r3 = rb2 + C, *rb3 = r3 + C * 9;
+    double* r1 = row, *rb1 = r1 + C * E * 9, *r2 = rb1 + C, *rb2 = r2 + C * C * 9, *r3 = rb2 + C, *rb3 = r3 + NO * C * 9;
     reduce_slices(red, acc1, E, C, r1, rb1);
     reduce_slices(red, acc2, C, C, r2, rb2);
-    reduce_slices(red, acc3, C, 1, r3, rb3);
+    reduce_slices(red, acc3, C, NO, r3, rb3);
     if (emb_lds) {                                                // (reduce_slices' barriers order the last tile's atomics)
         for (int i = tid; i < K * E; i += NT)
             if (pfix[i]) atomicAdd(emb_fix + i, pfix[i]);
@@ -307,6 +320,18 @@ __global__ void train_scale(const double* __restrict__ stats, int batch, int mea
     double n = 0.0, l = 0.0;
     for (int b = 0; b < batch; ++b) { n += stats[b * SK + VQAE_CLS_N_VALID]; l += stats[b * SK + VQAE_CLS_LOSS_SUM]; }
     *loss = mean ? l / n : l;                                     // (mean over no valid code: nan, as the reference's)
+    *scale = mean ? (n > 0.0 ? 1.0 / n : 0.0) : 1.0;
+}
+
+// the same for cross-entropy rows: loss = (1 - eps) * sum nll + (eps / NO) * sum smooth, 'mean' divides by sum w[y]
+__global__ void train_scale_ce(const double* __restrict__ stats, int batch, int mean, double keep, double smooth,
+                               double* __restrict__ loss, double* __restrict__ scale) {
+    double n = 0.0, a = 0.0, s = 0.0;
+    for (int b = 0; b < batch; ++b) {
+        n += stats[b * CEK + VQAE_CE_WEIGHT_SUM]; a += stats[b * CEK + VQAE_CE_NLL_SUM]; s += stats[b * CEK + VQAE_CE_SMOOTH_SUM];
+    }
+    const double l = keep * a + smooth * s;
+    *loss = mean ? l / n : l;                                     // (mean over a zero weight sum: nan, as torch's)
     *scale = mean ? (n > 0.0 ? 1.0 / n : 0.0) : 1.0;
 }
 
@@ -331,15 +356,16 @@ struct Plan {
     size_t o_glogit, o_fix, o_rows, o_scale, bytes;
 };
 
-Plan make_plan(const vqae_classifier* c, int batch, int h, int w) {
+Plan make_plan(const vqae_classifier* c, int batch, int h, int w, bool ce = false) {
     Plan p;
     p.total = (int64_t)batch * tile_count(c, h, w, nullptr);
     p.n_wg = (int)(p.total < MAX_WG ? p.total : MAX_WG);
     p.n_emb = c->K * c->E;
-    p.row_len = c->C * c->E * 9 + c->C + c->C * c->C * 9 + c->C + c->C * 9 + 1;
-    size_t n = vqae_classifier_workspace_bytes(c, batch, h, w);   // the forward's stats partials come first
+    p.row_len = c->C * c->E * 9 + c->C + c->C * c->C * 9 + c->C + c->NO * c->C * 9 + c->NO;
+    // the forward's stats partials come first
+    size_t n = ce ? vqae_classifier_ce_workspace_bytes(c, batch, h, w) : vqae_classifier_workspace_bytes(c, batch, h, w);
     auto take = [&n](int64_t bytes) { const size_t o = n; n += (size_t)vqae::round_up(bytes, 256); return o; };
-    p.o_glogit = take((int64_t)batch * h * w * 4);
+    p.o_glogit = take((int64_t)batch * c->NO * h * w * 4);
     p.o_fix = take((int64_t)p.n_emb * 8);
     p.o_rows = take((int64_t)p.n_wg * p.row_len * 8);
     p.o_scale = take(8);
@@ -347,13 +373,20 @@ Plan make_plan(const vqae_classifier* c, int batch, int h, int w) {
     return p;
 }
 
-template <int C, int TW>
+// Where the fixed-point table gradient is accumulated: in LDS while the table has at most EMB_LDS_MAX entries AND the planes
+// beside it stay within the 160 KiB a workgroup may request, in HBM otherwise.  The planes depend on (E, C, NO) and on the
+// tile width, itself a function of (E, C): the choice, and with it the partition and the bits, is a function of
+// (K, E, C, NO) alone.  (With the geometries in use -- TW = 62 only for C = 8, E <= 6 -- the largest case, E = 6, NO = 4,
+// takes 140 256 B of planes + 16 384 B of table = 156 640 B: the LDS path is always taken for K * E <= 2048.)
+template <int C, int NO, int TW>
 int launch_backward(const vqae_classifier* c, const Plan& p, const void* codes, int idx_dtype, int h, int w, int tiles_x, int ntiles,
                     char* ws, hipStream_t st) {
     constexpr int EN = (TH + 8) * (TW + 8), AN = (TH + 6) * (TW + 6), BN = (TH + 4) * (TW + 4);
-    const int emb_lds = p.n_emb <= EMB_LDS_MAX;
-    const int lds = (emb_lds ? p.n_emb * 8 : 0) + 4 * (C * AN + C * BN + AN + c->E * EN);
-    auto kern = classifier_backward_kernel<C, TW>;
+    const int planes = 4 * (C * AN + C * BN + NO * AN + c->E * EN);
+    const int emb_lds = p.n_emb <= EMB_LDS_MAX && p.n_emb * 8 + planes <= 160 * 1024;
+    const int lds = (emb_lds ? p.n_emb * 8 : 0) + planes;
+    VQAE_REQUIRE(lds <= 160 * 1024, VQAE_ERR_UNSUPPORTED, "classifier backward: %d bytes of LDS", lds);
+    auto kern = classifier_backward_kernel<C, NO, TW>;
     if (int rc = vqae::set_max_dynamic_lds((const void*)kern, 160 * 1024)) return rc;
     kern<<<p.n_wg, NT, lds, st>>>(codes, idx_dtype, h, w, tiles_x, ntiles, p.total, c->dev + c->o_table, c->K, c->E,
                                   c->dev + c->o_w1, c->dev + c->o_b1, c->dev + c->o_w2, c->dev + c->o_b2, c->dev + c->o_w3,
@@ -406,12 +439,77 @@ extern "C" int vqae_classifier_loss_grad(vqae_classifier* c, const void* codes_d
         return rc;
     VQAE_HIP_CHECK(hipMemsetAsync(ws + p.o_fix, 0, (size_t)p.n_emb * 8, st));
     int rc;
-    if (c->tw == 62) rc = launch_backward<8, 62>(c, p, codes_dev, idx_dtype, h, w, tiles_x, (int)ntiles, ws, st);
-    else if (c->C == 8) rc = launch_backward<8, 30>(c, p, codes_dev, idx_dtype, h, w, tiles_x, (int)ntiles, ws, st);
-    else rc = launch_backward<16, 30>(c, p, codes_dev, idx_dtype, h, w, tiles_x, (int)ntiles, ws, st);
+    if (c->tw == 62) rc = launch_backward<8, 1, 62>(c, p, codes_dev, idx_dtype, h, w, tiles_x, (int)ntiles, ws, st);
+    else if (c->C == 8) rc = launch_backward<8, 1, 30>(c, p, codes_dev, idx_dtype, h, w, tiles_x, (int)ntiles, ws, st);
+    else rc = launch_backward<16, 1, 30>(c, p, codes_dev, idx_dtype, h, w, tiles_x, (int)ntiles, ws, st);
     if (rc) return rc;
     double* scale = (double*)(ws + p.o_scale);
     train_scale<<<1, 1, 0, st>>>(stats_dev, batch, reduction, loss_dev, scale);
+    VQAE_LAUNCH_CHECK();
+    const int n_out = p.n_emb + p.row_len;
+    train_final<<<(unsigned)vqae::ceil_div(n_out, NT), NT, 0, st>>>((const unsigned long long*)(ws + p.o_fix), p.n_emb,
+                                                                   (const double*)(ws + p.o_rows), p.n_wg, p.row_len, scale, grads_dev);
+    VQAE_LAUNCH_CHECK();
+    return VQAE_OK;
+}
+
+// ---- Multi-class: nn.CrossEntropyLoss as loss_f of CNNClassifier.step -------------------------------------------------------
+namespace {
+
+template <int C, int TW>
+int launch_backward_no(const vqae_classifier* c, const Plan& p, const void* codes, int idx_dtype, int h, int w, int tiles_x, int ntiles,
+                       char* ws, hipStream_t st) {
+    switch (c->NO) {
+        case 2: return launch_backward<C, 2, TW>(c, p, codes, idx_dtype, h, w, tiles_x, ntiles, ws, st);
+        case 3: return launch_backward<C, 3, TW>(c, p, codes, idx_dtype, h, w, tiles_x, ntiles, ws, st);
+        default: return launch_backward<C, 4, TW>(c, p, codes, idx_dtype, h, w, tiles_x, ntiles, ws, st);
+    }
+}
+
+}  // namespace
+
+extern "C" size_t vqae_classifier_ce_train_workspace_bytes(const vqae_classifier* c, int batch, int h, int w) {
+    if (!c || c->NO == 1 || batch <= 0 || h < 1 || w < 1) return 0;
+    return make_plan(c, batch, h, w, true).bytes;
+}
+
+extern "C" int vqae_classifier_loss_grad_ce(vqae_classifier* c, const void* codes_dev, int idx_dtype, int batch, int h, int w,
+                                            const uint8_t* labels_dev, const float* weight, float label_smoothing, int reduction,
+                                            double* grads_dev, double* stats_dev, double* loss_dev, void* workspace_dev, void* stream) {
+    VQAE_REQUIRE(c && codes_dev && labels_dev && grads_dev && stats_dev && loss_dev && workspace_dev, VQAE_ERR_INVALID,
+                 "classifier_loss_grad_ce: null pointer");
+    VQAE_REQUIRE(idx_dtype_ok(idx_dtype), VQAE_ERR_INVALID, "classifier_loss_grad_ce: bad index dtype %d", idx_dtype);
+    VQAE_REQUIRE(batch >= 0 && h >= 1 && w >= 1, VQAE_ERR_INVALID, "classifier_loss_grad_ce: bad shape batch=%d h=%d w=%d", batch, h, w);
+    CeArgs ce;
+    if (int rc = ce_args("classifier_loss_grad_ce", c, weight, label_smoothing, &ce)) return rc;
+    VQAE_REQUIRE(reduction == 0 || reduction == 1, VQAE_ERR_INVALID, "classifier_loss_grad_ce: reduction %d is not 0 (sum) or 1 (mean)",
+                 reduction);
+    VQAE_REQUIRE(c->NO > 1, VQAE_ERR_UNSUPPORTED,
+                 "classifier_loss_grad_ce: cross-entropy needs n_out >= 2; vqae_classifier_loss_grad trains n_out == 1");
+    VQAE_REQUIRE(batch <= 65535, VQAE_ERR_UNSUPPORTED, "classifier_loss_grad_ce: batch %d > 65535", batch);
+    int tiles_x = 0;
+    const int64_t ntiles = tile_count(c, h, w, &tiles_x);
+    VQAE_REQUIRE(ntiles < (1ll << 31), VQAE_ERR_UNSUPPORTED, "classifier_loss_grad_ce: a grid of %d x %d codes", h, w);
+    const hipStream_t st = (hipStream_t)stream;
+    const size_t ng = vqae_classifier_grad_floats(c);
+    if (batch == 0) {
+        VQAE_HIP_CHECK(hipMemsetAsync(grads_dev, 0, ng * sizeof(double), st));
+        VQAE_HIP_CHECK(hipMemsetAsync(loss_dev, 0, sizeof(double), st));
+        return VQAE_OK;
+    }
+    const Plan p = make_plan(c, batch, h, w, true);
+    char* ws = (char*)workspace_dev;
+    if (int rc = forward_launch(c, codes_dev, idx_dtype, batch, h, w, nullptr, nullptr, labels_dev, nullptr, 1.0f,
+                                (float*)(ws + p.o_glogit), stats_dev, workspace_dev, st, &ce))
+        return rc;
+    VQAE_HIP_CHECK(hipMemsetAsync(ws + p.o_fix, 0, (size_t)p.n_emb * 8, st));
+    int rc;
+    if (c->tw == 62) rc = launch_backward_no<8, 62>(c, p, codes_dev, idx_dtype, h, w, tiles_x, (int)ntiles, ws, st);
+    else if (c->C == 8) rc = launch_backward_no<8, 30>(c, p, codes_dev, idx_dtype, h, w, tiles_x, (int)ntiles, ws, st);
+    else rc = launch_backward_no<16, 30>(c, p, codes_dev, idx_dtype, h, w, tiles_x, (int)ntiles, ws, st);
+    if (rc) return rc;
+    double* scale = (double*)(ws + p.o_scale);
+    train_scale_ce<<<1, 1, 0, st>>>(stats_dev, batch, reduction, (double)ce.keep, (double)ce.smooth, loss_dev, scale);
     VQAE_LAUNCH_CHECK();
     const int n_out = p.n_emb + p.row_len;
     train_final<<<(unsigned)vqae::ceil_div(n_out, NT), NT, 0, st>>>((const unsigned long long*)(ws + p.o_fix), p.n_emb,

@@ -403,6 +403,63 @@ def classifier_loss_grad(handle, codes, mask, target=None, pos_weight=1.0, reduc
     return loss, grads, stats
 
 
+def _ce_weight(weight, n_out):
+    """class weights -> a ctypes float [n_out] for the library (None = ones: a null pointer)"""
+    if weight is None:
+        return None
+    w = [float(v) for v in (weight.tolist() if hasattr(weight, "tolist") else weight)]
+    assert len(w) == n_out, f"class_weight has {len(w)} entries, the classifier {n_out} outputs"
+    return (ctypes.c_float * n_out)(*w)
+
+
+def classifier_forward_ce(handle, codes, n_out, logits=False, prob=False, cls=True, labels=None, weight=None, label_smoothing=0.0):
+    """vqae_classifier_forward_ce on codes [B,H,W] (as stored, in HBM) with the vqae_classifier `handle` of n_out = 2 .. 4
+    outputs -> (logits fp32 [B,n_out,H,W] | None, prob uint8 [B,n_out,H,W] | None, class uint8 [B,H,W] | None,
+    stats float64 [B, 20] | None: the VQAE_CE_* rows, computed when `labels` (uint8 [B,H,W], class indices) is given, with
+    `weight` (n_out floats or None = ones) and label_smoothing)."""
+    _need_gpu(codes, labels)
+    assert codes.dim() == 3, codes.shape
+    codes = codes.contiguous()
+    B, H, W = codes.shape
+    dev = codes.device
+    lg = torch.empty((B, n_out, H, W), dtype=torch.float32, device=dev) if logits else None
+    pr = torch.empty((B, n_out, H, W), dtype=torch.uint8, device=dev) if prob else None
+    cl = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if cls else None
+    stats = ws = None
+    if labels is not None:
+        assert labels.dtype == torch.uint8 and tuple(labels.shape) == (B, H, W), (labels.dtype, labels.shape)
+        labels = labels.contiguous()
+        stats = torch.empty((B, L.CE_STATS_K), dtype=torch.float64, device=dev)
+        ws = torch.empty(max(1, L.lib().vqae_classifier_ce_workspace_bytes(handle, B, H, W)), dtype=torch.uint8, device=dev)
+    L.check(L.lib().vqae_classifier_forward_ce(handle, _p(codes), idx_code(codes.dtype), B, H, W, _p(lg), _p(pr), _p(cl), _p(labels),
+                                               _ce_weight(weight, n_out), float(label_smoothing), _p(stats), _p(ws), _stream()))
+    return lg, pr, cl, stats
+
+
+def classifier_loss_grad_ce(handle, codes, labels, n_out, weight=None, label_smoothing=0.0, reduction="mean"):
+    """vqae_classifier_loss_grad_ce on codes [B,H,W] (as stored, in HBM) and labels uint8 [B,H,W] (class indices) ->
+    (loss float64 [1], grads float64 [vqae_classifier_grad_floats] packed as classifier_loss_grad's, stats float64 [B, 20]:
+    the VQAE_CE_* rows).  Neither codes nor labels are checked: a code outside the table is a zero vector, a label >= n_out
+    is counted in column 19 and passes no gradient."""
+    _need_gpu(codes, labels)
+    assert codes.dim() == 3, codes.shape
+    assert reduction in ("sum", "mean"), reduction
+    codes = codes.contiguous()
+    B, H, W = codes.shape
+    dev = codes.device
+    assert labels.dtype == torch.uint8 and tuple(labels.shape) == (B, H, W), (labels.dtype, labels.shape)
+    labels = labels.contiguous()
+    lib = L.lib()
+    grads = torch.empty(lib.vqae_classifier_grad_floats(handle), dtype=torch.float64, device=dev)
+    stats = torch.empty((B, L.CE_STATS_K), dtype=torch.float64, device=dev)
+    loss = torch.empty(1, dtype=torch.float64, device=dev)
+    ws = torch.empty(max(1, lib.vqae_classifier_ce_train_workspace_bytes(handle, B, H, W)), dtype=torch.uint8, device=dev)
+    L.check(lib.vqae_classifier_loss_grad_ce(handle, _p(codes), idx_code(codes.dtype), B, H, W, _p(labels), _ce_weight(weight, n_out),
+                                             float(label_smoothing), 1 if reduction == "mean" else 0, _p(grads), _p(stats),
+                                             _p(loss), _p(ws), _stream()))
+    return loss, grads, stats
+
+
 def code_histogram(codes, mask=None, *, num_embeddings, n_labels=None, pooled=False, out=None, bad=None):
     """vqae_code_histogram on codes [B, ...] (uint8 / uint16 / int32 / int64 as stored, in HBM; B equally sized grids, any
     contiguous view) and mask uint8 of the same shape or None -> (hist int64 [B or 1, n_labels, num_embeddings],

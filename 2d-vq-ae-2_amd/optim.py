@@ -24,8 +24,8 @@ from torch.optim import Optimizer
 
 from . import _lib as L
 from . import ops
-from .classifier import NativeClassifier, _as_codes, _check_codes
-from .classifier_train import PARAM_NAMES, _params, torch_loss_grad
+from .classifier import NativeClassifier, _as_codes, _check_codes, ce_arguments
+from .classifier_train import PARAM_NAMES, _as_labels, _params, ce_weight_sum, torch_ce_loss_grad, torch_loss_grad
 
 
 class Lamb(Optimizer):
@@ -157,15 +157,22 @@ def _base_factory(kind):
 
 class ClassifierTrainer:
     """ClassifierTrainer(clf, optimizer='adamw' | 'adam' | 'lamb', lr=, betas=, eps=, weight_decay=, sam_rho=None,
-    sam_adaptive=False, device=None): trains a private copy of `clf`'s weights (n_out == 1); `clf` itself changes only in
-    sync_to_module().  eps and weight_decay default to the optimiser's own (torch.optim.Adam / AdamW, lamb.py).  The first
-    step decides where it runs unless device= says so: tensors in HBM take the HIP path, CPU tensors the torch one."""
+    sam_adaptive=False, device=None, loss='bce', class_weight=None, label_smoothing=0.0): trains a private copy of `clf`'s
+    weights; `clf` itself changes only in sync_to_module().  loss='bce' (n_out == 1) is Camelyon16BCELoss; loss='ce'
+    (n_out = 2 .. 4) is nn.CrossEntropyLoss(weight=class_weight, label_smoothing), the masks being class indices.  eps and
+    weight_decay default to the optimiser's own (torch.optim.Adam / AdamW, lamb.py).  The first step decides where it runs
+    unless device= says so: tensors in HBM take the HIP path, CPU tensors the torch one."""
 
     def __init__(self, clf, optimizer="adamw", lr=1e-3, betas=(0.9, 0.999), eps=None, weight_decay=None, sam_rho=None,
-                 sam_adaptive=False, device=None):
+                 sam_adaptive=False, device=None, loss="bce", class_weight=None, label_smoothing=0.0):
         if optimizer not in L.OPTIM_KINDS:
             raise ValueError(f"optimizer must be one of {sorted(L.OPTIM_KINDS)}, got {optimizer!r}")
-        if clf.n_out != 1:
+        if loss not in ("bce", "ce"):
+            raise ValueError(f"loss must be 'bce' or 'ce', got {loss!r}")
+        self.loss = loss
+        if loss == "ce":                            # nn.CrossEntropyLoss(weight, label_smoothing) for n_out = 2 .. 4
+            self.class_weight, self.label_smoothing = ce_arguments(clf.n_out, class_weight, label_smoothing)
+        elif clf.n_out != 1:
             raise ValueError(f"the loss is defined for n_out == 1, this classifier has {clf.n_out}")
         self.clf, self.kind = clf, optimizer
         d = _DEFAULTS[optimizer]
@@ -200,7 +207,8 @@ class ClassifierTrainer:
             self._native = NativeClassifier(*dims, {"layers." + n: p for n, p in ls.named_parameters()})
             h = ctypes.c_void_p()
             cfg = self._config()
-            L.check(L.lib().vqae_classifier_optim_create(self._native._h, ctypes.byref(cfg), ctypes.byref(h)))
+            create = L.lib().vqae_classifier_optim_create_ce if self.loss == "ce" else L.lib().vqae_classifier_optim_create
+            L.check(create(self._native._h, ctypes.byref(cfg), ctypes.byref(h)))
             self._opt_h = h
             self._shapes = [tuple(p.shape) for p in _params(self.clf)]
         elif kind == "cpu":
@@ -246,6 +254,10 @@ class ClassifierTrainer:
         check=True runs loss_and_grads' validation of labels, targets and codes first: blocking reads."""
         if reduction not in ("sum", "mean"):
             raise ValueError(f"reduction must be 'sum' or 'mean', got {reduction!r}")
+        if self.loss == "ce":
+            if target is not None or target2 is not None:
+                raise ValueError("soft targets belong to the BCE loss; loss='ce' smooths with its label_smoothing")
+            return self._step_ce(codes, mask, reduction, check)
         pos_weight = float(pos_weight)
         if not (np.isfinite(pos_weight) and pos_weight >= 0):
             raise ValueError(f"pos_weight must be finite and >= 0, got {pos_weight}")
@@ -297,6 +309,53 @@ class ClassifierTrainer:
         else:
             self._opt.step()
         return loss, stats
+
+    def _step_ce(self, codes, labels, reduction, check):
+        """step for loss='ce': `mask` holds the class indices -> (loss float64 [1], stats float64 [B, 20]: the VQAE_CE_* rows;
+        one pooled row on CPU tensors), from the first pass with SAM.  check=True: ce_loss_and_grads' validation first.
+        Without it nothing is read on the host, as in the BCE step: the labels are cast to uint8 as they are, so they must
+        already fit a byte (an int64 label >= 256 would wrap into another class unseen)."""
+        codes = _as_codes(codes)
+        self._ensure(codes.device.type)
+        labels = _as_labels(labels, codes)
+        no = self.clf.n_out
+        if check:
+            if labels.numel() and (int(labels.min()) < 0 or int(labels.max()) >= no):
+                raise ValueError(f"labels are class indices 0 .. {no - 1}")
+            _check_codes(codes, self.clf.num_embeddings)
+            if reduction == "mean" and not ce_weight_sum(labels, self.class_weight, no) > 0:
+                raise ValueError("reduction='mean' over a batch whose class weights sum to zero")
+        labels = labels.to(device=codes.device, dtype=torch.uint8)
+        kw = dict(weight=self.class_weight, label_smoothing=self.label_smoothing, reduction=reduction)
+        if self.device == "cuda":
+            lib, st = L.lib(), ops._stream()
+            loss, g, stats = self._native.loss_grad_ce(codes, labels, **kw)
+            if self.sam_rho is not None:
+                L.check(lib.vqae_classifier_optim_sam_first(self._opt_h, ops._p(g), st))
+                _, g, _ = self._native.loss_grad_ce(codes, labels, **kw)
+            L.check(lib.vqae_classifier_optim_step(self._opt_h, ops._p(g), st))
+            return loss, stats
+        loss, stats = self._cpu_pass_ce(codes, labels, reduction)
+        if self.sam_rho is not None:
+            self._opt.first_step(zero_grad=True)
+            self._cpu_pass_ce(codes, labels, reduction)
+            self._opt.second_step(zero_grad=True)
+        else:
+            self._opt.step()
+        return loss, stats
+
+    def _cpu_pass_ce(self, codes, labels, reduction):
+        grads, (conf, wsum, nll, smooth, n_bad), loss = torch_ce_loss_grad(self._model, codes, labels, self.class_weight,
+                                                                             self.label_smoothing, reduction)
+        for p, g in zip(_params(self._model), grads):
+            p.grad = g.detach().clone()
+        row = torch.zeros((1, L.CE_STATS_K), dtype=torch.float64)
+        no = conf.shape[0]
+        for l in range(no):
+            for q in range(no):
+                row[0, l * 4 + q] = float(conf[l, q])
+        row[0, L.CE_WEIGHT_SUM], row[0, L.CE_NLL_SUM], row[0, L.CE_SMOOTH_SUM], row[0, L.CE_N_BAD] = wsum, nll, smooth, n_bad
+        return torch.tensor([loss], dtype=torch.float64), row
 
     def _cpu_pass(self, codes, mask, target, pos_weight, reduction):
         grads, (tp, fp, fn, tn, loss_sum) = torch_loss_grad(self._model, codes, mask, target, pos_weight, reduction)

@@ -576,6 +576,60 @@ int vqae_classifier_optim_export(vqae_classifier_optim* opt, float* exp_avg, flo
 int vqae_classifier_optim_import(vqae_classifier_optim* opt, const float* exp_avg, const float* exp_avg_sq, int64_t step,
                                  void* stream);
 
+/* ---- Multi-class (n_out = 2 .. 4): replaces torch.nn.CrossEntropyLoss(weight, label_smoothing, reduction) as loss_f of
+ * CNNClassifier.step (validation_nn/model.py:131-139; conf/model/loss_f/cross_entropy.yaml, with the weights and smoothing of
+ * conf/model/optional_overrides/loss_f/cross_entropy_camelyon16_embeddings.yaml), over logits [B][n_out][h][w] and the stored
+ * mask bytes as class indices [B][h][w] (datamodules/camelyon16.py:259 casts them for the loss; out_conv's channels are
+ * [background, tissue, cancer], cnn_classifier.yaml).  There is no ignore_index.  Per position with label y, p = softmax(x):
+ *   nll = w[y] * -log p_y,   smooth = sum_c w[c] * -log p_c,
+ *   loss_sum = (1 - eps) * sum nll + (eps / n_out) * sum smooth;   'mean' divides by sum w[y] over the whole batch;
+ *   dL/dx_k = (1 - eps) * w[y] * (p_k - [k == y]) + (eps / n_out) * (W * p_k - w_k),   W = sum_c w_c.
+ * The log-softmax is taken in fp32 on the max-subtracted logits, the sums in fp64.  A position whose label is >= n_out is
+ * counted aside and contributes to nothing else (zero gradient).  The n_out == 1 entry points above are unchanged and keep
+ * refusing n_out != 1; these refuse n_out == 1. ---- */
+/* Columns of a cross-entropy stats row: 0 .. 15 the confusion counts at [label * 4 + prediction] over the positions with
+ * label < n_out (exact integers held in doubles, unused cells 0; prediction = argmax, lowest index on ties), then
+ * sum w[y], sum nll, sum smooth, and the number of positions with label >= n_out. */
+enum { VQAE_CE_CONFUSION = 0, VQAE_CE_WEIGHT_SUM = 16, VQAE_CE_NLL_SUM = 17, VQAE_CE_SMOOTH_SUM = 18, VQAE_CE_N_BAD = 19,
+       VQAE_CE_STATS_K = 20 };
+/* Bytes of scratch vqae_classifier_forward_ce needs with stats (0 for an empty batch, a bad shape or n_out == 1). */
+size_t vqae_classifier_ce_workspace_bytes(const vqae_classifier* c, int batch, int h, int w);
+/* CNNClassifier.forward (validation_nn/model.py:141-142) and the scores of CNNClassifier.step with the cross-entropy loss on
+ * codes_dev [B][h][w], one launch.  Each output is optional, at least one is required:
+ *   logits_dev    fp32 [B][n_out][h][w];
+ *   prob_u8_dev   uint8 [B][n_out][h][w] = rintf(255 * softmax(logits));
+ *   class_u8_dev  uint8 [B][h][w] = argmax over the classes, the lowest index on ties (torch.argmax);
+ *   stats_dev     double [B][VQAE_CE_STATS_K] over labels_dev uint8 [B][h][w] with `weight` (HOST float [n_out], null = ones)
+ *                 and label_smoothing; needs workspace_dev of vqae_classifier_ce_workspace_bytes bytes.  Reduced as
+ *                 vqae_classifier_forward's rows are: bit-identical run to run and at any batch position.
+ * The raw counts are the loss's; the `out[:, 0][labels == 0] = inf` of validation_nn/model.py:103 (row 0 of the confusion
+ * matrix collapses into column 0) is the caller's, from these counts.
+ * Errors, all before any HIP call: null c / codes, no output at all, stats without labels or without the workspace, a bad
+ * idx_dtype, h < 1 or w < 1, batch < 0, a negative or non-finite weight, label_smoothing outside [0, 1] ->
+ * VQAE_ERR_INVALID; n_out == 1, batch > 65535 -> VQAE_ERR_UNSUPPORTED; batch == 0 -> VQAE_OK. */
+int vqae_classifier_forward_ce(vqae_classifier* c, const void* codes_dev, int idx_dtype, int batch, int h, int w,
+                               float* logits_dev, uint8_t* prob_u8_dev, uint8_t* class_u8_dev, const uint8_t* labels_dev,
+                               const float* weight, float label_smoothing, double* stats_dev, void* workspace_dev, void* stream);
+/* Bytes of scratch vqae_classifier_loss_grad_ce needs: as vqae_classifier_train_workspace_bytes, with dL/dlogit at
+ * 4 * n_out bytes per code.  0 for an empty batch, a bad shape or n_out == 1. */
+size_t vqae_classifier_ce_train_workspace_bytes(const vqae_classifier* c, int batch, int h, int w);
+/* Loss and gradients of the cross-entropy step (validation_nn/model.py:131-139 with loss_f = nn.CrossEntropyLoss and the
+ * backward() autograd runs over both): the forward launch above storing dL/dlogit, then vqae_classifier_loss_grad's backward
+ * with n_out planes of it.  reduction 0 = 'sum', 1 = 'mean' (loss and gradients times 1 / sum w[y] of the whole batch, applied
+ * once, in fp64; a zero weight sum gives a nan loss and zero gradients).  Outputs as vqae_classifier_loss_grad's: grads_dev
+ * double [vqae_classifier_grad_floats(c)] packed as described there, stats_dev double [B][VQAE_CE_STATS_K] exactly
+ * vqae_classifier_forward_ce's rows, loss_dev double [1].  Border rule, sums and determinism as there.
+ * Errors, all before any HIP call: null c / codes / labels / grads / stats / loss / workspace, a bad idx_dtype, h < 1 or
+ * w < 1, batch < 0, a negative or non-finite weight, label_smoothing outside [0, 1], a reduction other than 0 or 1 ->
+ * VQAE_ERR_INVALID; n_out == 1, batch > 65535 -> VQAE_ERR_UNSUPPORTED.  batch == 0 -> VQAE_OK with zero gradients and loss. */
+int vqae_classifier_loss_grad_ce(vqae_classifier* c, const void* codes_dev, int idx_dtype, int batch, int h, int w,
+                                 const uint8_t* labels_dev, const float* weight, float label_smoothing, int reduction,
+                                 double* grads_dev, double* stats_dev, double* loss_dev, void* workspace_dev, void* stream);
+/* vqae_classifier_optim_create for a classifier with n_out = 2 .. 4 (the optimizer.step() after the cross-entropy step): the
+ * same optimiser, state and checks; every other vqae_classifier_optim_* call takes its handle.  out_conv's weight and bias
+ * are tensors of their own for LAMB's norms at any n_out.  n_out == 1 -> VQAE_ERR_UNSUPPORTED. */
+int vqae_classifier_optim_create_ce(vqae_classifier* c, const vqae_classifier_optim_config* cfg, vqae_classifier_optim** out);
+
 /* ---------------------------------------------------------------------------------------------
  * 7. Counts of stored code grids -- produces what the reference commits as data under scripts/create_wsi_histograms/
  *    (embedding_idx_histogram_{K}_{split}.npy, histogram_{split}.npy; it ships no program for them) and reads its loss
