@@ -186,4 +186,9 @@ int vq_loss_from_idx(const float* z, const float* embed, const int* idx32, int64
                      float* loss, hipStream_t stream);
 int vq_write_idx(const int* idx32, int64_t N, void* out, int idx_dtype, hipStream_t stream);
 
+// ---- vq_backward.hip ---------------------------------------------------------------------------
+// The backward of both quantisers (vqae_vq_backward_f32, vqae_vq_projected_backward_f32 and its workspace size): C ABI
+// only, include/vqae_hip.h.  Rows per workgroup and the number of fp64 partial rows are functions of n_rows alone
+// (bw_grid there), which is what makes the gradients bit-identical run to run.
+
 }  // namespace vqae

@@ -233,6 +233,45 @@ def vq_projected(x_flat, proj_in_w, proj_in_b, embed, proj_out_w, proj_out_b, co
     return out, idx, loss, z, margin
 
 
+def vq_backward(g_q, z_flat, q_flat, g_loss, commitment_cost):
+    """g_z = g_q + g_loss * commitment_cost * 2 / (N * D) * (z - q) on [N, D] rows (the backward of vq.py:143-146).  g_q [N, D] or
+    None, g_loss a 0-d fp32 device tensor or None (either None: a zero upstream gradient); g_loss is never read back."""
+    _need_gpu(g_q, z_flat, q_flat, g_loss)
+    z_flat, q_flat = z_flat.contiguous(), q_flat.contiguous()
+    N, D = z_flat.shape
+    g_q = g_q.contiguous().float() if g_q is not None else None
+    g_loss = g_loss.reshape(()).float().contiguous() if g_loss is not None else None
+    g_z = torch.empty_like(z_flat)
+    L.check(L.lib().vqae_vq_backward_f32(_p(g_q), _p(z_flat), _p(q_flat), _p(g_loss), float(commitment_cost), N, D, _p(g_z),
+                                         _stream()))
+    return g_z
+
+
+def vq_projected_backward(g_out, x_flat, z, q, g_loss, proj_in_w, proj_out_w, commitment_cost=1.0,
+                          want=(True, True, True, True, True)):
+    """All five gradients of ProjectedEMAVectorQuantizer2d.forward (projection_dim 8) in one pass over g_out [N, C] and
+    x_flat [N, C]: -> (g_x [N, C], g_w_in [8, C], g_b_in [8], g_w_out [C, 8], g_b_out [C]), None where `want` is False.
+    z, q [N, 8] as the forward saved them; g_out / g_loss may be None (zero); proj_in_w [8, C(,1,1)], proj_out_w
+    [C, 8(,1,1)] as PyTorch stores them.  Bit-identical run to run."""
+    _need_gpu(g_out, x_flat, z, q, g_loss, proj_in_w, proj_out_w)
+    x_flat, z, q = x_flat.contiguous(), z.contiguous(), q.contiguous()
+    N, C = x_flat.shape
+    D = z.shape[1]
+    dev = x_flat.device
+    g_out = g_out.contiguous().float() if g_out is not None else None
+    g_loss = g_loss.reshape(()).float().contiguous() if g_loss is not None else None
+    wt_in = proj_in_w.reshape(D, C).float().t().contiguous()
+    w_out = proj_out_w.reshape(C, D).float().contiguous()
+    new = lambda on, *shape: torch.empty(shape, dtype=torch.float32, device=dev) if on else None
+    g_x, g_w_in, g_b_in, g_w_out, g_b_out = (new(want[0], N, C), new(want[1], D, C), new(want[2], D), new(want[3], C, D),
+                                             new(want[4], C))
+    ws = torch.empty(L.lib().vqae_vq_projected_backward_workspace_bytes(N, C), dtype=torch.uint8, device=dev)
+    L.check(L.lib().vqae_vq_projected_backward_f32(_p(g_out), _p(x_flat), _p(z), _p(q), _p(g_loss), _p(wt_in), _p(w_out), N, C, D,
+                                                   float(commitment_cost), _p(g_x), _p(g_w_in), _p(g_b_in), _p(g_w_out),
+                                                   _p(g_b_out), _p(ws), _stream()))
+    return g_x, g_w_in, g_b_in, g_w_out, g_b_out
+
+
 def embed_code(idx, embed):
     _need_gpu(idx, embed)
     idx = idx.contiguous()

@@ -105,6 +105,42 @@ int vqae_vq_projected_f32(const float* x_dev, const float* wt_in_dev, const floa
                           int n_codes, float commitment_cost, int dtype, void* idx_dev, int idx_dtype, float* out_dev,
                           float* z_dev, float* loss_dev, float* margin_dev, void* workspace_dev, void* stream);
 
+/* Backward of EMAVectorQuantizer.forward (vq.py:143-146): the gradient autograd gives `inputs` through
+ *   loss = commitment_cost * mse_loss(inputs, quantized) (vq.py:143) and quantized = inputs + (quantized - inputs).detach()
+ *   (vq.py:146), on the channel-last rows of vq.py:107-116:
+ *   g_z[n][c] = g_q[n][c] + g_loss * commitment_cost * 2 / (n_rows * dim) * (z[n][c] - q[n][c]).
+ *   g_q_dev    [n_rows][dim] incoming gradient of the first output, or NULL (zero)
+ *   z_dev, q_dev [n_rows][dim] the forward's rows and its lookup (the q of the PRE-update codebook in training mode)
+ *   g_loss_dev one fp32 ON THE DEVICE, the incoming gradient of the loss, or NULL (zero; z / q are then not read):
+ *              the kernel forms the scale itself, so no value is read back and nothing synchronises
+ *   g_z_dev    [n_rows][dim]; may alias g_q_dev.   dim: any 1 .. 4096.  n_rows == 0 -> VQAE_OK. */
+int vqae_vq_backward_f32(const float* g_q_dev, const float* z_dev, const float* q_dev, const float* g_loss_dev,
+                         float commitment_cost, int64_t n_rows, int dim, float* g_z_dev, void* stream);
+
+/* Backward of ProjectedEMAVectorQuantizer2d.forward (vq.py:190-192 around vq.py:143-146), projection_dim = 8, in one pass
+ * over g_out and x (each read once, g_x written once):
+ *   g_q = g_out W_out                      g_W_out = g_out^T q    [channels][8]     g_b_out = sum_n g_out  [channels]
+ *   g_z = g_q + g_loss cc 2 / (8 n_rows) (z - q)    g_W_in = g_z^T x  [8][channels]     g_b_in  = sum_n g_z    [8]
+ *   g_x = g_z W_in
+ *   g_out_dev  [n_rows][channels] incoming gradient of the output (NHWC rows), or NULL (zero)
+ *   x_dev [n_rows][channels], z_dev [n_rows][8] = proj_in(x), q_dev [n_rows][8]: saved by the forward
+ *   g_loss_dev one fp32 on the device or NULL, as vqae_vq_backward_f32
+ *   wt_in_dev [channels][8] proj_in.weight TRANSPOSED, w_out_dev [channels][8] proj_out.weight as stored
+ *     (the layouts of vqae_vq_projected_f32)
+ *   g_x_dev [n_rows][channels], g_w_in_dev [8][channels], g_b_in_dev [8], g_w_out_dev [channels][8], g_b_out_dev [channels]:
+ *     each may be NULL (not written)
+ *   workspace_dev: vqae_vq_projected_backward_workspace_bytes(n_rows, channels) bytes.
+ * The three sums over n_rows are accumulated in fp64 per workgroup, written to the workspace and added in index order by a
+ * second launch; the grid is a function of the shapes alone and there are no floating-point atomics: bit-identical run to
+ * run.  n_rows == 0 writes zeros.
+ * Errors: projection_dim != 8, channels % 4 != 0, channels > 256 -> VQAE_ERR_UNSUPPORTED. */
+size_t vqae_vq_projected_backward_workspace_bytes(int64_t n_rows, int channels);
+int vqae_vq_projected_backward_f32(const float* g_out_dev, const float* x_dev, const float* z_dev, const float* q_dev,
+                                   const float* g_loss_dev, const float* wt_in_dev, const float* w_out_dev, int64_t n_rows,
+                                   int channels, int projection_dim, float commitment_cost, float* g_x_dev,
+                                   float* g_w_in_dev, float* g_b_in_dev, float* g_w_out_dev, float* g_b_out_dev,
+                                   void* workspace_dev, void* stream);
+
 /* out[n][:] = embed[idx[n]][:]   (embed_code, vq.py:44-45 = F.embedding) */
 int vqae_embed_code_f32(const void* idx_dev, int idx_dtype, const float* embed_dev, int64_t n_rows, int n_codes,
                         int dim, float* out_dev, void* stream);
