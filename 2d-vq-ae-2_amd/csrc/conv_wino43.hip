@@ -27,6 +27,13 @@
 // operand as three bf16 pieces and six of their nine products.
 // The same kernel serves the level above the trunk (C = 64 on the 64-wide grid: 2 slices x 2 tile groups) and C = 256 on the code
 // grid (8 slices, 512 threads, one workgroup per CU).
+// Wide form (WIDE: the split form at C = 128 when H % 16 == 0): one 512-thread workgroup per CU owns 16 image rows = two 8-row bands =
+// 32 tiles.  Wave cb = 0..7 owns ONE 16-channel block and both bands: the block index of Y / Z / acc becomes the band index, and every
+// weight fragment a wave loads (one per plane and chunk: 16 registers double-buffered, where the 8-row form has 32 single-buffered for
+// two blocks) feeds both bands' V fragments, so the weight stream per CU and position is 96 KiB instead of 2 x 96 KiB.  Every
+// accumulator sees the MFMAs of the 8-row form in their order: the results are that form's bit for bit (tests/test_wino43_wide_gpu.py).
+// V is [nu][32 tiles][3 C + 8] bf16 = 150 528 B, T [256 px][132] fp32 overlays it; both exceed the 64 KiB a DS offset field
+// reaches, hence the second, opaque bases.  H % 8 == 0 only, VQAE_W43_SPLIT=0, C = 64 and C = 256 keep the 8-row kernels.
 #include "kernels.h"
 #include "mfma.h"
 
@@ -50,16 +57,20 @@ struct W43K {
 };
 
 // (C, grid width): (256, 32) [512 threads, one workgroup per CU], (128, 32), (64, 64): 8 image rows x the whole grid width
-template <int C_> struct W43Cfg {
+// WIDE (C = 128, split form, H % 16 == 0): 512 threads own two 8-row bands, 16 image rows x 32 columns, one workgroup per CU
+template <int C_, bool WIDE_ = false> struct W43Cfg {
     static constexpr int C = C_;
+    static constexpr bool WIDE = WIDE_;
+    static constexpr int BANDS = WIDE ? 2 : 1;          // 8-row bands of a workgroup
+    static constexpr int ROWS = 8 * BANDS;
     static constexpr int W = C >= 128 ? 32 : 64;
-    static constexpr int NT = C == 256 ? 512 : 256;
+    static constexpr int NT = (C == 256 || WIDE) ? 512 : 256;
     static constexpr int NWV = NT / 64;
     static constexpr int NS = C / 32;                  // 32-channel slices
-    static constexpr int TG = NWV / NS;                // 16-tile groups (a wave = one slice x one group)
-    static constexpr int TILES = 16 * TG;              // = 2 tile rows x W / 4 tile columns
+    static constexpr int TG = NWV / NS;                // 16-tile groups (a wave = one slice x one group; WIDE: the two bands)
+    static constexpr int TILES = 16 * TG;              // = 2 tile rows x W / 4 tile columns per band
     static constexpr int TC = W / 4;
-    static constexpr int PXH = 4 * W;                  // pixels of one half (4 of the 8 rows)
+    static constexpr int PXH = 4 * W * BANDS;          // pixels of one half (4 of the 8 rows of every band)
     static constexpr int C4 = C / 4;
     static constexpr int RP = NT / C4;                 // pixels one sweep of the workgroup's threads covers (= TC)
     static constexpr int LDT = C + 4;
@@ -74,7 +85,8 @@ template <int C_> struct W43Cfg {
     static constexpr int LDVB = 3 * C + 8, KC = C / 32, KS2 = C / 16;
     static constexpr int VS_BYTES = 6 * TILES * LDVB * 2;
     static constexpr int LDS_SPLIT = VS_BYTES > T_BYTES ? VS_BYTES : T_BYTES;
-    static_assert(TILES == 2 * TC && RP == TC && PXH / RP == 16 && MI * NI == 4, "geometry");
+    static_assert(TILES == 2 * TC * BANDS && RP == TC * BANDS && PXH / RP == 16 && MI * NI == 4, "geometry");
+    static_assert(!WIDE || C == 128, "the wide form serves C = 128");
 };
 constexpr int EARLY = 1;                             // input batches of the next pass requested before the fold over xi (0, 1, 2)
 constexpr int RD = 4;                                // weight-fragment ring depth (k-groups of 8 MFMAs = 256 MFMA cycles each)
@@ -105,10 +117,17 @@ __device__ __forceinline__ f32x4 ldg(const float* sbase, unsigned voff_bytes) {
 
 template <int N> struct IC { static constexpr int value = N; };
 
-template <int C, int TAIL, bool SPLIT>
-__global__ __launch_bounds__((W43Cfg<C>::NT), (W43Cfg<C>::NT == 512 ? 1 : 2))
+// image row (relative to the workgroup's first row of the half) of row r of T: band r / 4, rows {0, 1, 4, 5} of its 8.  Used by the wide
+// form only: the 8-row forms spell 4 (r >> 1) + (r & 1) out in place, because routing that one expression through a function, even an
+// inlined one with the same text, changes hipcc's address arithmetic around it (a few dozen instructions per kernel), and those kernels
+// are to stay what they were, instruction for instruction.
+constexpr int tail_row(int r) { return 8 * (r >> 2) + 4 * ((r >> 1) & 1) + (r & 1); }
+
+template <int C, int TAIL, bool SPLIT, bool WIDE = false>
+__global__ __launch_bounds__((W43Cfg<C, WIDE>::NT), (W43Cfg<C, WIDE>::NT == 512 ? 1 : 2))
 void wino43_trunk_kernel(const W43K p) {
-    using K = W43Cfg<C>;
+    using K = W43Cfg<C, WIDE>;
+    static_assert(!WIDE || SPLIT, "the wide form is a split form");
     constexpr int W = K::W, LDT = K::LDT, KG = K::KG, KS = K::KS, TILES = K::TILES, TC = K::TC, NS = K::NS, C4 = K::C4, RP = K::RP;
     constexpr int MI = K::MI, NI = K::NI, WN = K::WN;
     constexpr int LDVB = K::LDVB, KC = K::KC, KS2 = K::KS2;
@@ -117,7 +136,8 @@ void wino43_trunk_kernel(const W43K p) {
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, q = lane >> 4;                         // main phase: tile of the group, channel quad of the 16-channel block
-    const int ns = wave % NS, tg = wave / NS;                        // main phase: 32-channel slice, 16-tile group
+    // main phase: 32-channel slice, 16-tile group.  WIDE: wave = 16-channel block cb of slice cb >> 1, both bands (16 tiles each)
+    const int ns = WIDE ? wave >> 1 : wave % NS, tg = WIDE ? 0 : wave / NS;
 
     int tile_m;                                                      // XCD-contiguous order (conv_wino.hip)
     {
@@ -125,22 +145,24 @@ void wino43_trunk_kernel(const W43K p) {
         const int qq = nwg >> 3, r = nwg & 7, xcd = bid & 7;
         tile_m = (xcd < r ? xcd * (qq + 1) : r * (qq + 1) + (xcd - r) * qq) + (bid >> 3);
     }
-    const int tpi = p.H / 8;
+    const int tpi = p.H / K::ROWS;
     const int img = tile_m / tpi;
-    const int row0 = 8 * (tile_m - img * tpi);
+    const int row0 = K::ROWS * (tile_m - img * tpi);
     const float* const xim = p.t1 + (int64_t)img * p.H * W * C;
 
     // ---- transform geometry: thread -> channel quad cg, tile column tj, both tile rows ------------------------------------
+    // (WIDE: tj = 8 band + tile column; the band is uniform per wave, and its halo rows may lie in the other band or workgroup)
     const int cg = tid % C4, tj = tid / C4;
+    const int tjc = WIDE ? tj & (TC - 1) : tj, band = WIDE ? wave >> 2 : 0;
     unsigned coff[6];                                                // per-lane byte offsets of the unit's 6 columns
     int roff[2][6];                                                  // uniform float offsets of its 6 rows
 #pragma unroll
-    for (int j = 0; j < 6; ++j) coff[j] = (unsigned)((((4 * tj - 1 + j) & (W - 1)) * C + 4 * cg) * 4);
+    for (int j = 0; j < 6; ++j) coff[j] = (unsigned)((((4 * tjc - 1 + j) & (W - 1)) * C + 4 * cg) * 4);
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
-            int r = row0 + 4 * s - 1 + i;
+            int r = row0 + 8 * band + 4 * s - 1 + i;
             r = r < 0 ? r + p.H : (r >= p.H ? r - p.H : r);
             roff[s][i] = r * W * C;
         }
@@ -168,14 +190,21 @@ void wino43_trunk_kernel(const W43K p) {
         }
     };
     auto columns = [&](int s) __attribute__((always_inline)) {                                      // (w B)[nu] -> V[nu][tile][c]
-        float* const dst = lds + (s * TC + tj) * LDT + 4 * cg;
-        __bf16* const dsb = reinterpret_cast<__bf16*>(lds) + (s * TC + tj) * LDVB + 4 * cg;
+        float* const dst = lds + (16 * band + s * TC + tjc) * LDT + 4 * cg;
+        __bf16* const dsb = reinterpret_cast<__bf16*>(lds) + (16 * band + s * TC + tjc) * LDVB + 4 * cg;
+        // WIDE: V spans 147 KiB and a DS instruction's offset field 64 KiB, so nu = 3..5 go through a second base, opaque so that
+        // hipcc forms it once per use instead of keeping (and spilling) one address per access
+        int vhi = 3 * TILES * LDVB;
+        if constexpr (WIDE) asm volatile("" : "+v"(vhi));
         auto put = [&](int nu, const f32x4& v) __attribute__((always_inline)) {
             if constexpr (SPLIT) {                                    // split once here, not after every wave's ds_read
                 bf16x4 h[3];
                 split3(v, h);
 #pragma unroll
-                for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<bf16x4*>(dsb + nu * TILES * LDVB + pl * C) = h[pl];
+                for (int pl = 0; pl < 3; ++pl) {
+                    if (WIDE && nu >= 3) *reinterpret_cast<bf16x4*>(dsb + vhi + (nu - 3) * TILES * LDVB + pl * C) = h[pl];
+                    else *reinterpret_cast<bf16x4*>(dsb + nu * TILES * LDVB + pl * C) = h[pl];
+                }
             } else {
                 *reinterpret_cast<f32x4*>(dst + nu * TILES * LDT) = v;
             }
@@ -192,7 +221,8 @@ void wino43_trunk_kernel(const W43K p) {
 
     // weights: this wave's 16 KiB of a position are contiguous ([k-group][block][lane][4]); positions C * C floats apart
     const float* const ub = p.U + ns * (KG * 512);                   // uniform; + 16 lane bytes per lane
-    const float* const ubs = p.Us + ns * (KC * 1536);                // split form: this wave's 24 KiB of a position
+    // split form: this wave's 24 KiB of a position (WIDE: the 12 KiB of its 16-channel block, 768 floats into every chunk)
+    const float* const ubs = p.Us + ns * (KC * 1536) + (WIDE ? 768 * (wave & 1) : 0);
     const __bf16* const vbs = reinterpret_cast<const __bf16*>(lds) + (16 * tg + li) * LDVB + 8 * q;   // split V fragment base
     const unsigned wl = 16u * lane;
     const float* const bfrag = lds + (16 * tg + li) * LDT + 4 * q;  // V fragment base, + nu * TILES * LDT + 16 kg
@@ -241,7 +271,62 @@ void wino43_trunk_kernel(const W43K p) {
             if (nu == 0 || nu == 2 || nu == 4)
                 asm volatile("" : "+v"(Z[0][0]), "+v"(Z[0][1]), "+v"(Z[1][0]), "+v"(Z[1][1]), "+v"(Z[2][0]), "+v"(Z[2][1]), "+v"(Z[3][0]), "+v"(Z[3][1]));
         };
-        if constexpr (SPLIT) {
+        if constexpr (WIDE) {
+            // Wide form: the split walk below with the band in place of the 16-channel block -- per 32-channel chunk one fragment
+            // per plane (16 registers) feeds both bands' V fragments (24 registers); every accumulator sees the MFMAs of the
+            // 8-row form in their order.
+            int64_t uoff = (int64_t)xi * 6 * (3 * C * C / 2);
+            asm volatile("" : "+s"(uoff));
+            const float* const ux = ubs + uoff;
+#define WS(s, pl) (((s) / KC) * (3 * C * C / 2) + 1536 * ((s) % KC) + 256 * (pl))
+            // (nu = 3..5 through a second, opaque base: see columns())
+            int vhi = 3 * TILES * LDVB;
+            asm volatile("" : "+v"(vhi));
+            const __bf16* const vbh = vbs + vhi;
+#define VB(s, g, pl) (*reinterpret_cast<const bf16x8*>(((s) / KC >= 3 ? vbh - 3 * TILES * LDVB : vbs) + ((s) / KC) * TILES * LDVB + (g) * 16 * LDVB + (pl) * C + 32 * ((s) % KC)))
+            f32x4 w0[2], w1[2], w2[2];                                   // [slot]: every plane two chunks ahead
+            w1[0] = ldg(ux + WS(0, 1), wl);
+            w2[0] = ldg(ux + WS(0, 2), wl);
+            w0[0] = ldg(ux + WS(0, 0), wl);
+            w1[1] = ldg(ux + WS(1, 1), wl);
+            w2[1] = ldg(ux + WS(1, 2), wl);
+            w0[1] = ldg(ux + WS(1, 0), wl);
+            lds_barrier();                                               // V complete
+#pragma unroll
+            for (int b = 0; b < 4; ++b) { Z[b][0] = f32x4{0.f, 0.f, 0.f, 0.f}; Z[b][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+            bf16x8 vb0[2], vb1[2], vb2[2];                               // [band]
+#pragma unroll
+            for (int g = 0; g < 2; ++g) { vb0[g] = VB(0, g, 0); vb1[g] = VB(0, g, 1); vb2[g] = VB(0, g, 2); }
+#pragma unroll
+            for (int nu = 0; nu < 6; ++nu) {
+                const int st = nu & 1;
+                acc[st][0] = f32x4{0.f, 0.f, 0.f, 0.f};
+                acc[st][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int kc = 0; kc < KC; ++kc) {
+                    const int s = KC * nu + kc, sl = s & 1;
+                    const bool nxt = s + 1 < 6 * KC;
+#define MM(wa, vb) for (int g = 0; g < 2; ++g) acc[st][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf8(wa), vb[g], acc[st][g], 0, 0, 0)
+                    MM(w1[sl], vb1);                                     // a1 b1
+                    MM(w1[sl], vb0);                                     // a1 b0
+                    if (s + 2 < 6 * KC) w1[sl] = ldg(ux + WS(s + 2, 1), wl);
+                    MM(w2[sl], vb0);                                     // a2 b0
+                    if (s + 2 < 6 * KC) w2[sl] = ldg(ux + WS(s + 2, 2), wl);
+                    MM(w0[sl], vb2);                                     // a0 b2
+                    if (nxt) for (int g = 0; g < 2; ++g) vb2[g] = VB(s + 1, g, 2);
+                    MM(w0[sl], vb1);                                     // a0 b1
+                    if (nxt) for (int g = 0; g < 2; ++g) vb1[g] = VB(s + 1, g, 1);
+                    MM(w0[sl], vb0);                                     // a0 b0
+                    if (s + 2 < 6 * KC) w0[sl] = ldg(ux + WS(s + 2, 0), wl);
+                    if (nxt) for (int g = 0; g < 2; ++g) vb0[g] = VB(s + 1, g, 0);
+#undef MM
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                fold_nu(nu);
+            }
+#undef WS
+#undef VB
+        } else if constexpr (SPLIT) {
             // Split form: per 32-channel chunk, six v_mfma_f32_16x16x32_bf16 per block (96 cycles) replace 16 v_mfma_f32_16x16x4_f32
             // (256 cycles).  Registers allow 32 for weights (Y, Z and the accumulators hold 176): the hi plane is double-buffered, mid and
             // lo are used first in each chunk and re-requested for the next one right after their last use; the V planes likewise.
@@ -380,11 +465,12 @@ void wino43_trunk_kernel(const W43K p) {
     pass(IC<5>{}, IC<-1>{}, 5, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f);
 
     // ---- tails on two 128-pixel halves: half hf = output rows 2 hf, 2 hf + 1 of every tile = image rows row0 + {0, 1, 4, 5} + 2 hf ----
+    // (WIDE: 256-pixel halves, band 0's 128 pixels then band 1's; the wave tiling is the same with four waves along the pixels)
     float* const T = lds;
     const int li32 = lane & 31, hh = lane >> 5;                      // 32x32x2 layout of the tails
     const int wm = wave / WN, wn = wave % WN;                        // MI * 32 pixels x NI * 32 channels per wave
     const int tj0 = tj;                                              // row-coalesced view: thread (cg, tj0) owns pixels tj0 + RP i of the half
-    float* const trow = T + tj0 * LDT + 4 * cg;
+    [[maybe_unused]] float* const trow = WIDE ? nullptr : T + tj0 * LDT + 4 * cg;   // 8-row forms; WIDE: tr() below
     const int ty = (16 * tg + li) / TC, tx = (16 * tg + li) % TC;
     f32x4 bt[RT][NI];
     f32x4 bs0[2][NI], bs1[NI], bs2[NI];                              // split form: the hi plane of two k-slices, mid / lo of one
@@ -497,6 +583,16 @@ void wino43_trunk_kernel(const W43K p) {
 
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf) {
+        // WIDE: T spans 132 KiB (a DS offset field: 64 KiB), so band 1 / the sweeps i >= 8 go through second bases, opaque per half so
+        // that hipcc neither forms one address per access nor keeps them from one half to the next
+        int tbo = (2 * ty * W + 4 * tx) * LDT + 16 * wave + 4 * q, tro = tj0 * LDT + 4 * cg;
+        if constexpr (WIDE) asm volatile("" : "+v"(tbo), "+v"(tro));
+        int tbo1 = tbo + 4 * W * LDT, tro1 = tro + 8 * RP * LDT;
+        if constexpr (WIDE) asm volatile("" : "+v"(tbo1), "+v"(tro1));
+        auto tr = [&](int i) __attribute__((always_inline)) {
+            if constexpr (WIDE) return reinterpret_cast<f32x4*>(T + (i < 8 ? tro + RP * i * LDT : tro1 + RP * (i - 8) * LDT));
+            else return reinterpret_cast<f32x4*>(trow + RP * i * LDT);
+        };
         // t2 = ELU(conv2 + b3a) + b3b -> T[pixel][channel]; T row r' <-> image row row0 + 4 (r' >> 1) + 2 hf + (r' & 1)
 #pragma unroll
         for (int a2 = 0; a2 < 2; ++a2)
@@ -507,22 +603,43 @@ void wino43_trunk_kernel(const W43K p) {
                     f32x4 o;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) o[e] = elu_act(Y[2 * hf + a2][b][bl][e] + p.act_a) + p.act_b;
-                    *reinterpret_cast<f32x4*>(T + ((2 * ty + a2) * W + 4 * tx + b) * LDT + 32 * ns + 16 * bl + 4 * q) = o;
+                    if constexpr (WIDE) *reinterpret_cast<f32x4*>(T + (bl ? tbo1 : tbo) + (a2 * W + b) * LDT) = o;
+                    else *reinterpret_cast<f32x4*>(T + ((2 * ty + a2) * W + 4 * tx + b) * LDT + 32 * ns + 16 * bl + 4 * q) = o;
                 }
         tail_prefetch(SPLIT ? p.w3s : p.w3);
-        const int64_t pixb = ((int64_t)img * p.H + row0 + 2 * hf) * W + tj0;
-        float* xr[4];
+        // pixel (i) of the thread in the residual stream / the next t1.  8-row forms: one pointer per row of the half.  WIDE: eight row
+        // pointers per half do not fit the registers; a uniform row base + one per-lane offset (as ldg) instead
+        [[maybe_unused]] float* xr[WIDE ? 1 : K::PXH / W];
+        [[maybe_unused]] int64_t xu = 0;
+        [[maybe_unused]] unsigned xvo = 0;
+        if constexpr (WIDE) {
+            xu = (((int64_t)img * p.H + row0 + 2 * hf) * W) * C;
+            xvo = (unsigned)((tj0 * C + 4 * cg) * 4);
+            asm volatile("" : "+v"(xvo));
+        } else {
+            const int64_t pixb = ((int64_t)img * p.H + row0 + 2 * hf) * W + tj0;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) xr[r] = p.xio + (pixb + (int64_t)(4 * (r >> 1) + (r & 1)) * W) * C + 4 * cg;
+            for (int r = 0; r < K::PXH / W; ++r) xr[r] = p.xio + (pixb + (int64_t)(4 * (r >> 1) + (r & 1)) * W) * C + 4 * cg;
+        }
+        auto xp = [&](float* base, int i) __attribute__((always_inline)) {
+            const int r = (RP * i) / W;
+            if constexpr (WIDE) {
+                int64_t ro = xu + (tail_row(r) * W + (RP * i) % W) * C;
+                asm volatile("" : "+s"(ro));                          // stays a scalar base: no 64-bit per-lane address per row
+                return reinterpret_cast<f32x4*>(reinterpret_cast<char*>(base + ro) + xvo);
+            } else {
+                return reinterpret_cast<f32x4*>(xr[r] + ((RP * i) % W) * C);
+            }
+        };
         // residual rows: requested ahead of conv3 -- in the first half only half of them (the second half's Y is still live: registers)
         f32x4 res[16];
 #pragma unroll
-        for (int i = 0; i < (hf == 0 ? NRES0 : 16); ++i) res[i] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(xr[(RP * i) / W] + ((RP * i) % W) * C));
+        for (int i = 0; i < (hf == 0 ? NRES0 : 16); ++i) res[i] = __builtin_nontemporal_load(xp(p.xio, i));
         lds_barrier();                                               // t2 complete
         gemm_tail(SPLIT ? p.w3s : p.w3);                             // conv3
         if (hf == 0) {
 #pragma unroll
-            for (int i = NRES0; i < 16; ++i) res[i] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(xr[(RP * i) / W] + ((RP * i) % W) * C));
+            for (int i = NRES0; i < 16; ++i) res[i] = __builtin_nontemporal_load(xp(p.xio, i));
         }
         if (TAIL == 2) tail_prefetch(SPLIT ? p.w1ns : p.w1n);
         lds_barrier();                                               // every wave is done reading t2
@@ -531,15 +648,15 @@ void wino43_trunk_kernel(const W43K p) {
         // out = conv3 * scale + bias4 + x, in place over the residual stream, whole pixel rows per 8th of a workgroup
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            f32x4 t = *reinterpret_cast<const f32x4*>(trow + RP * i * LDT);
+            f32x4 t = *tr(i);
             t = t * p.t_scale;
             t = t + p.t_b4;
             t = t + res[i];
-            __builtin_nontemporal_store(t, reinterpret_cast<f32x4*>(xr[(RP * i) / W] + ((RP * i) % W) * C));
+            __builtin_nontemporal_store(t, xp(p.xio, i));
             if (TAIL == 2) {                                          // next block's conv1 pre-op, back into T in place
 #pragma unroll
                 for (int e = 0; e < 4; ++e) t[e] = elu_act(t[e] + p.n_b1a) + p.n_b1b;
-                *reinterpret_cast<f32x4*>(trow + RP * i * LDT) = t;
+                *tr(i) = t;
             }
         }
         if constexpr (TAIL == 2) {
@@ -548,14 +665,16 @@ void wino43_trunk_kernel(const W43K p) {
             lds_barrier();                                           // every wave is done reading T
             acc_to_lds();
             lds_barrier();
-            float* const y0 = p.y2 + (xr[0] - p.xio);
+            [[maybe_unused]] float* y0 = nullptr;
+            if constexpr (!WIDE) y0 = p.y2 + (xr[0] - p.xio);
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                f32x4 t = *reinterpret_cast<const f32x4*>(trow + RP * i * LDT);
+                f32x4 t = *tr(i);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) t[e] = elu_act(t[e] + p.n_b2a) + p.n_b2b;
                 const int r = (RP * i) / W;
-                __builtin_nontemporal_store(t, reinterpret_cast<f32x4*>(y0 + ((4 * (r >> 1) + (r & 1)) * W + (RP * i) % W) * C));
+                if constexpr (WIDE) __builtin_nontemporal_store(t, xp(p.y2, i));
+                else __builtin_nontemporal_store(t, reinterpret_cast<f32x4*>(y0 + ((4 * (r >> 1) + (r & 1)) * W + (RP * i) % W) * C));
             }
         }
         if (hf == 0) lds_barrier();                                  // T is rewritten by the second half's t2
@@ -669,19 +788,19 @@ int wino43_transform_weight(const float* w_oihw_dev, int c, float* U_dev, hipStr
     return VQAE_OK;
 }
 
-template <int C, bool SPLIT>
+template <int C, bool SPLIT, bool WIDE = false>
 static int launch_w43(W43K& k, int64_t M, bool chain, hipStream_t stream) {
-    using K = W43Cfg<C>;
+    using K = W43Cfg<C, WIDE>;
     constexpr int lds = SPLIT ? K::LDS_SPLIT : K::LDS_BYTES;
-    if (int rc = set_max_dynamic_lds((const void*)wino43_trunk_kernel<C, 1, SPLIT>, lds)) return rc;
-    if (int rc = set_max_dynamic_lds((const void*)wino43_trunk_kernel<C, 2, SPLIT>, lds)) return rc;
-    const unsigned grid = (unsigned)(M / (8 * K::W));
+    if (int rc = set_max_dynamic_lds((const void*)wino43_trunk_kernel<C, 1, SPLIT, WIDE>, lds)) return rc;
+    if (int rc = set_max_dynamic_lds((const void*)wino43_trunk_kernel<C, 2, SPLIT, WIDE>, lds)) return rc;
+    const unsigned grid = (unsigned)(M / (K::ROWS * K::W));
     // executed matrix work: 36 GEMMs of K = C per 16 output pixels (K_eff = 2.25 C per pixel) + the 1x1 tails, priced as fp32 work
     // in both forms (the split form executes 3x these products on the bf16 pipe)
     const double flops = 2.0 * (double)M * C * (2.25 * C + C + (chain ? C : 0));
     ProfScope prof(C >= 128 ? PROF_CONV3X3_TRUNK : PROF_NONE, stream, flops);
-    if (chain) wino43_trunk_kernel<C, 2, SPLIT><<<grid, K::NT, lds, stream>>>(k);
-    else wino43_trunk_kernel<C, 1, SPLIT><<<grid, K::NT, lds, stream>>>(k);
+    if (chain) wino43_trunk_kernel<C, 2, SPLIT, WIDE><<<grid, K::NT, lds, stream>>>(k);
+    else wino43_trunk_kernel<C, 1, SPLIT, WIDE><<<grid, K::NT, lds, stream>>>(k);
     prof.done();
     VQAE_LAUNCH_CHECK();
     return VQAE_OK;
@@ -706,6 +825,7 @@ int wino43_trunk_tail(const float* t1, const float* U, const float* w3, float ac
     if (Us) {
         VQAE_REQUIRE(wino43_split_supported(c) && w3s && (!w1n || next.w1s), VQAE_ERR_INVALID, "wino43_trunk_tail: split form needs C = 128 and its three weights");
         k.Us = (const float*)Us; k.w3s = (const float*)w3s; k.w1ns = (const float*)next.w1s;
+        if (h % 16 == 0) return launch_w43<128, true, true>(k, M, w1n != nullptr, stream);   // 16-row workgroups: every weight fragment once per CU
         return launch_w43<128, true>(k, M, w1n != nullptr, stream);
     }
     switch (c) {
