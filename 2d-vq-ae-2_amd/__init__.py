@@ -7,17 +7,19 @@ through the loader module of the same name at the repository root.
 Layout: csrc/ (HIP kernels + C ABI, built into libvqae_hip.so), _lib.py / ops.py (ctypes binding),
 native.py (whole-model handle), layers/ + model.py (mirrors of the reference's module API),
 extract_embeddings.py (whole-slide driver), metrics.py (reconstruction metrics) + validate.py (dataset
-validation driver), reconstruct.py (stored code grids -> uint8 slide pixels), classifier.py (the downstream slide
+validation driver), reconstruct.py (stored code grids -> uint8 slide pixels), ingest.py (uint8 slide arrays -> code and
+label grids, no DataLoader), classifier.py (the downstream slide
 classifier on stored code grids: heatmaps and scores), classifier_train.py + optim.py (its training: the fused backward, the
 LAMB / SAM mirrors and the device-resident optimiser step), code_stats.py (exact code / label histograms of stored code grids and
 the loss weights read off them), dist.py (one-process-per-GPU sharding over RCCL).
 """
-from . import _lib, classifier, classifier_train, code_stats, ops, optim, reconstruct, spec  # noqa: F401
+from . import _lib, classifier, classifier_train, code_stats, ingest, ops, optim, reconstruct, spec  # noqa: F401
 from .classifier import CNNClassifier, classify_hdf5, classify_slide  # noqa: F401
 from .classifier_train import (ce_loss_and_grads, collate_random_crop, embeddings_split, loss_and_grads,  # noqa: F401
                                smooth_targets, train_hdf5)
 from .code_stats import (class_weights, code_histogram, histogram_hdf5, label_histogram_hdf5, perplexity,  # noqa: F401
                          pos_weight_hdf5)
+from .ingest import encode_arrays_hdf5, encode_region, encode_slide  # noqa: F401
 from .native import NativeVQAE  # noqa: F401
 from .optim import SAM, ClassifierTrainer, Lamb  # noqa: F401
 from .reconstruct import reconstruct_hdf5, reconstruct_overview, reconstruct_region, reconstruct_slide  # noqa: F401

@@ -126,6 +126,9 @@ SYMBOLS = {
                                c_int, c_int, c_void_p]),
     "vqae_pixels_u8_level": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, POINTER(c_float), POINTER(c_float),
                                      c_void_p, c_int, c_int, c_void_p]),
+    "vqae_cut_pixels_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                   c_void_p]),
+    "vqae_pool_labels_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "vqae_create": (c_int, [POINTER(Config), POINTER(Tensor), c_int, POINTER(c_void_p)]),
     "vqae_destroy": (None, [c_void_p]),
     "vqae_reserve": (c_int, [c_void_p, c_int, c_int, c_int]),

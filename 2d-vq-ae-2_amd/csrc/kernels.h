@@ -171,6 +171,13 @@ int pixels_u8_level_check(const char* who, int H, int W, int level, bool canvas,
 int pixels_u8_level(const float* x, int layout, int B, int H, int W, int level, const int32_t* rc, const float* mean255,
                     const float* std255, uint8_t* out, int canvas_h, int canvas_w, hipStream_t stream);
 
+// ---- ingest.hip --------------------------------------------------------------------------------
+// vqae_cut_pixels_u8 / vqae_pool_labels_u8 (include/vqae_hip.h) on a hipStream_t
+int cut_pixels_u8(const uint8_t* canvas, int canvas_h, int canvas_w, int ch, const int32_t* rc, int n_tiles, int h, int w, int y0,
+                  int x0, int level, uint8_t* tiles, hipStream_t stream);
+int pool_labels_u8(const uint8_t* mask, int mask_h, int mask_w, int y0, int x0, int win_h, int win_w, uint8_t* out, int out_h,
+                   int out_w, hipStream_t stream);
+
 // ---- vq_filter.hip / vq_kernels.hip ------------------------------------------------------------
 bool vq_filter_supported(int K, int D);
 size_t vq_filter_table_bytes(int K, int D);

@@ -391,6 +391,78 @@ def pixels_u8(x, layout="NCHW", rc=None, canvas=None, mean=MEAN, std=STD, level=
     return run(_p(rc), canvas, canvas.shape[0], canvas.shape[1])
 
 
+def cut_pixels_u8(canvas, rc, h, w, *, y0=0, x0=0, level=0, out=None):
+    """Tiles [n, h, w, ch] (uint8) cut out of the pixel canvas [H, W, ch] (uint8, ch 1 or 3, in HBM) at the patch positions rc
+    [n, 2] (int32), box-reduced to `level` (f = 2**level): tile t covers the (h * f) x (w * f) canvas pixels at
+    (y0 + rc[t, 0] * h * f, x0 + rc[t, 1] * w * f), every output pixel the integer mean, rounding half up, of its f x f block
+    (level 0: a copy).  A tile that does not lie wholly inside the canvas is skipped: it keeps what `out`, a contiguous
+    [n, h, w, ch] tensor to fill, held (without `out`: whatever the allocation held)."""
+    _need_gpu(canvas, rc, out)
+    assert canvas.dtype == torch.uint8 and canvas.dim() == 3 and canvas.is_contiguous(), \
+        "cut_pixels_u8: canvas must be a contiguous uint8 [H, W, ch] tensor"
+    H, W, ch = canvas.shape
+    rc = rc.to(torch.int32).contiguous()
+    assert rc.dim() == 2 and rc.shape[1] == 2, rc.shape
+    n = rc.shape[0]
+    if out is not None:
+        assert out.dtype == torch.uint8 and tuple(out.shape) == (n, h, w, ch) and out.is_contiguous(), out.shape
+    else:
+        out = torch.empty((n, h, w, ch), dtype=torch.uint8, device=canvas.device)
+    L.check(L.lib().vqae_cut_pixels_u8(_p(canvas), H, W, ch, _p(rc) if n else None, n, int(h), int(w), int(y0), int(x0), int(level),
+                                       _p(out) if n else None, _stream()))
+    return out
+
+
+def pool_labels_u8(mask, win, *, y0=0, x0=0, out_hw=None):
+    """Label grid [out_h, out_w] (uint8) of the mask canvas [H, W] (uint8, in HBM): out[Y, X] = the maximum of the win x win (or
+    (win_h, win_w)) window at (y0 + Y * win_h, x0 + X * win_w).  out_hw defaults to every whole window from the origin on; a
+    window reaching outside the mask raises."""
+    _need_gpu(mask)
+    assert mask.dtype == torch.uint8 and mask.dim() == 2 and mask.is_contiguous(), "pool_labels_u8: mask must be a contiguous uint8 [H, W] tensor"
+    wh, ww = (win, win) if isinstance(win, int) else (int(win[0]), int(win[1]))
+    H, W = mask.shape
+    if out_hw is None:
+        assert wh >= 1 and ww >= 1, win
+        out_hw = (max(H - y0, 0) // wh, max(W - x0, 0) // ww)
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    out = torch.empty((max(oh, 0), max(ow, 0)), dtype=torch.uint8, device=mask.device)
+    L.check(L.lib().vqae_pool_labels_u8(_p(mask), H, W, int(y0), int(x0), wh, ww, _p(out) if out.numel() else None, oh, ow,
+                                        _stream()))
+    return out
+
+
+def cut_pixels_reference(canvas, rc, h, w, *, y0=0, x0=0, level=0, out=None):
+    """numpy restatement of cut_pixels_u8 for host arrays (the yardstick of the tests, and the cut of the injected-encode
+    path): the same tiles, the same skipped tiles."""
+    import numpy as np
+    canvas, rc = np.asarray(canvas), np.asarray(rc).reshape(-1, 2)
+    assert canvas.dtype == np.uint8 and canvas.ndim == 3, (canvas.dtype, canvas.shape)
+    H, W, ch = canvas.shape
+    f = 1 << level
+    tiles = out if out is not None else np.zeros((len(rc), h, w, ch), np.uint8)
+    for t, (r, c) in enumerate(rc.tolist()):
+        sy, sx = y0 + r * h * f, x0 + c * w * f
+        if r < 0 or c < 0 or sy + h * f > H or sx + w * f > W:
+            continue
+        block = canvas[sy:sy + h * f, sx:sx + w * f].astype(np.uint32).reshape(h, f, w, f, ch)
+        tiles[t] = ((block.sum(axis=(1, 3), dtype=np.uint32) + (f * f) // 2) >> (2 * level)).astype(np.uint8)
+    return tiles
+
+
+def pool_labels_reference(mask, win, *, y0=0, x0=0, out_hw=None):
+    """numpy restatement of pool_labels_u8 for host arrays; AssertionError, like the library's, for a window reaching outside
+    the mask"""
+    import numpy as np
+    mask = np.asarray(mask)
+    assert mask.dtype == np.uint8 and mask.ndim == 2, (mask.dtype, mask.shape)
+    wh, ww = (win, win) if isinstance(win, int) else (int(win[0]), int(win[1]))
+    H, W = mask.shape
+    oh, ow = out_hw if out_hw is not None else ((H - y0) // wh, (W - x0) // ww)
+    assert y0 >= 0 and x0 >= 0 and oh >= 0 and ow >= 0 and y0 + oh * wh <= H and x0 + ow * ww <= W, \
+        f"pool_labels: {oh} x {ow} windows of {wh} x {ww} at ({y0}, {x0}) reach outside the {H} x {W} mask"
+    return np.ascontiguousarray(mask[y0:y0 + oh * wh, x0:x0 + ow * ww].reshape(oh, wh, ow, ww).max(axis=(1, 3), initial=0))
+
+
 def classifier_forward(handle, codes, n_out=1, logits=True, heat=False, mask=None, pos_weight=1.0):
     """vqae_classifier_forward on codes [B,H,W] (uint8 / uint16 / int32 / int64, in HBM) with the vqae_classifier `handle`
     (a ctypes pointer; classifier.NativeClassifier owns one) of `n_out` outputs -> (logits fp32 [B,n_out,H,W] | None,

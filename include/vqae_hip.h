@@ -313,8 +313,35 @@ int vqae_pixels_u8_level(const float* x_dev, int layout, int batch, int h, int w
                          const float* mean255, const float* std255, uint8_t* out_dev, int canvas_h, int canvas_w,
                          void* stream);
 
+/* Cut encoder tiles out of a resident uint8 pixel canvas, box-reduced to level L (f = 2^level): the device form of
+ * CAMELYON16SlicePatchDataSet.__getitem__ (datamodules/camelyon16.py:149-211: the patch at patch position (r, c) is the
+ * patch_size block at pixel (r, c) * patch_size of the slide's level) for a slide that is already an array:
+ *   tiles[t][y][x][c] = ( sum over dy < f, dx < f of canvas[y0 + (rc[t].r*h + y)*f + dy][x0 + (rc[t].c*w + x)*f + dx][c]
+ *                         +  f*f/2 ) >> (2*level)
+ *   canvas_dev [canvas_h][canvas_w][ch] uint8, ch 1 or 3; tiles_dev dense [n_tiles][h][w][ch] uint8, what vqae_encode_u8 takes;
+ *   rc_dev [n_tiles][2] int32 patch positions as get_encodings uses them (extract_embeddings.py:77-84); (y0, x0) a pixel
+ *   origin in the canvas.  level 0 is a plain copy; level L > 0 is the integer rule of vqae_pixels_u8_level: exact sums,
+ *   rounding half up, independent of the summation order.  Row offsets are 64-bit (a 100 000 x 200 000-pixel canvas indexes
+ *   correctly); every canvas byte of a tile is read once, in 16-byte loads where the rows are 16-byte aligned.
+ * A tile at a negative position or one that does not lie wholly inside the canvas is skipped (no access outside it) and its
+ * destination left untouched, the convention of vqae_unstitch_tiles.
+ * Errors: ch outside {1, 3}, a bad shape, a negative origin or level, a canvas that holds no tile at the origin, null pointers
+ * -> VQAE_ERR_INVALID; level > VQAE_MAX_PIXEL_LEVEL -> VQAE_ERR_UNSUPPORTED. */
+int vqae_cut_pixels_u8(const uint8_t* canvas_dev, int canvas_h, int canvas_w, int ch, const int32_t* rc_dev, int n_tiles, int h,
+                       int w, int y0, int x0, int level, uint8_t* tiles_dev, void* stream);
+
+/* Pool a mask canvas straight into a label grid:
+ *   out[Y][X] = max over dy < win_h, dx < win_w of mask[y0 + Y*win_h + dy][x0 + X*win_w + dx]
+ * mask_dev [mask_h][mask_w] uint8, out_dev dense [out_h][out_w] uint8.  Tiles are aligned and do not overlap and a code tile
+ * is patch / 2^n_down, so the per-tile F.adaptive_max_pool2d of run_eval (scripts/extract_embeddings/extract_embeddings.py:
+ * 127-130) over a region is ONE window maximum with win = 2^n_down * 2^level over the region's mask: a streaming pass that
+ * reads every mask byte once (vqae_label_maxpool_u8 remains the per-batch form).
+ * Errors: a bad shape, a negative origin, a window reaching outside the mask, null pointers -> VQAE_ERR_INVALID. */
+int vqae_pool_labels_u8(const uint8_t* mask_dev, int mask_h, int mask_w, int y0, int x0, int win_h, int win_w, uint8_t* out_dev,
+                        int out_h, int out_w, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
- * 3. Whole-model handle -- replaces Encoder.forward (vq_ae/model.py:189-217), Decoder.forward
+ * 3. Whole-model handle-- replaces Encoder.forward (vq_ae/model.py:189-217), Decoder.forward
  *    (:274-291) and VQAE.forward (:41-48) for the single-VQ-level Fixup model that every shipped
  *    config composes.
  * ------------------------------------------------------------------------------------------- */
