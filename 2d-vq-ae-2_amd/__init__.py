@@ -10,7 +10,8 @@ extract_embeddings.py (whole-slide driver), metrics.py (reconstruction metrics) 
 validation driver), reconstruct.py (stored code grids -> uint8 slide pixels), ingest.py (uint8 slide arrays -> code and
 label grids, no DataLoader), classifier.py (the downstream slide
 classifier on stored code grids: heatmaps and scores), classifier_train.py + optim.py (its training: the fused backward, the
-LAMB / SAM mirrors and the device-resident optimiser step), code_stats.py (exact code / label histograms of stored code grids and
+LAMB / SAM mirrors and the device-resident optimiser step; FusedAdam / FusedAdamW / FusedLamb: the fused multi-tensor step for
+any parameter list), code_stats.py (exact code / label histograms of stored code grids and
 the loss weights read off them), dist.py (one-process-per-GPU sharding over RCCL).
 """
 from . import _lib, classifier, classifier_train, code_stats, ingest, ops, optim, reconstruct, spec  # noqa: F401
@@ -21,6 +22,6 @@ from .code_stats import (class_weights, code_histogram, histogram_hdf5, label_hi
                          pos_weight_hdf5)
 from .ingest import encode_arrays_hdf5, encode_region, encode_slide  # noqa: F401
 from .native import NativeVQAE  # noqa: F401
-from .optim import SAM, ClassifierTrainer, Lamb  # noqa: F401
+from .optim import SAM, ClassifierTrainer, FusedAdam, FusedAdamW, FusedLamb, Lamb  # noqa: F401
 from .reconstruct import reconstruct_hdf5, reconstruct_overview, reconstruct_region, reconstruct_slide  # noqa: F401
 from .spec import SPECS, VQAESpec  # noqa: F401

@@ -69,6 +69,7 @@ class Tensor(Structure):
 
 
 OPTIM_KINDS = {"adam": 0, "adamw": 1, "lamb": 2}          # VQAE_OPTIM_*
+OPTIM_CHUNK, OPTIM_SMALL = 4096, 64                       # VQAE_OPTIM_CHUNK, VQAE_OPTIM_SMALL (vqae_optim_step's work split)
 
 
 class ClassifierOptimConfig(Structure):
@@ -179,6 +180,14 @@ SYMBOLS = {
     "vqae_classifier_loss_grad_ce": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, POINTER(c_float), c_float,
                                              c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vqae_classifier_optim_create_ce": (c_int, [c_void_p, POINTER(ClassifierOptimConfig), POINTER(c_void_p)]),
+    "vqae_optim_create": (c_int, [c_int, POINTER(c_int64), POINTER(c_int), c_int, POINTER(ClassifierOptimConfig),
+                                  POINTER(c_void_p)]),
+    "vqae_optim_destroy": (None, [c_void_p]),
+    "vqae_optim_set": (c_int, [c_void_p, POINTER(ClassifierOptimConfig)]),
+    "vqae_optim_step": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_void_p]),
+    "vqae_optim_sam_first": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_void_p]),
+    "vqae_optim_export": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_void_p]),
+    "vqae_optim_import": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_void_p]),
     "vqae_code_histogram_workspace_bytes": (c_size_t, [c_int, c_int64, c_int, c_int]),
     "vqae_code_histogram": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                     c_void_p, c_void_p]),

@@ -17,10 +17,12 @@
 // Division and square root are the correctly rounded ones (eps = 1e-8 stands next to sqrt(v)); the file is built like the
 // rest, without fast-math and without contraction.
 #include "classifier_impl.h"
+#include "optim_math.h"
 
 #include <cmath>
 
 using namespace vqae_cls;
+using vqae_om::check_config;
 
 namespace {
 
@@ -32,10 +34,9 @@ enum { MODE_ADAM = 0, MODE_LAMB = 1, MODE_CLIMB = 2 };
 
 struct Args {
     float* img; float* m; float* v; float* saved; const double* g; double* partial;
-    int G, mode, decoupled, restore, adaptive, wd_nonzero;
+    int G, mode, restore;
     ParamMap map;
-    // scalars formed in double on the host and rounded once, as torch rounds the Python scalars it is handed
-    float decay, w1, b1, b2, w2, bc1, bc2, bc2_sqrt, eps, neg_step, wd, neg_lr, rho;
+    vqae_om::Hyper h;                // the per-element arithmetic and these scalars are optim_math.h's, shared with optim.hip
 };
 
 // The elements of tensor I among the dense indices j0 .. j1-1, NT apart from the thread's own: f(j, place of j in the
@@ -56,30 +57,15 @@ __device__ __forceinline__ void for_tensor(const ParamMap& mp, int j0, int j1, F
     }
 }
 
-// lamb.py:84-104: the Adam step u of one element from its (already updated) moments
-__device__ __forceinline__ float lamb_u(const Args& a, float m, float v, float p) {
-    float u = (m / a.bc1) / (sqrtf(v / a.bc2) + a.eps);
-    if (a.wd_nonzero) u = u + a.wd * p;
-    return u;
-}
-
 // torch.optim.adam._single_tensor_adam, the non-capturable branch (decoupled = AdamW)
 template <int I>
 __device__ __forceinline__ void adam_tensors(const Args& a, int j0, int j1) {
     if constexpr (I < 7) {
         for_tensor<I>(a.map, j0, j1, [&](int j, int ii) {
-            float g = (float)a.g[j];
+            const float g = (float)a.g[j];
             float p = a.restore ? a.saved[j] : a.img[ii];
-            if (a.wd_nonzero) {
-                if (a.decoupled) p = p * a.decay;
-                else g = g + a.wd * p;
-            }
             float m = a.m[j], v = a.v[j];
-            const float d = g - m;
-            m = fabsf(a.w1) < 0.5f ? m + a.w1 * d : g - d * (1.0f - a.w1);  // Tensor.lerp_
-            v = v * a.b2 + (a.w2 * g) * g;
-            const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-            p = p + (a.neg_step * m) / denom;                                // addcdiv_
+            vqae_om::adam_element(a.h, g, p, m, v);
             a.m[j] = m; a.v[j] = v; a.img[ii] = p;
         });
         adam_tensors<I + 1>(a, j0, j1);
@@ -105,14 +91,13 @@ __device__ __forceinline__ void norm_tensors(const Args& a, int j0, int j1, doub
             const float p = a.restore ? a.saved[j] : a.img[ii];
             if (a.mode == MODE_LAMB) {
                 float m = a.m[j], v = a.v[j];
-                m = m * a.b1 + a.w1 * g;
-                v = v * a.b2 + (a.w2 * g) * g;
+                vqae_om::lamb_moments(a.h, g, m, v);
                 a.m[j] = m; a.v[j] = v;
-                const float u = lamb_u(a, m, v, p);
+                const float u = vqae_om::lamb_u(a.h, m, v, p);
                 sp += (double)(p * p);
                 su += (double)(u * u);
             } else {
-                const float q = a.adaptive ? fabsf(p) * g : g;
+                const float q = vqae_om::climb_q(a.h, p, g);
                 sp += (double)(q * q);
             }
         }
@@ -125,19 +110,15 @@ template <int I>
 __device__ __forceinline__ void apply_tensors(const Args& a, int j0, int j1, const double* sums, float scale) {
     if constexpr (I < 7) {
         float step = 0.0f;
-        if (a.mode == MODE_LAMB) {                                               // lamb.py:106-114
-            const float wn = (float)sqrt(sums[2 * I]), un = (float)sqrt(sums[2 * I + 1]);
-            const float r = (wn > 0.0f && un > 0.0f) ? wn / un : 1.0f;
-            step = a.neg_lr * r;
-        }
+        if (a.mode == MODE_LAMB) step = vqae_om::lamb_step(a.h, sums[2 * I], sums[2 * I + 1]);   // lamb.py:106-114
         for_tensor<I>(a.map, j0, j1, [&](int j, int ii) {
             const float p = a.restore ? a.saved[j] : a.img[ii];
             if (a.mode == MODE_LAMB) {
-                a.img[ii] = p + step * lamb_u(a, a.m[j], a.v[j], p);
+                a.img[ii] = p + step * vqae_om::lamb_u(a.h, a.m[j], a.v[j], p);
             } else {                                                             // sam.py:36-46
                 const float g = (float)a.g[j];
                 a.saved[j] = p;
-                a.img[ii] = p + (a.adaptive ? ((p * p) * g) * scale : g * scale);
+                a.img[ii] = vqae_om::climb(a.h, p, g, scale);
             }
         });
         apply_tensors<I + 1>(a, j0, j1, sums, scale);
@@ -150,7 +131,7 @@ __device__ __forceinline__ void apply_pass(const Args& a, int j0, int j1, const 
         double n2 = sums[0];
 #pragma unroll
         for (int i = 1; i < 7; ++i) n2 += sums[2 * i];
-        scale = a.rho / ((float)sqrt(n2) + 1e-12f);
+        scale = vqae_om::climb_scale(a.h, n2);
     }
     apply_tensors<0>(a, j0, j1, sums, scale);
 }
@@ -209,19 +190,6 @@ __global__ __launch_bounds__(NT) void optim_apply(Args a, int n_rows) {
     block_sums(acc, red, sums);
     const int j0 = blockIdx.x * CHUNK, j1 = min(j0 + CHUNK, a.G);
     apply_pass(a, j0, j1, sums);
-}
-
-int check_config(const char* who, const vqae_classifier_optim_config* cfg) {
-    VQAE_REQUIRE(cfg, VQAE_ERR_INVALID, "%s: null config", who);
-    VQAE_REQUIRE(cfg->kind == VQAE_OPTIM_ADAM || cfg->kind == VQAE_OPTIM_ADAMW || cfg->kind == VQAE_OPTIM_LAMB, VQAE_ERR_INVALID,
-                 "%s: unknown optimiser kind %d", who, cfg->kind);
-    VQAE_REQUIRE(cfg->lr >= 0.0, VQAE_ERR_INVALID, "%s: invalid learning rate %g", who, cfg->lr);
-    VQAE_REQUIRE(cfg->eps >= 0.0, VQAE_ERR_INVALID, "%s: invalid epsilon value %g", who, cfg->eps);
-    VQAE_REQUIRE(cfg->beta1 >= 0.0 && cfg->beta1 < 1.0, VQAE_ERR_INVALID, "%s: invalid beta parameter at index 0: %g", who, cfg->beta1);
-    VQAE_REQUIRE(cfg->beta2 >= 0.0 && cfg->beta2 < 1.0, VQAE_ERR_INVALID, "%s: invalid beta parameter at index 1: %g", who, cfg->beta2);
-    VQAE_REQUIRE(cfg->weight_decay >= 0.0, VQAE_ERR_INVALID, "%s: invalid weight_decay value %g", who, cfg->weight_decay);
-    VQAE_REQUIRE(!std::isnan(cfg->sam_rho), VQAE_ERR_INVALID, "%s: sam_rho is nan", who);
-    return VQAE_OK;
 }
 
 }  // namespace
@@ -305,12 +273,9 @@ int begin(const char* who, vqae_classifier_optim* o, const double* grads_dev, hi
     const vqae_classifier_optim_config& f = o->cfg;
     a->img = c->dev; a->m = o->m; a->v = o->v; a->saved = o->saved; a->g = grads_dev; a->partial = o->partial;
     a->G = o->G;
-    a->decoupled = f.kind == VQAE_OPTIM_ADAMW;
     a->restore = 0;
-    a->adaptive = f.sam_adaptive != 0;
-    a->wd_nonzero = f.weight_decay != 0.0;
     a->map = param_map(c);
-    a->rho = (float)f.sam_rho;
+    a->h = vqae_om::make_hyper(f, 0.0);                          // the climb reads rho and adaptive only
     return VQAE_OK;
 }
 
@@ -349,13 +314,8 @@ extern "C" int vqae_classifier_optim_step(vqae_classifier_optim* o, const double
     hipStream_t st = (hipStream_t)stream;
     if (int rc = begin("classifier_optim_step", o, grads_dev, st, &a)) return rc;
     const vqae_classifier_optim_config& f = o->cfg;
-    const double t = (double)(o->step + 1);
-    const double bc1 = 1.0 - std::pow(f.beta1, t), bc2 = 1.0 - std::pow(f.beta2, t);
     a.restore = o->climbed;                                        // sam.py:53-56: back to w, then the base step
-    a.decay = (float)(1.0 - f.lr * f.weight_decay);
-    a.w1 = (float)(1.0 - f.beta1); a.b1 = (float)f.beta1; a.b2 = (float)f.beta2; a.w2 = (float)(1.0 - f.beta2);
-    a.bc1 = (float)bc1; a.bc2 = (float)bc2; a.bc2_sqrt = (float)std::sqrt(bc2);
-    a.eps = (float)f.eps; a.neg_step = (float)(-(f.lr / bc1)); a.wd = (float)f.weight_decay; a.neg_lr = (float)(-f.lr);
+    a.h = vqae_om::make_hyper(f, (double)(o->step + 1));
     if (f.kind == VQAE_OPTIM_LAMB) {
         a.mode = MODE_LAMB;
         if (int rc = launch_norm_mode(o, a, st)) return rc;

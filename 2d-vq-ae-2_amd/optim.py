@@ -7,6 +7,12 @@ fp32 they are the yardstick the HIP kernel is measured against.  `SAM` takes the
 `f(param_groups, **overrides)` or the reference's `base_optimizer_conf` dict, whose `_target_` is resolved by import path
 (no hydra; `vq_ae.optim.lamb.Lamb` resolves to the mirror here).
 
+`FusedAdam`, `FusedAdamW` and `FusedLamb` are the same optimisers for any parameter list -- the ~1 600 tensors of an Encoder /
+Decoder -- as `torch.optim.Optimizer`s whose device step is csrc/optim.hip: one launch (Adam / AdamW) or three (LAMB, SAM's
+climb) over all tensors, the per-tensor norms and SAM's global norm formed on the device, nothing read back.  `SAM` accepts
+them as base optimiser (class, factory or `_target_: vqae_amd.optim.FusedLamb`) and then climbs and restores in the same
+handle.  On CPU tensors they run `Lamb` / torch's Adam and AdamW; their state_dict is torch.optim's either way.
+
 `ClassifierTrainer` is one training step of `loss_and_grads` + `optimizer.step()` without the host in between: it owns a
 vqae_classifier made from the module's parameters and a vqae_classifier_optim on it (csrc/classifier_optim.hip); `step` runs
 vqae_classifier_loss_grad and the optimiser kernel on the packed gradient in HBM, which rewrites the weight image the next
@@ -71,6 +77,297 @@ class Lamb(Optimizer):
         return loss
 
 
+# ---- the fused multi-tensor step (csrc/optim.hip) ----------------------------------------------------------------------------
+def _dense(t):
+    """Dense and non-overlapping in any memory format: walking the storage visits every element once."""
+    n = 1
+    for size, stride in sorted(((s, st) for s, st in zip(t.shape, t.stride()) if s != 1), key=lambda x: x[1]):
+        if stride != n:
+            return False
+        n *= size
+    return True
+
+
+def _storage_order(t, like):
+    """`t` (the logical shape of `like`) as a flat view of its elements in the order `like` keeps them in memory."""
+    if t.stride() != like.stride():
+        t = torch.empty_like(like, dtype=t.dtype, device=t.device).copy_(t)
+    return t.as_strided((t.numel(),), (1,), t.storage_offset())
+
+
+class _Fused(Optimizer):
+    """What FusedAdam, FusedAdamW and FusedLamb share.  On device parameters a step collects the parameter and gradient
+    addresses and calls vqae_optim_step on the current stream: nothing is read back, the moments live dense in a
+    vqae_optim handle and come out as tensors only for state_dict().  On CPU parameters the step is the torch code of
+    `_cpu_class` on this optimiser's own param_groups and state.  Either way state_dict() has torch.optim's layout."""
+    _kind = None
+    _cpu_class = None
+
+    def __init__(self, params, defaults):
+        self._h = None                  # the vqae_optim handle, its parameters and the address arrays of a step
+        self._sig = None
+        self._params = []
+        self._cpu = None
+        self._climbing = False          # a SAM first step is waiting for its step
+        super().__init__(params, defaults)
+
+    # ---- parameters ---------------------------------------------------------------------------------------------------------
+    def _all_params(self):
+        return [p for g in self.param_groups for p in g["params"]]
+
+    def add_param_group(self, param_group):
+        """After the first device step this rebuilds the handle at the next step; the state is kept."""
+        if getattr(self, "_h", None) is not None:
+            self._export_into_state()
+            self._drop()
+        super().add_param_group(param_group)
+        ps = self._all_params()
+        for p in ps:
+            if p.dtype not in (torch.float32, torch.float64):
+                raise TypeError(f"{type(self).__name__} steps fp32 parameters (fp64 on the CPU), got {p.dtype}")
+        if len({p.device for p in ps}) > 1:
+            raise ValueError(f"{type(self).__name__}: the parameters are on several devices: "
+                             f"{sorted(str(p.device) for p in ps)[0]} ... {sorted(str(p.device) for p in ps)[-1]}")
+
+    def _on_device(self):
+        return self.param_groups[0]["params"][0].is_cuda
+
+    def _configs(self):
+        arr = (L.ClassifierOptimConfig * len(self.param_groups))()
+        for k, g in enumerate(self.param_groups):
+            for flag in ("amsgrad", "maximize", "capturable", "differentiable"):
+                if g.get(flag):
+                    raise NotImplementedError(f"{type(self).__name__}: {flag}=True is not provided")
+            rho = g.get("rho")
+            arr[k] = L.ClassifierOptimConfig(L.OPTIM_KINDS[self._kind], float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]),
+                                             float(g["eps"]), float(g["weight_decay"]), -1.0 if rho is None else float(rho),
+                                             int(bool(g.get("adaptive", False))))
+        return arr
+
+    # ---- the handle ---------------------------------------------------------------------------------------------------------
+    def _ensure_handle(self):
+        params = self._all_params()
+        sig = tuple(map(id, params))
+        if self._h is not None and sig == self._sig:
+            return
+        if self._h is not None:                                   # the parameter list changed under a live handle
+            self._export_into_state()
+            self._drop()
+        group_of = [k for k, g in enumerate(self.param_groups) for _ in g["params"]]
+        for p in params:
+            if p.dtype != torch.float32:
+                raise TypeError(f"{type(self).__name__} steps fp32 parameters on the device, got {p.dtype}")
+            if p.device != params[0].device:
+                raise ValueError(f"{type(self).__name__}: the parameters are on several devices")
+            if p.numel() < 1 or not _dense(p):
+                raise ValueError(f"{type(self).__name__}: a parameter of shape {tuple(p.shape)} and strides {p.stride()} is empty or "
+                                 "not dense in memory")
+        n = len(params)
+        numel = (ctypes.c_int64 * n)(*[p.numel() for p in params])
+        h = ctypes.c_void_p()
+        cfgs = self._configs()
+        with torch.cuda.device(params[0].device):
+            L.check(L.lib().vqae_optim_create(n, numel, (ctypes.c_int * n)(*group_of), len(self.param_groups), cfgs, ctypes.byref(h)))
+        self._h, self._sig, self._params = h, sig, params
+        self._strides = [p.stride() for p in params]
+        self._pp, self._gp = (ctypes.c_void_p * n)(), (ctypes.c_void_p * n)()
+        if self.state:
+            self._import_from_state()
+            self.state.clear()
+
+    def _drop(self):
+        if getattr(self, "_h", None) is not None:
+            if self._climbing:
+                raise RuntimeError(f"{type(self).__name__}: a SAM first step is waiting for its second step")
+            L.lib().vqae_optim_destroy(self._h)
+        self._h, self._sig, self._params = None, None, []
+
+    def __del__(self):
+        try:
+            if self._h is not None:
+                L.lib().vqae_optim_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def _step_value(self, k):
+        return int(k) if self._kind == "lamb" else torch.tensor(float(k), dtype=torch.float32)
+
+    def _export_into_state(self):
+        """The handle's moments and step counts as self.state entries (tensors on the parameters' device, of their shapes and
+        strides; a tensor that has not stepped has no entry, as in torch's lazy state).  Synchronises."""
+        params = self._params
+        total = sum(p.numel() for p in params)
+        m, v = np.empty(total, np.float32), np.empty(total, np.float32)
+        steps = (ctypes.c_int64 * len(params))()
+        dev = params[0].device
+        with torch.cuda.device(dev):
+            L.check(L.lib().vqae_optim_export(self._h, m.ctypes.data, v.ctypes.data, steps, ops._stream()))
+            m, v = torch.from_numpy(m).to(dev), torch.from_numpy(v).to(dev)
+        o = 0
+        for p, k in zip(params, steps):
+            n = p.numel()
+            if k > 0:
+                self.state[p] = {"step": self._step_value(k), "exp_avg": m[o:o + n].as_strided(p.shape, p.stride()),
+                                 "exp_avg_sq": v[o:o + n].as_strided(p.shape, p.stride())}
+            o += n
+
+    def _import_from_state(self):
+        params = self._params
+        total = sum(p.numel() for p in params)
+        m, v = np.zeros(total, np.float32), np.zeros(total, np.float32)
+        steps = (ctypes.c_int64 * len(params))()
+        o = 0
+        for i, p in enumerate(params):
+            n = p.numel()
+            st = self.state.get(p)
+            if st:
+                steps[i] = int(st["step"])
+                for dst, key in ((m, "exp_avg"), (v, "exp_avg_sq")):
+                    t = st[key]
+                    if tuple(t.shape) != tuple(p.shape):
+                        raise ValueError(f"{type(self).__name__}: {key} of shape {tuple(t.shape)} for a parameter of shape {tuple(p.shape)}")
+                    dst[o:o + n] = _storage_order(t.detach().to(torch.float32), p).cpu().numpy()
+            o += n
+        with torch.cuda.device(params[0].device):
+            L.check(L.lib().vqae_optim_import(self._h, m.ctypes.data, v.ctypes.data, steps, ops._stream()))
+
+    # ---- the step -----------------------------------------------------------------------------------------------------------
+    def _run(self, first):
+        self._ensure_handle()
+        name = type(self).__name__
+        pp, gp, keep = [], [], []
+        for p, strides in zip(self._params, self._strides):        # (the host's share of a step: kept short)
+            g = p.grad
+            pp.append(p.data_ptr())
+            if g is None:
+                gp.append(None)
+                continue
+            if g.is_sparse:
+                raise RuntimeError(f"{name} does not support sparse gradients")
+            if g.stride() != strides:                              # (dtype and device are the parameter's: torch checks `.grad =`)
+                g = torch.empty_like(p).copy_(g)                   # the parameter's layout
+                keep.append(g)
+            gp.append(g.data_ptr())
+        self._pp[:] = pp
+        self._gp[:] = gp
+        lib = L.lib()
+        with torch.cuda.device(self._params[0].device):
+            L.check(lib.vqae_optim_set(self._h, self._configs()))   # the groups are read at every step: lr schedules
+            L.check((lib.vqae_optim_sam_first if first else lib.vqae_optim_step)(self._h, self._pp, self._gp, ops._stream()))
+        self._climbing = first
+
+    def _cpu_opt(self):
+        if self._cpu is None:
+            d = self.defaults
+            self._cpu = self._cpu_class(self.param_groups, lr=d["lr"], betas=d["betas"], eps=d["eps"], weight_decay=d["weight_decay"])
+        self._cpu.param_groups, self._cpu.state = self.param_groups, self.state
+        return self._cpu
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        if self._on_device():
+            self._run(False)
+        else:
+            self._configs()                                        # the same NotImplementedErrors on either path
+            self._cpu_opt().step()
+        return loss
+
+    # ---- state --------------------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        """torch.optim's layout: state[i] = {step, exp_avg, exp_avg_sq} of parameter i's shape (step as the installed torch's
+        Adam / AdamW keeps it, an int for LAMB), what torch.optim.Adam / AdamW / `Lamb` load.  With a live handle this
+        downloads the moments (one synchronising copy)."""
+        live = self._h is not None
+        if live:
+            self._export_into_state()
+        sd = super().state_dict()
+        if live:
+            self.state.clear()
+        return sd
+
+    def load_state_dict(self, state_dict):
+        self._drop()                                               # the next device step builds a handle from the loaded state
+        super().load_state_dict(state_dict)
+
+    def __getstate__(self):                                        # copy.deepcopy and pickle: through the exported state
+        live = self._h is not None
+        if live:
+            self._export_into_state()
+        out = {"defaults": self.defaults, "state": dict(self.state), "param_groups": self.param_groups}
+        if live:
+            self.state.clear()
+        return out
+
+    def __setstate__(self, state):
+        self._drop()
+        self._cpu, self._climbing = None, False
+        super().__setstate__(state)
+        if not hasattr(self.state, "default_factory"):
+            from collections import defaultdict
+            self.state = defaultdict(dict, self.state)
+
+
+def _check_hyper(lr, betas, eps, weight_decay):
+    if not 0.0 <= lr:
+        raise ValueError(f"Invalid learning rate: {lr}")
+    if not 0.0 <= eps:
+        raise ValueError(f"Invalid epsilon value: {eps}")
+    for i in (0, 1):
+        if not 0.0 <= betas[i] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index {i}: {betas[i]}")
+    if not 0.0 <= weight_decay:
+        raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+
+
+class FusedAdam(_Fused):
+    """torch.optim.Adam (single-tensor form, amsgrad=False, maximize=False) with one fused launch per step on device
+    parameters.  Constructor, defaults and ValueErrors are torch.optim.Adam's; amsgrad / maximize / capturable /
+    differentiable raise NotImplementedError, foreach and fused are accepted and not read."""
+    _kind = "adam"
+    _cpu_class = torch.optim.Adam
+    _weight_decay = 0.0
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=None, amsgrad=False, *, foreach=None,
+                 maximize=False, capturable=False, differentiable=False, fused=None):
+        weight_decay = self._weight_decay if weight_decay is None else weight_decay
+        _check_hyper(lr, betas, eps, weight_decay)
+        for flag, on in (("amsgrad", amsgrad), ("maximize", maximize), ("capturable", capturable), ("differentiable", differentiable)):
+            if on:
+                raise NotImplementedError(f"{type(self).__name__}: {flag}=True is not provided")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
+                                      foreach=None, capturable=False, differentiable=False, fused=None,
+                                      decoupled_weight_decay=self._kind == "adamw"))
+
+
+class FusedAdamW(FusedAdam):
+    """torch.optim.AdamW, as FusedAdam is torch.optim.Adam (weight_decay defaults to 1e-2 and is decoupled)."""
+    _kind = "adamw"
+    _cpu_class = torch.optim.AdamW
+    _weight_decay = 1e-2
+
+
+class FusedLamb(_Fused):
+    """`Lamb` (vq_ae.optim.lamb.Lamb) in three fused launches per step on device parameters; the trust ratios are formed on
+    the device, so no step reads a norm back.  Constructor, defaults and ValueErrors are Lamb's."""
+    _kind = "lamb"
+    _cpu_class = Lamb
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0):
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        for i in (0, 1):
+            if not 0.0 <= betas[i] < 1.0:
+                raise ValueError(f"Invalid beta parameter at index {i}: {betas[i]}")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+
+
 _MIRRORED = {"vq_ae.optim.lamb.Lamb": Lamb}
 
 
@@ -104,8 +401,19 @@ class SAM(Optimizer):
             self.base_optimizer = base(self.param_groups, **base_optimizer_overrides)
         self.param_groups = self.base_optimizer.param_groups
 
+    def _fused(self):
+        """The base optimiser where it is a fused one on device tensors: climb and step run in its vqae_optim handle."""
+        base = self.base_optimizer
+        return base if isinstance(base, _Fused) and base._on_device() else None
+
     @torch.no_grad()
     def first_step(self, zero_grad=False):
+        fused = self._fused()
+        if fused is not None:                                      # vqae_optim_sam_first: norm, old_p and climb on the device
+            fused._run(True)
+            if zero_grad:
+                self.zero_grad()
+            return
         norm = self._grad_norm()
         for group in self.param_groups:
             scale = group["rho"] / (norm + 1e-12)
@@ -119,6 +427,12 @@ class SAM(Optimizer):
 
     @torch.no_grad()
     def second_step(self, zero_grad=False):
+        fused = self._fused()
+        if fused is not None:                                      # vqae_optim_step reads the saved weights: restore + step
+            fused.step()
+            if zero_grad:
+                self.zero_grad()
+            return
         for group in self.param_groups:
             for p in group["params"]:
                 if p.grad is None:
@@ -482,4 +796,4 @@ class ClassifierTrainer:
         L.check(L.lib().vqae_classifier_optim_import(self._opt_h, m.ctypes.data, v.ctypes.data, steps.pop(), ops._stream()))
 
 
-__all__ = ["Lamb", "SAM", "ClassifierTrainer", "PARAM_NAMES"]
+__all__ = ["Lamb", "SAM", "FusedAdam", "FusedAdamW", "FusedLamb", "ClassifierTrainer", "PARAM_NAMES"]

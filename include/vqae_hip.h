@@ -693,6 +693,57 @@ int vqae_classifier_loss_grad_ce(vqae_classifier* c, const void* codes_dev, int 
  * are tensors of their own for LAMB's norms at any n_out.  n_out == 1 -> VQAE_ERR_UNSUPPORTED. */
 int vqae_classifier_optim_create_ce(vqae_classifier* c, const vqae_classifier_optim_config* cfg, vqae_classifier_optim** out);
 
+/* ---- Optimiser over any list of tensors: replaces the optimizer.step() of the auto-encoder's own training
+ * (conf/model/optim/: torch.optim.Adam / AdamW, vq_ae/optim/lamb.py, and vq_ae/optim/sam.py around either) for n fp32 tensors
+ * given as device pointers -- the ~1 600 parameters of an Encoder / Decoder, most of them Fixup scalars.  The arithmetic per
+ * element is the classifier optimiser's above (the same code); norms are formed on the device, nothing is read back and
+ * nothing in a step synchronises the host.  vqae_classifier_optim_config holds the hyper-parameters of one param group. ---- */
+/* VQAE_OPTIM_CHUNK: a tensor of more than VQAE_OPTIM_SMALL elements is stepped in pieces of this many, one workgroup and one
+ * row of fp64 partial sums each; a tensor of at most VQAE_OPTIM_SMALL elements is taken whole by one wave, four per workgroup. */
+enum { VQAE_OPTIM_CHUNK = 4096, VQAE_OPTIM_SMALL = 64 };
+typedef struct vqae_optim vqae_optim;
+/* An optimiser over n_tensors tensors of numel[i] elements, tensor i in param group group_of[i] of n_groups, with exp_avg =
+ * exp_avg_sq = 0 and step = 0 for every tensor (lamb.py:69-76; torch.optim.Adam's lazy state).  The state (exp_avg,
+ * exp_avg_sq, SAM's old_p: 12 bytes per element, every tensor on a 16-byte boundary), the sums and a ring of table slots are
+ * allocated here, on the current device, where every later call must run; a step allocates nothing.
+ * Errors, all before any HIP call: null pointers, n_tensors < 1, n_groups < 1, a numel < 1, a group index outside
+ * 0 .. n_groups - 1, per group the checks of vqae_classifier_optim_create (the ValueErrors of lamb.py:34-41 and
+ * torch.optim.Adam, a nan sam_rho), groups that differ in kind or in whether SAM is on (sam_rho >= 0) -> VQAE_ERR_INVALID;
+ * more than 2^31 - 1 elements in all -> VQAE_ERR_UNSUPPORTED. */
+int vqae_optim_create(int n_tensors, const int64_t* numel, const int* group_of, int n_groups,
+                      const vqae_classifier_optim_config* groups, vqae_optim** out);
+void vqae_optim_destroy(vqae_optim* opt);
+/* New hyper-parameters of all n_groups groups from the next call on (an lr schedule's writes to param_groups).  The checks of
+ * create; the kind, and whether SAM is on, cannot change -> VQAE_ERR_INVALID.  No HIP call. */
+int vqae_optim_set(vqae_optim* opt, const vqae_classifier_optim_config* groups);
+/* One optimizer.step().  params_dev / grads_dev are HOST arrays of n_tensors device pointers, each to numel[i] fp32 values
+ * that are 4-byte aligned (16-byte accesses are used where both pointers of a tensor allow); they may differ from call to
+ * call.  A tensor whose gradient pointer is null is skipped as lamb.py:81-82 skips `p.grad is None`: it does not move and
+ * its step count, which is therefore per tensor, does not advance.  Formulas, rounding and bias corrections are those of
+ * vqae_classifier_optim_step, with each tensor's own step count and its group's hyper-parameters.  After
+ * vqae_optim_sam_first this is SAM.second_step (sam.py:49-60): the tensors climbed there are read from their saved values.
+ *   Adam / AdamW  one launch.
+ *   LAMB          three: moments and partial norms (tensors of <= VQAE_OPTIM_SMALL elements are finished there), each
+ *                 larger tensor's rows added in index order, the update with u recomputed from the stored moments.
+ * The pointers and scalars travel in a table written to page-locked memory and copied on `stream` into one of 8 device slots;
+ * an event behind the step's last kernel guards the slot, and the host waits for it only once it is 8 tables ahead.  Sums
+ * are fp64 of fp32 squares in an order fixed by the element counts: results are bit-identical run to run.  A non-finite
+ * gradient is not an error: it propagates as in torch.
+ * Errors, before any HIP call: a null handle or array, a null parameter pointer -> VQAE_ERR_INVALID; then another current
+ * device than create's -> VQAE_ERR_INVALID. */
+int vqae_optim_step(vqae_optim* opt, float* const* params_dev, const float* const* grads_dev, void* stream);
+/* SAM.first_step (sam.py:31-46) with _grad_norm (sam.py:96-111) over the tensors that have a gradient: n = sqrt(sum of
+ * (a * g)^2), a = |p| if sam_adaptive else 1; each is saved and p += (p * p if sam_adaptive else 1) * g * rho / (n + 1e-12),
+ * rho and sam_adaptive being the tensor's group's.  Three launches: partial sums, their total in one workgroup, the climb.
+ * Errors, before any HIP call: as vqae_optim_step, an optimiser created without SAM, a second first step without a step in
+ * between -> VQAE_ERR_INVALID. */
+int vqae_optim_sam_first(vqae_optim* opt, float* const* params_dev, const float* const* grads_dev, void* stream);
+/* state[p]['exp_avg'], ['exp_avg_sq'] and ['step'] of torch.optim's state_dict: two HOST arrays of sum(numel) floats, the
+ * tensors dense in list order (each in the order its elements lie in memory), and n_tensors step counts.  Both synchronise
+ * `stream`.  Import with a SAM first step pending, a step < 0, null pointers -> VQAE_ERR_INVALID, before any HIP call. */
+int vqae_optim_export(vqae_optim* opt, float* exp_avg, float* exp_avg_sq, int64_t* steps, void* stream);
+int vqae_optim_import(vqae_optim* opt, const float* exp_avg, const float* exp_avg_sq, const int64_t* steps, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * 7. Counts of stored code grids -- produces what the reference commits as data under scripts/create_wsi_histograms/
  *    (embedding_idx_histogram_{K}_{split}.npy, histogram_{split}.npy; it ships no program for them) and reads its loss
