@@ -188,6 +188,15 @@ SYMBOLS = {
     "vqae_optim_sam_first": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_void_p]),
     "vqae_optim_export": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_void_p]),
     "vqae_optim_import": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_void_p]),
+    "vqae_fixup_train_workspace_bytes": (c_size_t, [c_int64]),
+    "vqae_fixup_act_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "vqae_fixup_act_backward_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vqae_fixup_out_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "vqae_fixup_out_backward_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p]),
+    "vqae_bicubic_up2_bias_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "vqae_bicubic_up2_backward_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vqae_code_histogram_workspace_bytes": (c_size_t, [c_int, c_int64, c_int, c_int]),
     "vqae_code_histogram": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                     c_void_p, c_void_p]),

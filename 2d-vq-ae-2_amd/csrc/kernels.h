@@ -198,4 +198,9 @@ int vq_write_idx(const int* idx32, int64_t N, void* out, int idx_dtype, hipStrea
 // only, include/vqae_hip.h.  Rows per workgroup and the number of fp64 partial rows are functions of n_rows alone
 // (bw_grid there), which is what makes the gradients bit-identical run to run.
 
+// ---- fixup_train.hip ---------------------------------------------------------------------------
+// The training forms of a Fixup block's non-conv ops (vqae_fixup_act_f32 / _backward, vqae_fixup_out_f32 / _backward,
+// vqae_bicubic_up2_bias_f32, vqae_bicubic_up2_backward_f32 and their workspace size): C ABI only, include/vqae_hip.h.  The
+// grid and the number of fp64 partial rows are functions of the shape alone (ft_grid there).
+
 }  // namespace vqae

@@ -186,6 +186,100 @@ def bicubic_up2(x, pre_bias=0.0):
     return y
 
 
+def _scalar(p):
+    """A one-element parameter as the kernels read it: one fp32 in HBM (no copy for an fp32 Parameter); never read back."""
+    if p is None:
+        return None
+    _need_gpu(p)
+    return p.detach().reshape(-1)[:1].float().contiguous()
+
+
+def _train_ws(n, dev):
+    return torch.empty(L.lib().vqae_fixup_train_workspace_bytes(int(n)), dtype=torch.uint8, device=dev)
+
+
+def fixup_act(x, a, b, halo=0):
+    """y = ELU(x + a) + b on x [B, H, W, C]; a, b one-element device tensors; a None: the plain mode y = x + b.
+    halo = 1: y [B, H + 2, W + 2, C] with the circular wrap written (= F.pad(y, (1, 1, 1, 1), 'circular') in NCHW terms)."""
+    _need_gpu(x)
+    x = x.contiguous()
+    B, H, W, C = x.shape
+    y = torch.empty((B, H + 2 * halo, W + 2 * halo, C), dtype=torch.float32, device=x.device)
+    L.check(L.lib().vqae_fixup_act_f32(_p(x), _p(_scalar(a)), _p(_scalar(b)), int(a is not None), int(halo), B, H, W, C, _p(y),
+                                       _stream()))
+    return y
+
+
+def fixup_act_backward(g, x, a, halo=0, act=True):
+    """-> (g_x [B, H, W, C], g_a [1], g_b [1]) from g (with the halo when halo = 1) and the forward's x and a.  Plain mode
+    (act False; x, a unused): (g, None, g_b) -- the input gradient is the incoming tensor itself."""
+    _need_gpu(g)
+    g = g.contiguous()
+    B, H, W, C = g.shape[0], g.shape[1] - 2 * halo, g.shape[2] - 2 * halo, g.shape[3]
+    dev = g.device
+    g_b = torch.empty(1, dtype=torch.float32, device=dev)
+    ws = _train_ws(g.numel(), dev)
+    if not act:
+        L.check(L.lib().vqae_fixup_act_backward_f32(_p(g), None, None, 0, 0, B, H, W, C, None, None, _p(g_b), _p(ws), _stream()))
+        return g, None, g_b
+    x = x.contiguous()
+    assert tuple(x.shape) == (B, H, W, C), (x.shape, g.shape)
+    g_x = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
+    g_a = torch.empty(1, dtype=torch.float32, device=dev)
+    L.check(L.lib().vqae_fixup_act_backward_f32(_p(g), _p(x), _p(_scalar(a)), 1, int(halo), B, H, W, C, _p(g_x), _p(g_a), _p(g_b),
+                                                _p(ws), _stream()))
+    return g_x, g_a, g_b
+
+
+def fixup_out(t, skip, scale, bias4, bias1d=None):
+    """y = (t * scale + bias4) + (skip [+ bias1d]) on equally shaped dense tensors; the scalars are one-element device tensors."""
+    _need_gpu(t, skip)
+    t, skip = t.contiguous(), skip.contiguous()
+    assert t.shape == skip.shape, (t.shape, skip.shape)
+    y = torch.empty_like(t)
+    L.check(L.lib().vqae_fixup_out_f32(_p(t), _p(skip), _p(_scalar(scale)), _p(_scalar(bias4)), _p(_scalar(bias1d)), t.numel(),
+                                       _p(y), _stream()))
+    return y
+
+
+def fixup_out_backward(g, t, scale):
+    """-> (g_t = g * scale, g_scale [1] = sum g t, g_bias [1] = sum g); the skip gradient is g itself."""
+    _need_gpu(g, t)
+    g, t = g.contiguous(), t.contiguous()
+    assert t.shape == g.shape, (t.shape, g.shape)
+    dev = g.device
+    g_t = torch.empty_like(g)
+    g_scale, g_bias = (torch.empty(1, dtype=torch.float32, device=dev) for _ in range(2))
+    ws = _train_ws(g.numel(), dev)
+    L.check(L.lib().vqae_fixup_out_backward_f32(_p(g), _p(t), _p(_scalar(scale)), g.numel(), _p(g_t), _p(g_scale), _p(g_bias),
+                                                None, _p(ws), _stream()))
+    return g_t, g_scale, g_bias
+
+
+def bicubic_up2_bias(x, pre_bias=None):
+    """bicubic_up2 with pre_bias a one-element device tensor (or None) and any channel count."""
+    _need_gpu(x)
+    x = x.contiguous()
+    B, H, W, C = x.shape
+    y = torch.empty((B, 2 * H, 2 * W, C), dtype=torch.float32, device=x.device)
+    L.check(L.lib().vqae_bicubic_up2_bias_f32(_p(x), B, H, W, C, _p(_scalar(pre_bias)), _p(y), _stream()))
+    return y
+
+
+def bicubic_up2_backward(g, want_bias=True):
+    """The adjoint of bicubic_up2: g [B, 2H, 2W, C] -> (g_x [B, H, W, C], g_pre_bias [1] = sum g_x | None)."""
+    _need_gpu(g)
+    g = g.contiguous()
+    B, OH, OW, C = g.shape
+    assert OH % 2 == 0 and OW % 2 == 0, g.shape
+    dev = g.device
+    g_x = torch.empty((B, OH // 2, OW // 2, C), dtype=torch.float32, device=dev)
+    g_pb = torch.empty(1, dtype=torch.float32, device=dev) if want_bias else None
+    ws = _train_ws(g.numel(), dev)
+    L.check(L.lib().vqae_bicubic_up2_backward_f32(_p(g), B, OH // 2, OW // 2, C, _p(g_x), _p(g_pb), _p(ws), _stream()))
+    return g_x, g_pb
+
+
 def vq_forward(z_flat, embed, commitment_cost=1.0, idx_dtype=torch.int64, want_q=True, want_margin=False, p=4):
     """z_flat [N, D], embed [K, D] -> (q [N, D] | None, idx [N], loss 0-d, margin [N] | None).  p: the Minkowski exponent of the
     reference's cdist = the rank of the quantiser's input (vq.py:97,121-129): 4 for NCHW, 3 / 5 for [B, D, L] / [B, D, d, h, w]."""

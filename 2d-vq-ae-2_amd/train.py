@@ -1,0 +1,356 @@
+"""Training through the Fixup mirrors: every op of a PreActFixupResBlock that is not a convolution (conv_block.py:196-216)
+is a fused HIP forward / backward (csrc/fixup_train.hip) behind a torch.autograd.Function; the convolutions themselves are
+`torch.nn.functional.conv2d` on the block's own `weight` Parameters, whose gradients torch has on ROCm.  Four seams remain
+per block (conv1, conv2, conv3, skip_conv) where a conv-gradient kernel can later replace torch.
+
+    block_forward(block, x)      one block, NCHW in and out, any of the four modes, with or without a skip_conv
+    forward_train(model, x)      VQAE.forward (vq_ae/model.py:41-48) over a vqae_amd.model.VQAE mirror -> (out, (vq_loss,))
+    step(model, batch, loss_f)   VQAE.step (vq_ae/model.py:114-122) -> (out, recon_loss, (vq_loss,))
+
+The functional ops (fixup_act, fixup_add, fixup_out, bicubic_up2) take channel-last tensors [B, H, W, C], like every other
+op of the package.  The graph stays channel-last throughout (the reference trains in channels_last: model.py:124-126): a conv
+sees the NCHW-shaped view of an NHWC tensor, and a conv result that comes back in another layout is copied once
+(`stats["layout_copies"]` counts those copies, `stats["layout_checks"]` the places where one could happen).
+
+The one-element parameters (bias1a .. bias4, scale, bias1c / bias1d) are read by the kernels from device memory and their
+gradients are written to device tensors by fixed-order fp64 sums: a step never synchronises the host for them, and two runs
+of any op here give the same bits.  (A whole step also runs MIOpen's conv gradients, for which no such claim is made.)
+
+Each Function has a restatement in plain torch ops, taken when its tensors are on the CPU: the same forward, and the SAME
+hand-derived backward (the gather-fold of the halo, the bicubic adjoint, the fixed-order sums), which is what
+torch.autograd.gradcheck checks in tests/test_fixup_train_cpu.py.  fp32 only on the device; the Functions are
+once-differentiable.
+"""
+import functools
+
+import torch
+import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
+
+from . import ops
+from .layers.conv_block import PreActFixupResBlock
+from .layers.vq import ProjectedEMAVectorQuantizer2d
+
+stats = {"layout_checks": 0, "layout_copies": 0}
+
+_W75 = (-0.03515625, 0.26171875, 0.87890625, -0.10546875)     # even outputs: inputs m-2 .. m+1, m = o >> 1
+_W25 = (-0.10546875, 0.87890625, 0.26171875, -0.03515625)     # odd outputs:  inputs m-1 .. m+2
+
+
+def _dense(t):
+    stats["layout_checks"] += 1
+    if not t.is_contiguous():
+        stats["layout_copies"] += 1
+        t = t.contiguous()
+    return t
+
+
+def to_nhwc(x):
+    """NCHW-shaped tensor -> its [B, H, W, C] form, a view when x is channels_last already."""
+    return _dense(x.permute(0, 2, 3, 1))
+
+
+def to_nchw(x):
+    """[B, H, W, C] -> the NCHW-shaped (channels_last) view."""
+    return x.permute(0, 3, 1, 2)
+
+
+# ---- plain-torch restatements (CPU) ------------------------------------------------------------------------------------
+def _wrap_index(n, device):
+    return torch.arange(-1, n + 1, device=device) % n
+
+
+def pad_circular_nhwc(y):
+    """F.pad(y, (1, 1, 1, 1), mode='circular') of the NCHW view, on [B, H, W, C]."""
+    return y[:, _wrap_index(y.shape[1], y.device)][:, :, _wrap_index(y.shape[2], y.device)]
+
+
+def fold_circular_nhwc(g):
+    """The adjoint of pad_circular_nhwc: [B, H + 2, W + 2, C] -> [B, H, W, C], every interior pixel the sum of its images."""
+    B, PH, PW, C = g.shape
+    rows = g.new_zeros((B, PH - 2, PW, C)).index_add_(1, _wrap_index(PH - 2, g.device), g)
+    return g.new_zeros((B, PH - 2, PW - 2, C)).index_add_(2, _wrap_index(PW - 2, g.device), rows)
+
+
+def elu_grad(v):
+    """ELU'(v), alpha = 1: 1 where v > 0, exp(v) elsewhere."""
+    return torch.where(v > 0, torch.ones_like(v), torch.exp(v))
+
+
+@functools.lru_cache(maxsize=64)
+def _up2_matrix_cached(n):
+    a = torch.zeros(2 * n, n, dtype=torch.float64)
+    for o in range(2 * n):
+        odd = o & 1
+        base = (o >> 1) - (1 if odd else 2)
+        for k in range(4):
+            a[o, min(max(base + k, 0), n - 1)] += (_W25 if odd else _W75)[k]
+    return a
+
+
+def up2_matrix(n, dtype=torch.float64, device="cpu"):
+    """[2n, n]: the bicubic x2 operator (A = -0.75, align_corners False, clamped indices) along one axis.  Row o holds the sums
+    of o's taps by clamped index; its non-zeros lie in the columns i with 2i - 3 <= o <= 2i + 4, the window the kernel walks."""
+    return _up2_matrix_cached(int(n)).to(device=device, dtype=dtype)
+
+
+def _bicubic_up2_torch(x, pre_bias):
+    ah, aw = up2_matrix(x.shape[1], x.dtype, x.device), up2_matrix(x.shape[2], x.dtype, x.device)
+    v = x if pre_bias is None else x + pre_bias
+    return torch.einsum("oh,bhwc->bowc", ah, torch.einsum("pw,bhwc->bhpc", aw, v))
+
+
+def _bicubic_up2_adjoint_torch(g):
+    ah, aw = up2_matrix(g.shape[1] // 2, g.dtype, g.device), up2_matrix(g.shape[2] // 2, g.dtype, g.device)
+    return torch.einsum("pw,bhpc->bhwc", aw, torch.einsum("oh,bowc->bhwc", ah, g))
+
+
+def _like(g, p):
+    """A [1] sum as the gradient of parameter p."""
+    return g.reshape(p.shape).to(p.dtype)
+
+
+# ---- autograd Functions --------------------------------------------------------------------------------------------------
+class _ActFn(torch.autograd.Function):
+    """y = ELU(x + a) + b (+ circular halo).  Saves x: ELU' from the output, (y - b) + 1, has no correct bits where the ELU
+    saturates, and Adam steps dead channels by the sign of that noise (DESIGN section 16 has both measured distances)."""
+
+    @staticmethod
+    def forward(ctx, x, a, b, halo):
+        if x.is_cuda:
+            y = ops.fixup_act(x.float(), a, b, halo)
+        else:
+            y = F.elu(x + a) + b
+            if halo:
+                y = pad_circular_nhwc(y)
+        ctx.save_for_backward(x, a)
+        ctx.halo, ctx.b = halo, b
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, a = ctx.saved_tensors
+        if g.is_cuda:
+            g_x, g_a, g_b = ops.fixup_act_backward(_dense(g.float()), x, a, ctx.halo)
+        else:
+            if ctx.halo:
+                g = fold_circular_nhwc(g)
+            g_x = g * elu_grad(x + a)
+            g_a, g_b = g_x.sum(), g.sum()
+        return g_x, _like(g_a, a), _like(g_b, ctx.b), None
+
+
+class _AddFn(torch.autograd.Function):
+    """y = x + c, c a one-element parameter.  g_x is the incoming gradient itself; g_c = sum g."""
+
+    @staticmethod
+    def forward(ctx, x, c):
+        ctx.c = c
+        return ops.fixup_act(x.float(), None, c) if x.is_cuda else x + c
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        if g.is_cuda:
+            g, _, g_c = ops.fixup_act_backward(_dense(g.float()), None, None, act=False)
+        else:
+            g_c = g.sum()
+        return g, _like(g_c, ctx.c)
+
+
+class _OutFn(torch.autograd.Function):
+    """y = (t * scale + bias4) + (skip [+ bias1d])."""
+
+    @staticmethod
+    def forward(ctx, t, skip, scale, bias4, bias1d):
+        if t.is_cuda:
+            y = ops.fixup_out(t.float(), _dense(skip.float()), scale, bias4, bias1d)
+        else:
+            y = (t * scale + bias4) + (skip if bias1d is None else skip + bias1d)
+        ctx.save_for_backward(t, scale)
+        ctx.b4, ctx.b1d = bias4, bias1d
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        t, scale = ctx.saved_tensors
+        if g.is_cuda:
+            g = _dense(g.float())
+            g_t, g_scale, g_bias = ops.fixup_out_backward(g, t, scale)
+        else:
+            g_t, g_scale, g_bias = g * scale, (g * t).sum(), g.sum()
+        return (g_t, g, _like(g_scale, scale), _like(g_bias, ctx.b4),
+                _like(g_bias, ctx.b1d) if ctx.b1d is not None else None)
+
+
+class _BicubicFn(torch.autograd.Function):
+    """y = bicubic_x2(x + pre_bias) (nn.Upsample of ResizeConv2D, layers/conv.py:8) and its exact adjoint."""
+
+    @staticmethod
+    def forward(ctx, x, pre_bias):
+        ctx.pb = pre_bias
+        if not x.is_cuda:
+            return _bicubic_up2_torch(x, pre_bias)
+        if pre_bias is None and x.shape[3] % 4 == 0:
+            return ops.bicubic_up2(x.float())                  # the inference kernel: the same sums in the same order
+        return ops.bicubic_up2_bias(x.float(), pre_bias)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        if g.is_cuda:
+            g_x, g_pb = ops.bicubic_up2_backward(_dense(g.float()), want_bias=ctx.pb is not None)
+        else:
+            g_x = _bicubic_up2_adjoint_torch(g)
+            g_pb = g_x.sum()
+        return g_x, _like(g_pb, ctx.pb) if ctx.pb is not None else None
+
+
+def fixup_act(x, a, b, halo=0):
+    """ELU(x + a) + b on [B, H, W, C]; halo = 1: [B, H + 2, W + 2, C] with the circular wrap written."""
+    return _ActFn.apply(x, a, b, int(halo))
+
+
+def fixup_add(x, c):
+    return _AddFn.apply(x, c)
+
+
+def fixup_out(t, skip, scale, bias4, bias1d=None):
+    return _OutFn.apply(t, skip, scale, bias4, bias1d)
+
+
+def bicubic_up2(x, pre_bias=None):
+    return _BicubicFn.apply(x, pre_bias)
+
+
+# ---- blocks and the model ------------------------------------------------------------------------------------------------
+def _conv(t, w, bias=None, stride=1, padding=0):
+    """F.conv2d on a channel-last tensor, channel-last result."""
+    return to_nhwc(F.conv2d(to_nchw(t), w, bias, stride=stride, padding=padding))
+
+
+def block_forward_nhwc(block, x):
+    """conv_block.py:196-216 on [B, H, W, C] with a graph: the fused ops around F.conv2d."""
+    if not isinstance(block, PreActFixupResBlock):
+        raise NotImplementedError(f"training is implemented for Fixup blocks only (no MBConv / BatchNorm training), not "
+                                  f"{type(block).__name__}")
+    mode = block.mode
+    t = fixup_act(x, block.bias1a, block.bias1b)
+    t = _conv(t, block.branch_conv1.weight)
+    if mode in ("same", "out"):                         # 3x3 circular: the activation writes the wrap, the conv pads nothing
+        t = _conv(fixup_act(t, block.bias2a, block.bias2b, halo=1), block.branch_conv2.weight)
+    elif mode == "down":
+        t = _conv(fixup_act(t, block.bias2a, block.bias2b), block.branch_conv2.weight, stride=2)
+    else:                                               # ResizeConv2D: bicubic x2, then 1x1
+        t = _conv(bicubic_up2(fixup_act(t, block.bias2a, block.bias2b)), block.branch_conv2.weight)
+    t = fixup_act(t, block.bias3a, block.bias3b)
+    t = _conv(t, block.branch_conv3.weight)
+    if block.skip_conv is None:
+        return fixup_out(t, x, block.scale, block.bias4)
+    w = block.skip_conv.weight
+    if mode == "up":
+        skip = _conv(bicubic_up2(x, block.bias1c), w)
+    elif mode == "down":
+        skip = _conv(fixup_add(x, block.bias1c), w, stride=2)
+    elif mode == "same":
+        skip = _conv(fixup_add(x, block.bias1c), w)
+    else:                                               # out2d: 3x3, zero padding
+        skip = _conv(fixup_add(x, block.bias1c), w, padding=1)
+    return fixup_out(t, skip, block.scale, block.bias4, block.bias1d)
+
+
+def _compute_dtype(x):
+    """fp32 on the device; fp64 CPU tensors stay fp64 (gradcheck, the fp64 restatement)."""
+    return x if x.dtype == torch.float64 and not x.is_cuda else x.float()
+
+
+def block_forward(block, x):
+    """One PreActFixupResBlock mirror on an NCHW-shaped tensor (channels_last preferred: no copy) -> NCHW-shaped, with a graph."""
+    return to_nchw(block_forward_nhwc(block, to_nhwc(_compute_dtype(x))))
+
+
+def block_forward_torch(block, x):
+    """The same block written with stock torch ops only (F.elu, F.pad, F.interpolate, the same F.conv2d), NCHW-shaped in and
+    out, autograd's own backward: the yardstick of the tests and of tools/bench_fixup_train.py.  No training path calls it."""
+    mode, conv = block.mode, F.conv2d
+    up = lambda t: F.interpolate(t, scale_factor=2, mode="bicubic", align_corners=False)
+    t = conv(F.elu(x + block.bias1a) + block.bias1b, block.branch_conv1.weight)
+    t = F.elu(t + block.bias2a) + block.bias2b
+    if mode in ("same", "out"):
+        t = conv(F.pad(t, (1, 1, 1, 1), mode="circular"), block.branch_conv2.weight)
+    elif mode == "down":
+        t = conv(t, block.branch_conv2.weight, stride=2)
+    else:
+        t = conv(up(t), block.branch_conv2.weight)
+    t = conv(F.elu(t + block.bias3a) + block.bias3b, block.branch_conv3.weight)
+    t = t * block.scale + block.bias4
+    if block.skip_conv is None:
+        return t + x
+    s, w = x + block.bias1c, block.skip_conv.weight
+    if mode == "up":
+        s = conv(up(s), w)
+    elif mode == "down":
+        s = conv(s, w, stride=2)
+    else:
+        s = conv(s, w, padding=1 if mode == "out" else 0)
+    return t + (s + block.bias1d)
+
+
+def _quantize_torch(vq, inputs):
+    """EMAVectorQuantizer.forward (vq.py:96-154; :190-192 for the projected form) in torch ops, for tensors on the CPU: the
+    restatement of the device quantiser, its training-mode bookkeeping (vq.py:47-94) included."""
+    projected = isinstance(vq, ProjectedEMAVectorQuantizer2d)
+    z = F.conv2d(inputs, vq.proj_in.weight, vq.proj_in.bias) if projected else inputs
+    with torch.no_grad():
+        cl = z.permute(0, 2, 3, 1)
+        flat = cl.reshape(-1, vq.embedding_dim)
+        if vq.first_pass and vq.training:
+            vq._init_ema(flat)
+        idx = torch.argmin(torch.cdist(flat, vq.embed, 4, compute_mode="donot_use_mm_for_euclid_dist"), dim=1)
+        q = vq.embed[idx].reshape(cl.shape).permute(0, 3, 1, 2)
+        if vq.training:
+            onehot = F.one_hot(idx, num_classes=vq.num_embeddings).type_as(flat)
+            vq.cluster_size.mul_(vq.decay).add_(onehot.sum(dim=0), alpha=1 - vq.decay)
+            vq.embed_avg.mul_(vq.decay).add_(onehot.T @ flat, alpha=1 - vq.decay)
+            n = vq.cluster_size.sum()
+            size = n * ((vq.cluster_size + vq.laplace_alpha) / (n + vq.num_embeddings * vq.laplace_alpha))
+            vq.embed.copy_(vq.embed_avg / size.unsqueeze(-1))
+    loss = F.mse_loss(z, q) * vq.commitment_cost
+    q = z + (q - z).detach()
+    if projected:
+        q = F.conv2d(q, vq.proj_out.weight, vq.proj_out.bias)
+    return q, idx.reshape(cl.shape[:-1]), loss
+
+
+def forward_train(model, x, return_indices=False):
+    """VQAE.forward (vq_ae/model.py:41-48) over a vqae_amd.model.VQAE mirror, with a graph: -> (out, (vq_loss,)), out NCHW-shaped
+    (channels_last).  The stems are F.conv2d, the blocks block_forward, the quantiser its own trainable mirror (its EMA buffers
+    are updated in training mode, as in the reference)."""
+    enc, dec = model.encoder, model.decoder
+    h = to_nhwc(_compute_dtype(x))
+    h = _conv(h, enc.in_stem.weight, enc.in_stem.bias, padding=1)
+    for level in enc.down_layers[0].layers:
+        for blk in level.layers:
+            h = block_forward_nhwc(blk, h)
+    for blk in enc.pre_enc_layers[0]:
+        h = block_forward_nhwc(blk, h)
+    vq = enc.vq_layers[0]
+    q, idx, vq_loss = vq(to_nchw(h)) if h.is_cuda else _quantize_torch(vq, to_nchw(h))
+    h = to_nhwc(q)
+    for blk in dec.post_enc_layers[0]:
+        h = block_forward_nhwc(blk, h)
+    for level in dec.up_layers[0].layers:
+        for blk in level.layers:
+            h = block_forward_nhwc(blk, h)
+    out = to_nchw(_conv(h, dec.out_stem.weight, dec.out_stem.bias, padding=1))
+    if return_indices:
+        return out, (vq_loss,), (idx,)
+    return out, (vq_loss,)
+
+
+def step(model, batch, loss_f=F.huber_loss):
+    """VQAE.step (vq_ae/model.py:114-122): -> (out, recon_loss, (vq_loss,)); the caller backpropagates recon_loss + sum(vq_loss)."""
+    out, encoding_loss = forward_train(model, batch)
+    return out, loss_f(input=out, target=batch), encoding_loss

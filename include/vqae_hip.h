@@ -745,6 +745,46 @@ int vqae_optim_export(vqae_optim* opt, float* exp_avg, float* exp_avg_sq, int64_
 int vqae_optim_import(vqae_optim* opt, const float* exp_avg, const float* exp_avg_sq, const int64_t* steps, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * 6b. Training forms of the non-conv ops of a Fixup block (conv_block.py:196-216), fp32, NHWC: forward and backward of
+ *     everything between the block's convolutions, which stay with the caller.  Every one-element parameter (bias1a ..
+ *     bias4, scale, bias1c / bias1d) is a pointer to ONE fp32 ON THE DEVICE and every scalar gradient is written to one fp32
+ *     on the device: no call synchronises.  Sums are per-workgroup fp64 partials over a grid that depends on the shape
+ *     only, added in a fixed order by a second launch and rounded to fp32 once; no floating-point atomics: bit-identical
+ *     run to run.  workspace_dev: vqae_fixup_train_workspace_bytes(n) bytes, 8-byte aligned, n = the element count of the
+ *     largest tensor of the call.  Errors, before any HIP call: null pointers, a dimension < 1, a bad act / halo ->
+ *     VQAE_ERR_INVALID; more than 2^40 elements, the plain mode with a halo -> VQAE_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------------- */
+size_t vqae_fixup_train_workspace_bytes(int64_t n_elems);
+/* act != 0: y = ELU(x + *a) + *b (alpha 1, expm1-accurate); act == 0 ("plain"): y = x + *b, a unused.
+ * x [B][H][W][C].  halo == 0: y [B][H][W][C].  halo == 1 (act only): y [B][H+2][W+2][C] with the circular wrap written,
+ * y[b][py][px] = value at ((py-1) mod H, (px-1) mod W): bit for bit F.pad(y, (1, 1, 1, 1), mode='circular'). */
+int vqae_fixup_act_f32(const float* x_dev, const float* a_dev, const float* b_dev, int act, int halo, int batch, int h, int w,
+                       int c, float* y_dev, void* stream);
+/* g: the shape of the forward's y; x [B][H][W][C] and *a: the forward's (NULL for the plain mode).  act: with a halo the
+ * padded gradient is first folded onto the interior (each interior pixel adds its images, gather form), then
+ *   g_x [B][H][W][C] = fold * ELU'(x + *a), ELU'(v) = v > 0 ? 1 : exp(v);   *g_a = sum g_x;   *g_b = sum fold.
+ * plain: *g_b = sum g; g_x is the incoming tensor itself and is not written (pass NULL).  g_a / g_b may be NULL. */
+int vqae_fixup_act_backward_f32(const float* g_dev, const float* x_dev, const float* a_dev, int act, int halo, int batch, int h,
+                                int w, int c, float* g_x_dev, float* g_a_dev, float* g_b_dev, void* workspace_dev,
+                                void* stream);
+/* y = (t * *scale + *bias4) + (skip + *bias1d), or + skip where bias1d_dev is NULL (conv_block.py:208-214), n elements. */
+int vqae_fixup_out_f32(const float* t_dev, const float* skip_dev, const float* scale_dev, const float* bias4_dev,
+                       const float* bias1d_dev, int64_t n, float* y_dev, void* stream);
+/* g_t = g * *scale (one rounding);  *g_scale = sum g * t;  *g_bias4 = *g_bias1d = sum g (each may be NULL).  The skip
+ * gradient is g itself. */
+int vqae_fixup_out_backward_f32(const float* g_dev, const float* t_dev, const float* scale_dev, int64_t n, float* g_t_dev,
+                                float* g_scale_dev, float* g_bias4_dev, float* g_bias1d_dev, void* workspace_dev,
+                                void* stream);
+/* vqae_bicubic_up2_f32 with pre_bias read from the device (NULL: none) and any channel count; per output the same sums
+ * in the same order. */
+int vqae_bicubic_up2_bias_f32(const float* x_dev, int batch, int h, int w, int c, const float* pre_bias_dev, float* y_dev,
+                              void* stream);
+/* The exact adjoint: g [B][2H][2W][C] -> g_x [B][H][W][C], gather form (input pixel i adds, over the outputs 2i-3 .. 2i+4 of
+ * each axis, the sum of that output's taps whose clamped index is i);  *g_pre_bias = sum g_x (may be NULL). */
+int vqae_bicubic_up2_backward_f32(const float* g_dev, int batch, int h, int w, int c, float* g_x_dev, float* g_pre_bias_dev,
+                                  void* workspace_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * 7. Counts of stored code grids -- produces what the reference commits as data under scripts/create_wsi_histograms/
  *    (embedding_idx_histogram_{K}_{split}.npy, histogram_{split}.npy; it ships no program for them) and reads its loss
  *    weights from (conf/model/optional_overrides/loss_f/bce_with_logits_loss_camelyon16_embeddings.yaml: "values taken
