@@ -2,6 +2,8 @@
 builds a graph (vqae_amd.train.block_forward: fused HIP forward / backward for everything that is not a convolution,
 torch's conv2d for the convolutions).  Select through Hydra in the reference's stock Encoder / Decoder with
     _target_: vqae_amd.layers.fixup_train.PreActFixupResBlock
+The keyword `conv1x1` ("torch", the default, or "hip") is train.block_forward's: "hip" runs the 1x1, stride-1 convs and the op
+in front of each as one fused HIP node (csrc/conv1x1_train.hip).
 The inference mirror of conv_block.py is unchanged and still runs under no_grad.
 """
 import torch
@@ -11,5 +13,11 @@ from .conv_block import PreActFixupResBlock as _InferenceBlock
 
 
 class PreActFixupResBlock(_InferenceBlock):
+    def __init__(self, *args, conv1x1: str = "torch", **kwargs):
+        super().__init__(*args, **kwargs)
+        if conv1x1 not in train.CONV1X1_ROUTES:
+            raise ValueError(f"conv1x1 must be one of {train.CONV1X1_ROUTES}, not {conv1x1!r}")
+        self.conv1x1 = conv1x1
+
     def forward(self, inp: torch.Tensor):
-        return train.block_forward(self, inp)
+        return train.block_forward(self, inp, conv1x1=self.conv1x1)

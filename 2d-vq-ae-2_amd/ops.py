@@ -280,6 +280,56 @@ def bicubic_up2_backward(g, want_bias=True):
     return g_x, g_pb
 
 
+def conv1x1_train_supported(cin, cout):
+    """Whether the trainable 1x1 conv kernels take (cin, cout).  A host-side question: needs no GPU."""
+    return bool(L.lib().vqae_conv1x1_train_supported(int(cin), int(cout)))
+
+
+def conv1x1_train_wgrad_run():
+    """R: the longest fp32 accumulation run of the weight gradient, in rows."""
+    return int(L.lib().vqae_conv1x1_train_wgrad_run())
+
+
+def _conv1x1_args(x, w, a, b):
+    w = w.detach().float().contiguous()
+    cout, cin = w.shape[0], w.shape[1]
+    assert w.numel() == cout * cin and x.shape[-1] == cin, (x.shape, w.shape)
+    assert a is None or b is not None, "pre-op: none (a, b None), x + b (a None), ELU(x + a) + b"
+    return w, cin, cout, (0 if b is None else 1 if a is None else 2)
+
+
+def conv1x1_train_forward(x, w, a=None, b=None):
+    """y [..., Co] = u [..., Ci] . w^T, w [Co, Ci(, 1, 1)] as torch stores it; u = x (a, b None), x + b (a None) or
+    ELU(x + a) + b, with a, b one-element device tensors.  u is not materialised."""
+    _need_gpu(x, w)
+    x = x.contiguous()
+    w, cin, cout, pre = _conv1x1_args(x, w, a, b)
+    y = torch.empty(x.shape[:-1] + (cout,), dtype=torch.float32, device=x.device)
+    L.check(L.lib().vqae_conv1x1_train_forward_f32(_p(x), _p(_scalar(a)), _p(_scalar(b)), pre, _p(w), x.numel() // cin, cin,
+                                                   cout, _p(y), _stream()))
+    return y
+
+
+def conv1x1_train_backward(g, x, w, a=None, b=None, need_x=True, need_w=True):
+    """-> (g_x [..., Ci] | None, g_w (w's shape) | None, g_a [1] | None, g_b [1] | None) from g [..., Co] and the forward's
+    x, w, a, b: g_u = g . w, g_x = g_u * ELU'(x + a) (g_u without an activation), g_a = sum g_x, g_b = sum g_u,
+    g_w = g^T . u with u recomputed from x."""
+    _need_gpu(g, x, w)
+    g, x = g.contiguous(), x.contiguous()
+    wc, cin, cout, pre = _conv1x1_args(x, w, a, b)
+    m = x.numel() // cin
+    assert g.shape[-1] == cout and g.numel() == m * cout, (g.shape, x.shape, w.shape)
+    dev = g.device
+    g_x = torch.empty_like(x) if need_x else None
+    g_w = torch.empty(w.shape, dtype=torch.float32, device=dev) if need_w else None
+    g_a = torch.empty(1, dtype=torch.float32, device=dev) if pre == 2 else None
+    g_b = torch.empty(1, dtype=torch.float32, device=dev) if pre >= 1 else None
+    ws = torch.empty(L.lib().vqae_conv1x1_train_workspace_bytes(m, cin, cout), dtype=torch.uint8, device=dev)
+    L.check(L.lib().vqae_conv1x1_train_backward_f32(_p(g), _p(x), _p(_scalar(a)), _p(_scalar(b)), pre, _p(wc), m, cin, cout,
+                                                    _p(g_x), _p(g_w), _p(g_a), _p(g_b), _p(ws), _stream()))
+    return g_x, g_w, g_a, g_b
+
+
 def vq_forward(z_flat, embed, commitment_cost=1.0, idx_dtype=torch.int64, want_q=True, want_margin=False, p=4):
     """z_flat [N, D], embed [K, D] -> (q [N, D] | None, idx [N], loss 0-d, margin [N] | None).  p: the Minkowski exponent of the
     reference's cdist = the rank of the quantiser's input (vq.py:97,121-129): 4 for NCHW, 3 / 5 for [B, D, L] / [B, D, d, h, w]."""

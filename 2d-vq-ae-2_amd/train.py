@@ -1,11 +1,20 @@
 """Training through the Fixup mirrors: every op of a PreActFixupResBlock that is not a convolution (conv_block.py:196-216)
 is a fused HIP forward / backward (csrc/fixup_train.hip) behind a torch.autograd.Function; the convolutions themselves are
-`torch.nn.functional.conv2d` on the block's own `weight` Parameters, whose gradients torch has on ROCm.  Four seams remain
-per block (conv1, conv2, conv3, skip_conv) where a conv-gradient kernel can later replace torch.
+`torch.nn.functional.conv2d` on the block's own `weight` Parameters, whose gradients torch has on ROCm.  Of the four seams
+per block (conv1, conv2, conv3, skip_conv) the 1x1, stride-1 ones have a kernel of ours behind the keyword `conv1x1`:
+
+    conv1x1="torch"  (default)   every conv is F.conv2d: the graph this module has always built, op for op
+    conv1x1="hip"                every 1x1, stride-1 conv whose channel counts csrc/conv1x1_train.hip takes (multiples of 8 up
+                                 to 256) is ONE node together with the op in front of it: fixup_act + conv1 / conv3,
+                                 fixup_add + the skip conv of a 'same' block, the 1x1 after the bicubic of an 'up' block.
+                                 Other shapes (Co = 3 of an 'out' block) take the torch route, counted in
+                                 stats["conv1x1_fallbacks"]; stats["conv1x1_hip"] counts the fused nodes.
+The 3x3 convs, the 2x2 stride-2 convs, the stems and the quantiser's projections stay with torch.
 
     block_forward(block, x)      one block, NCHW in and out, any of the four modes, with or without a skip_conv
     forward_train(model, x)      VQAE.forward (vq_ae/model.py:41-48) over a vqae_amd.model.VQAE mirror -> (out, (vq_loss,))
     step(model, batch, loss_f)   VQAE.step (vq_ae/model.py:114-122) -> (out, recon_loss, (vq_loss,))
+    conv1x1(x, w, a, b)          the fused node on [B, H, W, Ci]
 
 The functional ops (fixup_act, fixup_add, fixup_out, bicubic_up2) take channel-last tensors [B, H, W, C], like every other
 op of the package.  The graph stays channel-last throughout (the reference trains in channels_last: model.py:124-126): a conv
@@ -14,7 +23,8 @@ sees the NCHW-shaped view of an NHWC tensor, and a conv result that comes back i
 
 The one-element parameters (bias1a .. bias4, scale, bias1c / bias1d) are read by the kernels from device memory and their
 gradients are written to device tensors by fixed-order fp64 sums: a step never synchronises the host for them, and two runs
-of any op here give the same bits.  (A whole step also runs MIOpen's conv gradients, for which no such claim is made.)
+of any op here give the same bits -- under conv1x1="hip" the 1x1 convs and their weight gradients included.  (A whole step
+also runs MIOpen's gradients of the remaining convs, for which no such claim is made.)
 
 Each Function has a restatement in plain torch ops, taken when its tensors are on the CPU: the same forward, and the SAME
 hand-derived backward (the gather-fold of the halo, the bicubic adjoint, the fixed-order sums), which is what
@@ -31,7 +41,8 @@ from . import ops
 from .layers.conv_block import PreActFixupResBlock
 from .layers.vq import ProjectedEMAVectorQuantizer2d
 
-stats = {"layout_checks": 0, "layout_copies": 0}
+stats = {"layout_checks": 0, "layout_copies": 0, "conv1x1_hip": 0, "conv1x1_fallbacks": 0}
+CONV1X1_ROUTES = ("torch", "hip")
 
 _W75 = (-0.03515625, 0.26171875, 0.87890625, -0.10546875)     # even outputs: inputs m-2 .. m+1, m = o >> 1
 _W25 = (-0.10546875, 0.87890625, 0.26171875, -0.03515625)     # odd outputs:  inputs m-1 .. m+2
@@ -208,6 +219,55 @@ class _BicubicFn(torch.autograd.Function):
         return g_x, _like(g_pb, ctx.pb) if ctx.pb is not None else None
 
 
+class _Conv1x1Fn(torch.autograd.Function):
+    """y = u . w^T on [B, H, W, Ci], w [Co, Ci, 1, 1], with the op in front of the conv folded in: u = x (a, b None), x + b
+    (a None) or ELU(x + a) + b.  Saves x, a, b, w -- not u: the backward recomputes it for g_w and takes ELU' from x + a."""
+
+    @staticmethod
+    def forward(ctx, x, w, a, b):
+        if x.is_cuda:
+            y = ops.conv1x1_train_forward(x.float(), w, a, b)
+        else:
+            y = to_nhwc(F.conv2d(to_nchw(_pre_op_torch(x, a, b)), w))
+        ctx.save_for_backward(x, w, *(t for t in (a, b) if t is not None))
+        ctx.has = (a is not None, b is not None)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, w, *ab = ctx.saved_tensors
+        a = ab[0] if ctx.has[0] else None
+        b = ab[-1] if ctx.has[1] else None
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if g.is_cuda:
+            g_x, g_w, g_a, g_b = ops.conv1x1_train_backward(_dense(g.float()), x.float(), w, a, b, need_x, need_w)
+        else:
+            w2 = w.reshape(w.shape[0], w.shape[1])
+            g_u = g @ w2
+            g_x = g_u * elu_grad(x + a) if a is not None else g_u
+            g_a, g_b = g_x.sum(), g_u.sum()
+            g_w = None
+            if need_w:
+                u = _pre_op_torch(x, a, b)
+                g_w = (g.reshape(-1, g.shape[-1]).t() @ u.reshape(-1, u.shape[-1])).reshape(w.shape)
+        return (g_x if need_x else None, g_w.to(w.dtype) if need_w else None, _like(g_a, a) if a is not None else None,
+                _like(g_b, b) if b is not None else None)
+
+
+def _pre_op_torch(x, a, b):
+    if b is None:
+        return x
+    return x + b if a is None else F.elu(x + a) + b
+
+
+def conv1x1(x, w, a=None, b=None):
+    """A 1x1, stride-1 conv on [B, H, W, Ci] -> [B, H, W, Co], w [Co, Ci, 1, 1], of ELU(x + a) + b (a None: of x + b; both
+    None: of x) as ONE node: csrc/conv1x1_train.hip on the device, a plain-torch restatement on CPU tensors."""
+    assert a is None or b is not None
+    return _Conv1x1Fn.apply(x, w, a, b)
+
+
 def fixup_act(x, a, b, halo=0):
     """ELU(x + a) + b on [B, H, W, C]; halo = 1: [B, H + 2, W + 2, C] with the circular wrap written."""
     return _ActFn.apply(x, a, b, int(halo))
@@ -231,31 +291,50 @@ def _conv(t, w, bias=None, stride=1, padding=0):
     return to_nhwc(F.conv2d(to_nchw(t), w, bias, stride=stride, padding=padding))
 
 
-def block_forward_nhwc(block, x):
-    """conv_block.py:196-216 on [B, H, W, C] with a graph: the fused ops around F.conv2d."""
+def _route(conv1x1):
+    if conv1x1 not in CONV1X1_ROUTES:
+        raise ValueError(f"conv1x1 must be one of {CONV1X1_ROUTES}, not {conv1x1!r}")
+    return conv1x1 == "hip"
+
+
+def _pre_conv1x1(hip, x, a, b, w):
+    """The 1x1, stride-1 conv of ELU(x + a) + b (a None: x + b; both None: x).  hip: one fused node where the kernels take the
+    shape; any other shape takes the torch route and is counted."""
+    if hip:
+        if tuple(w.shape[2:]) == (1, 1) and ops.conv1x1_train_supported(w.shape[1], w.shape[0]):
+            stats["conv1x1_hip"] += 1
+            return conv1x1(x, w, a, b)
+        stats["conv1x1_fallbacks"] += 1
+    if b is not None:
+        x = fixup_add(x, b) if a is None else fixup_act(x, a, b)
+    return _conv(x, w)
+
+
+def block_forward_nhwc(block, x, conv1x1="torch"):
+    """conv_block.py:196-216 on [B, H, W, C] with a graph: the fused ops around F.conv2d.  conv1x1 = "hip": every 1x1, stride-1
+    conv the kernels support is one node with the op in front of it (csrc/conv1x1_train.hip); "torch": F.conv2d throughout."""
     if not isinstance(block, PreActFixupResBlock):
         raise NotImplementedError(f"training is implemented for Fixup blocks only (no MBConv / BatchNorm training), not "
                                   f"{type(block).__name__}")
+    hip = _route(conv1x1)
     mode = block.mode
-    t = fixup_act(x, block.bias1a, block.bias1b)
-    t = _conv(t, block.branch_conv1.weight)
+    t = _pre_conv1x1(hip, x, block.bias1a, block.bias1b, block.branch_conv1.weight)
     if mode in ("same", "out"):                         # 3x3 circular: the activation writes the wrap, the conv pads nothing
         t = _conv(fixup_act(t, block.bias2a, block.bias2b, halo=1), block.branch_conv2.weight)
     elif mode == "down":
         t = _conv(fixup_act(t, block.bias2a, block.bias2b), block.branch_conv2.weight, stride=2)
     else:                                               # ResizeConv2D: bicubic x2, then 1x1
-        t = _conv(bicubic_up2(fixup_act(t, block.bias2a, block.bias2b)), block.branch_conv2.weight)
-    t = fixup_act(t, block.bias3a, block.bias3b)
-    t = _conv(t, block.branch_conv3.weight)
+        t = _pre_conv1x1(hip, bicubic_up2(fixup_act(t, block.bias2a, block.bias2b)), None, None, block.branch_conv2.weight)
+    t = _pre_conv1x1(hip, t, block.bias3a, block.bias3b, block.branch_conv3.weight)
     if block.skip_conv is None:
         return fixup_out(t, x, block.scale, block.bias4)
     w = block.skip_conv.weight
     if mode == "up":
-        skip = _conv(bicubic_up2(x, block.bias1c), w)
+        skip = _pre_conv1x1(hip, bicubic_up2(x, block.bias1c), None, None, w)
     elif mode == "down":
         skip = _conv(fixup_add(x, block.bias1c), w, stride=2)
     elif mode == "same":
-        skip = _conv(fixup_add(x, block.bias1c), w)
+        skip = _pre_conv1x1(hip, x, None, block.bias1c, w)
     else:                                               # out2d: 3x3, zero padding
         skip = _conv(fixup_add(x, block.bias1c), w, padding=1)
     return fixup_out(t, skip, block.scale, block.bias4, block.bias1d)
@@ -266,9 +345,9 @@ def _compute_dtype(x):
     return x if x.dtype == torch.float64 and not x.is_cuda else x.float()
 
 
-def block_forward(block, x):
+def block_forward(block, x, conv1x1="torch"):
     """One PreActFixupResBlock mirror on an NCHW-shaped tensor (channels_last preferred: no copy) -> NCHW-shaped, with a graph."""
-    return to_nchw(block_forward_nhwc(block, to_nhwc(_compute_dtype(x))))
+    return to_nchw(block_forward_nhwc(block, to_nhwc(_compute_dtype(x)), conv1x1=conv1x1))
 
 
 def block_forward_torch(block, x):
@@ -324,33 +403,34 @@ def _quantize_torch(vq, inputs):
     return q, idx.reshape(cl.shape[:-1]), loss
 
 
-def forward_train(model, x, return_indices=False):
+def forward_train(model, x, return_indices=False, conv1x1="torch"):
     """VQAE.forward (vq_ae/model.py:41-48) over a vqae_amd.model.VQAE mirror, with a graph: -> (out, (vq_loss,)), out NCHW-shaped
     (channels_last).  The stems are F.conv2d, the blocks block_forward, the quantiser its own trainable mirror (its EMA buffers
-    are updated in training mode, as in the reference)."""
+    are updated in training mode, as in the reference).  conv1x1: the route of the blocks' 1x1 convs (block_forward_nhwc)."""
+    _route(conv1x1)
     enc, dec = model.encoder, model.decoder
     h = to_nhwc(_compute_dtype(x))
     h = _conv(h, enc.in_stem.weight, enc.in_stem.bias, padding=1)
     for level in enc.down_layers[0].layers:
         for blk in level.layers:
-            h = block_forward_nhwc(blk, h)
+            h = block_forward_nhwc(blk, h, conv1x1=conv1x1)
     for blk in enc.pre_enc_layers[0]:
-        h = block_forward_nhwc(blk, h)
+        h = block_forward_nhwc(blk, h, conv1x1=conv1x1)
     vq = enc.vq_layers[0]
     q, idx, vq_loss = vq(to_nchw(h)) if h.is_cuda else _quantize_torch(vq, to_nchw(h))
     h = to_nhwc(q)
     for blk in dec.post_enc_layers[0]:
-        h = block_forward_nhwc(blk, h)
+        h = block_forward_nhwc(blk, h, conv1x1=conv1x1)
     for level in dec.up_layers[0].layers:
         for blk in level.layers:
-            h = block_forward_nhwc(blk, h)
+            h = block_forward_nhwc(blk, h, conv1x1=conv1x1)
     out = to_nchw(_conv(h, dec.out_stem.weight, dec.out_stem.bias, padding=1))
     if return_indices:
         return out, (vq_loss,), (idx,)
     return out, (vq_loss,)
 
 
-def step(model, batch, loss_f=F.huber_loss):
+def step(model, batch, loss_f=F.huber_loss, conv1x1="torch"):
     """VQAE.step (vq_ae/model.py:114-122): -> (out, recon_loss, (vq_loss,)); the caller backpropagates recon_loss + sum(vq_loss)."""
-    out, encoding_loss = forward_train(model, batch)
+    out, encoding_loss = forward_train(model, batch, conv1x1=conv1x1)
     return out, loss_f(input=out, target=batch), encoding_loss

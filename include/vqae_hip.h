@@ -785,6 +785,37 @@ int vqae_bicubic_up2_backward_f32(const float* g_dev, int batch, int h, int w, i
                                   void* workspace_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * 6c. Trainable 1x1, stride-1 convolutions of a Fixup block (conv_block.py:196-216: branch_conv1, branch_conv3, the 1x1 after
+ *     the bicubic of 'up' blocks, skip_conv of 'same' blocks; conf/model/layers/conv_layer/proj2d.yaml: kernel 1, no bias), fp32,
+ *     NHWC, with the element-wise op in front of the conv folded into the operand load:
+ *         m = B H W rows;  x [m][cin];  w [cout][cin] exactly as torch stores a [cout, cin, 1, 1] weight (no packing);  y [m][cout]
+ *         pre = 0: u = x      pre = 1: u = x + *b      pre = 2: u = ELU(x + *a) + *b (alpha 1, expm1-accurate)
+ *         y = u . w^T       (u is never written to memory)
+ *     a, b: pointers to ONE fp32 ON THE DEVICE (a unused for pre < 2, b for pre < 1); no call synchronises.  All products
+ *     run on the fp32-input MFMA.  Grids depend on (m, cin, cout) only, no floating-point atomics: bit-identical run to run.
+ *     Supported: cin, cout multiples of 8 in 8 .. 256, any m >= 1; x, w, y and the gradients 16-byte aligned.
+ *     Errors, before any HIP call: null pointers, m < 1, pre outside 0 .. 2, misaligned pointers -> VQAE_ERR_INVALID; any other
+ *     cin / cout -> VQAE_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------------- */
+int vqae_conv1x1_train_supported(int cin, int cout);
+/* Bytes of workspace of the backward (0 for an unsupported shape or m < 1): P fp64 partials of g_w with P <= 256 and
+ * P cin cout <= 2^20 (at most 8 MiB whatever m is), plus 1024 rows of the scalar sums.  8-byte aligned. */
+size_t vqae_conv1x1_train_workspace_bytes(int64_t m, int cin, int cout);
+/* R: the longest fp32 accumulation run of g_w, in rows.  Longer row ranges are added run by run in fp64. */
+int vqae_conv1x1_train_wgrad_run(void);
+int vqae_conv1x1_train_forward_f32(const float* x_dev, const float* a_dev, const float* b_dev, int pre, const float* w_dev,
+                                   int64_t m, int cin, int cout, float* y_dev, void* stream);
+/* From g [m][cout] and the forward's x, a, b, w:
+ *   g_u = g . w;   g_x [m][cin] = g_u * ELU'(x + *a) for pre = 2 (ELU'(v) = v > 0 ? 1 : exp(v)), g_u otherwise;
+ *   *g_a = sum g_x (pre = 2);   *g_b = sum g_u (pre >= 1);   g_w [cout][cin] = sum_m g[m][co] u[m][ci], u recomputed from x.
+ * g_x, g_w, g_a, g_b may each be NULL: what is not asked for is not computed (g_a / g_b are not written for a pre without
+ * them).  g_w: fp32 accumulation over runs of at most R rows, the runs added in fp64 in index order, rounded to fp32 once;
+ * the scalar sums in fp64 in a fixed order, rounded once. */
+int vqae_conv1x1_train_backward_f32(const float* g_dev, const float* x_dev, const float* a_dev, const float* b_dev, int pre,
+                                    const float* w_dev, int64_t m, int cin, int cout, float* g_x_dev, float* g_w_dev,
+                                    float* g_a_dev, float* g_b_dev, void* workspace_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * 7. Counts of stored code grids -- produces what the reference commits as data under scripts/create_wsi_histograms/
  *    (embedding_idx_histogram_{K}_{split}.npy, histogram_{split}.npy; it ships no program for them) and reads its loss
  *    weights from (conf/model/optional_overrides/loss_f/bce_with_logits_loss_camelyon16_embeddings.yaml: "values taken
