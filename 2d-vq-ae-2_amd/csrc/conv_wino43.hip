@@ -34,6 +34,14 @@
 // accumulator sees the MFMAs of the 8-row form in their order: the results are that form's bit for bit (tests/test_wino43_wide_gpu.py).
 // V is [nu][32 tiles][3 C + 8] bf16 = 150 528 B, T [256 px][132] fp32 overlays it; both exceed the 64 KiB a DS offset field
 // reaches, hence the second, opaque bases.  H % 8 == 0 only, VQAE_W43_SPLIT=0, C = 64 and C = 256 keep the 8-row kernels.
+// Wide transform: every input column once per pass.  Neighbouring tile columns share two of their six input columns, and the 8-row
+// transform (thread = tile column x channel quad, six columns each) fetches both copies from L2.  In the wide form a wave holds all
+// eight tile columns of a band for 32 channels (lane = 8 tile column + quad), a thread loads columns 4 t - 1 .. 4 t + 2 only (four
+// batches of 2 columns per pass instead of six, two in flight) and, after the row combination, takes columns 4 t + 3, 4 t + 4 from the
+// lane 8 further on (ds_bpermute_b32, 8 dwords per tile row; the rotation over the wave is the wrap in x): the neighbour formed them
+// from the same raw values through the same fma chain, so V is bit for bit what it was.  V slots are permuted within a band
+// (4 (t & 3) + 2 (t >> 2) + tile row) to keep the transform's ds_write_b64 free of bank conflicts under the new lane order; the GEMM
+// reads slot li, the tails map li back to (tile row, tile column).  tests/test_wino43_columns_gpu.py; DESIGN.md section 8.
 #include "kernels.h"
 #include "mfma.h"
 
@@ -151,13 +159,17 @@ void wino43_trunk_kernel(const W43K p) {
     const float* const xim = p.t1 + (int64_t)img * p.H * W * C;
 
     // ---- transform geometry: thread -> channel quad cg, tile column tj, both tile rows ------------------------------------
-    // (WIDE: tj = 8 band + tile column; the band is uniform per wave, and its halo rows may lie in the other band or workgroup)
-    const int cg = tid % C4, tj = tid / C4;
-    const int tjc = WIDE ? tj & (TC - 1) : tj, band = WIDE ? wave >> 2 : 0;
-    unsigned coff[6];                                                // per-lane byte offsets of the unit's 6 columns
+    // (WIDE: the band is uniform per wave, and its halo rows may lie in the other band or workgroup.  A wave covers all eight tile
+    // columns of its band for 32 channels -- lane = 8 tile column + channel quad of the 32, wave = 4 band + channel quarter -- and a
+    // thread loads only the first four of its six columns: the other two are the first two of the next tile column, which the lane 8
+    // further on holds row-combined after combine(); the rotation over the whole wave is the circular wrap in x (W = 32).)
+    const int cg = tid % C4, tj = tid / C4;                          // (the tails' row-coalesced view in every form)
+    const int xcg = WIDE ? 8 * (wave & 3) + (lane & 7) : cg, tjc = WIDE ? lane >> 3 : tj, band = WIDE ? wave >> 2 : 0;
+    constexpr int NCOL = WIDE ? 4 : 6, NB = NCOL / 2;                // columns a thread loads; batches (of 2 columns) per tile row
+    unsigned coff[NCOL];                                             // per-lane byte offsets of the unit's columns
     int roff[2][6];                                                  // uniform float offsets of its 6 rows
 #pragma unroll
-    for (int j = 0; j < 6; ++j) coff[j] = (unsigned)((((4 * tjc - 1 + j) & (W - 1)) * C + 4 * cg) * 4);
+    for (int j = 0; j < NCOL; ++j) coff[j] = (unsigned)((((4 * tjc - 1 + j) & (W - 1)) * C + 4 * xcg) * 4);
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -170,9 +182,9 @@ void wino43_trunk_kernel(const W43K p) {
     // One pass's input: per tile row s, column pair cp: rows (0, 2, 4) [KIND 0], (1, 3, 5) [KIND 5] or (1, 2, 3, 4) [KIND 1].
     f32x4 d[2][4][2];                                                // two batches in flight
     f32x4 w[6];                                                      // row-combined columns of the unit in work
-    auto issue = [&](auto kind_c, int k) __attribute__((always_inline)) {                           // batch k = 3 s + cp (compile-time after unrolling)
+    auto issue = [&](auto kind_c, int k) __attribute__((always_inline)) {                           // batch k = NB s + cp (compile-time after unrolling)
         constexpr int KIND = decltype(kind_c)::value;
-        const int s = k / 3, cp = k % 3, bf = k & 1;
+        const int s = k / NB, cp = k % NB, bf = k & 1;
 #pragma unroll
         for (int i = 0; i < (KIND == 1 ? 4 : 3); ++i) {
             const int row = KIND == 0 ? 2 * i : (KIND == 5 ? 2 * i + 1 : i + 1);
@@ -182,16 +194,33 @@ void wino43_trunk_kernel(const W43K p) {
     };
     auto combine = [&](auto kind_c, int k, float c1, float c2, float c3) __attribute__((always_inline)) {
         constexpr int KIND = decltype(kind_c)::value;
-        const int cp = k % 3, bf = k & 1;
+        const int cp = k % NB, bf = k & 1;
 #pragma unroll
         for (int jj = 0; jj < 2; ++jj) {
             if (KIND == 1) w[2 * cp + jj] = fma4(d[bf][0][jj], c1, fma4(d[bf][1][jj], c2, fma4(d[bf][2][jj], c3, d[bf][3][jj])));
             else w[2 * cp + jj] = fma4(d[bf][0][jj], 4.f, fma4(d[bf][1][jj], -5.f, d[bf][2][jj]));     // B^T rows 0 / 5: [4 0 -5 0 1 0]
         }
     };
+    // WIDE: columns 4, 5 of the unit = columns 0, 1 of the next tile column (the same raw values through the same fma chain, so the
+    // same bits), from the lane 8 further on: 8 ds_bpermute_b32 per tile row, no LDS memory, no barrier
+    auto exchange = [&]() __attribute__((always_inline)) {
+        const int nb = 4 * ((lane + 8) & 63);
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float mine = w[jj][e];                         // (a scalar copy: __builtin_bit_cast of a vector element reads element 0)
+                w[4 + jj][e] = __int_as_float(__builtin_amdgcn_ds_bpermute(nb, __float_as_int(mine)));
+            }
+    };
+    // V slot of tile (s, tile column) within its band.  WIDE: 4 (tjc & 3) + 2 (tjc >> 2) + s, so that neighbouring tile columns lie
+    // 4 slots = 16 banks (LDVB / 2 = 196 dwords = 4 mod 32) apart, next to the 16 banks of a lane group's eight channel quads: the
+    // 16 lanes of a ds_write_b64 group (two tile columns x eight quads) cover all 32 banks once.  The GEMM reads slot li, whatever tile
+    // that is; the tails invert the permutation (ty, tx).
     auto columns = [&](int s) __attribute__((always_inline)) {                                      // (w B)[nu] -> V[nu][tile][c]
-        float* const dst = lds + (16 * band + s * TC + tjc) * LDT + 4 * cg;
-        __bf16* const dsb = reinterpret_cast<__bf16*>(lds) + (16 * band + s * TC + tjc) * LDVB + 4 * cg;
+        const int slot = WIDE ? 4 * (tjc & 3) + 2 * (tjc >> 2) + s : s * TC + tjc;
+        float* const dst = lds + (16 * band + slot) * LDT + 4 * xcg;
+        __bf16* const dsb = reinterpret_cast<__bf16*>(lds) + (16 * band + slot) * LDVB + 4 * xcg;
         // WIDE: V spans 147 KiB and a DS instruction's offset field 64 KiB, so nu = 3..5 go through a second base, opaque so that
         // hipcc forms it once per use instead of keeping (and spilling) one address per access
         int vhi = 3 * TILES * LDVB;
@@ -239,14 +268,17 @@ void wino43_trunk_kernel(const W43K p) {
         constexpr int NEXT = decltype(next_c)::value;                // kind of the following pass (-1: none)
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int j = 0; j < 6; ++j) asm volatile("" : "+v"(coff[j]));    // opaque per pass (as uoff below): no hoisted 64-bit address per (row, column)
+        for (int j = 0; j < NCOL; ++j) asm volatile("" : "+v"(coff[j]));  // opaque per pass (as uoff below): no hoisted 64-bit address per (row, column)
         if (EARLY < 1) issue(kind_c, 0);                             // (EARLY batches of this pass went out before the previous pass's fold)
         if (EARLY < 2) issue(kind_c, 1);
 #pragma unroll
-        for (int k = 0; k < 6; ++k) {
+        for (int k = 0; k < 2 * NB; ++k) {
             combine(kind_c, k, c1, c2, c3);
-            if (k % 3 == 2) columns(k / 3);                          // before the next request: w, the column temporaries and TWO batches in flight do not fit
-            if (k + 2 < 6) issue(kind_c, k + 2);
+            if (k % NB == NB - 1) {
+                if constexpr (WIDE) exchange();
+                columns(k / NB);                                     // before the next request: w, the column temporaries and TWO batches in flight do not fit
+            }
+            if (k + 2 < 2 * NB) issue(kind_c, k + 2);
         }
         __builtin_amdgcn_sched_barrier(0);                            // (the weight loads below must not rise into the transform: registers)
         f32x4 Z[4][2];
@@ -471,7 +503,8 @@ void wino43_trunk_kernel(const W43K p) {
     const int wm = wave / WN, wn = wave % WN;                        // MI * 32 pixels x NI * 32 channels per wave
     const int tj0 = tj;                                              // row-coalesced view: thread (cg, tj0) owns pixels tj0 + RP i of the half
     [[maybe_unused]] float* const trow = WIDE ? nullptr : T + tj0 * LDT + 4 * cg;   // 8-row forms; WIDE: tr() below
-    const int ty = (16 * tg + li) / TC, tx = (16 * tg + li) % TC;
+    // tile row / column of the lane's Y (WIDE: li is the permuted V slot of columns())
+    const int ty = WIDE ? li & 1 : (16 * tg + li) / TC, tx = WIDE ? 4 * ((li >> 1) & 1) + (li >> 2) : (16 * tg + li) % TC;
     f32x4 bt[RT][NI];
     f32x4 bs0[2][NI], bs1[NI], bs2[NI];                              // split form: the hi plane of two k-slices, mid / lo of one
     auto tail_prefetch = [&](const float* __restrict__ wsrc) __attribute__((always_inline)) {
