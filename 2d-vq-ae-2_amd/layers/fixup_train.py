@@ -3,7 +3,8 @@ builds a graph (vqae_amd.train.block_forward: fused HIP forward / backward for e
 torch's conv2d for the convolutions).  Select through Hydra in the reference's stock Encoder / Decoder with
     _target_: vqae_amd.layers.fixup_train.PreActFixupResBlock
 The keyword `conv1x1` ("torch", the default, or "hip") is train.block_forward's: "hip" runs the 1x1, stride-1 convs and the op
-in front of each as one fused HIP node (csrc/conv1x1_train.hip).
+in front of each as one fused HIP node (csrc/conv1x1_train.hip).  The independent keyword `conv_down` ("torch" | "hip") does the
+same for the two 2x2, stride-2 convs of a 'down' block (csrc/conv_down_train.hip).
 The inference mirror of conv_block.py is unchanged and still runs under no_grad.
 """
 import torch
@@ -13,11 +14,13 @@ from .conv_block import PreActFixupResBlock as _InferenceBlock
 
 
 class PreActFixupResBlock(_InferenceBlock):
-    def __init__(self, *args, conv1x1: str = "torch", **kwargs):
+    def __init__(self, *args, conv1x1: str = "torch", conv_down: str = "torch", **kwargs):
         super().__init__(*args, **kwargs)
         if conv1x1 not in train.CONV1X1_ROUTES:
             raise ValueError(f"conv1x1 must be one of {train.CONV1X1_ROUTES}, not {conv1x1!r}")
-        self.conv1x1 = conv1x1
+        if conv_down not in train.CONV_DOWN_ROUTES:
+            raise ValueError(f"conv_down must be one of {train.CONV_DOWN_ROUTES}, not {conv_down!r}")
+        self.conv1x1, self.conv_down = conv1x1, conv_down
 
     def forward(self, inp: torch.Tensor):
-        return train.block_forward(self, inp, conv1x1=self.conv1x1)
+        return train.block_forward(self, inp, conv1x1=self.conv1x1, conv_down=self.conv_down)

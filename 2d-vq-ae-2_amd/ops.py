@@ -330,6 +330,71 @@ def conv1x1_train_backward(g, x, w, a=None, b=None, need_x=True, need_w=True):
     return g_x, g_w, g_a, g_b
 
 
+def conv_down_train_supported(cin, cout):
+    """Whether the trainable 2x2, stride-2 conv kernels take (cin, cout); H and W must be even besides.  Needs no GPU."""
+    return bool(L.lib().vqae_conv_down_train_supported(int(cin), int(cout)))
+
+
+def conv_down_train_wgrad_run():
+    """R: the longest fp32 accumulation run of the weight gradient, in rows."""
+    return int(L.lib().vqae_conv_down_train_wgrad_run())
+
+
+def _conv_down_args(x, w, a, b):
+    """-> (w as the library reads it, w_layout, cin, cout, pre).  A channels_last [Co, Ci, 2, 2] weight is [Co][2][2][Ci] in
+    memory and is passed as it lies (w_layout 1); anything else is made contiguous (w_layout 0).  No copy for either of the
+    two ways torch stores a dense fp32 weight."""
+    w = w.detach().float()
+    cout, cin = w.shape[0], w.shape[1]
+    assert x.dim() == 4 and tuple(w.shape[2:]) == (2, 2) and x.shape[-1] == cin, (x.shape, w.shape)
+    assert a is None or b is not None, "pre-op: none (a, b None), x + b (a None), ELU(x + a) + b"
+    if w.is_contiguous(memory_format=torch.channels_last) and not w.is_contiguous():
+        layout = 1
+    else:
+        w, layout = w.contiguous(), 0
+    return w, layout, cin, cout, (0 if b is None else 1 if a is None else 2)
+
+
+def _conv_down_ws(x, cin, cout):
+    B, H, W, _ = x.shape
+    return torch.empty(L.lib().vqae_conv_down_train_workspace_bytes(B, H, W, cin, cout), dtype=torch.uint8, device=x.device)
+
+
+def conv_down_train_forward(x, w, a=None, b=None):
+    """y [B, H/2, W/2, Co] = the 2x2, stride-2 conv of u [B, H, W, Ci] with w [Co, Ci, 2, 2] (contiguous or channels_last, read
+    in place); u = x (a, b None), x + b (a None) or ELU(x + a) + b, with a, b one-element device tensors.  u is not
+    materialised."""
+    _need_gpu(x, w)
+    x = x.contiguous()
+    wc, layout, cin, cout, pre = _conv_down_args(x, w, a, b)
+    B, H, W, _ = x.shape
+    y = torch.empty((B, H // 2, W // 2, cout), dtype=torch.float32, device=x.device)
+    ws = _conv_down_ws(x, cin, cout) if layout == 0 else None
+    L.check(L.lib().vqae_conv_down_train_forward_f32(_p(x), _p(_scalar(a)), _p(_scalar(b)), pre, _p(wc), layout, B, H, W, cin,
+                                                     cout, _p(y), _p(ws), _stream()))
+    return y
+
+
+def conv_down_train_backward(g, x, w, a=None, b=None, need_x=True, need_w=True):
+    """-> (g_x [B, H, W, Ci] | None, g_w (w's shape and memory format) | None, g_a [1] | None, g_b [1] | None) from
+    g [B, H/2, W/2, Co] and the forward's x, w, a, b: g_u = the data gradient, g_x = g_u * ELU'(x + a) (g_u without an
+    activation), g_a = sum g_x, g_b = sum g_u, g_w = the weight gradient with u recomputed from x."""
+    _need_gpu(g, x, w)
+    g, x = g.contiguous(), x.contiguous()
+    wc, layout, cin, cout, pre = _conv_down_args(x, w, a, b)
+    B, H, W, _ = x.shape
+    assert tuple(g.shape) == (B, H // 2, W // 2, cout), (g.shape, x.shape, w.shape)
+    dev = g.device
+    g_x = torch.empty_like(x) if need_x else None
+    g_w = torch.empty_like(wc) if need_w else None              # dense: the same strides, i.e. the same layout
+    g_a = torch.empty(1, dtype=torch.float32, device=dev) if pre == 2 else None
+    g_b = torch.empty(1, dtype=torch.float32, device=dev) if pre >= 1 else None
+    ws = _conv_down_ws(x, cin, cout)
+    L.check(L.lib().vqae_conv_down_train_backward_f32(_p(g), _p(x), _p(_scalar(a)), _p(_scalar(b)), pre, _p(wc), layout, B, H, W,
+                                                      cin, cout, _p(g_x), _p(g_w), _p(g_a), _p(g_b), _p(ws), _stream()))
+    return g_x, g_w, g_a, g_b
+
+
 def vq_forward(z_flat, embed, commitment_cost=1.0, idx_dtype=torch.int64, want_q=True, want_margin=False, p=4):
     """z_flat [N, D], embed [K, D] -> (q [N, D] | None, idx [N], loss 0-d, margin [N] | None).  p: the Minkowski exponent of the
     reference's cdist = the rank of the quantiser's input (vq.py:97,121-129): 4 for NCHW, 3 / 5 for [B, D, L] / [B, D, d, h, w]."""

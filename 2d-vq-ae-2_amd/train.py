@@ -9,12 +9,21 @@ per block (conv1, conv2, conv3, skip_conv) the 1x1, stride-1 ones have a kernel 
                                  fixup_add + the skip conv of a 'same' block, the 1x1 after the bicubic of an 'up' block.
                                  Other shapes (Co = 3 of an 'out' block) take the torch route, counted in
                                  stats["conv1x1_fallbacks"]; stats["conv1x1_hip"] counts the fused nodes.
-The 3x3 convs, the 2x2 stride-2 convs, the stems and the quantiser's projections stay with torch.
+The 2x2, stride-2 convs of a 'down' block (branch_conv2, skip_conv) have one behind the independent keyword `conv_down`:
+
+    conv_down="torch" (default)  F.conv2d(..., stride=2) behind fixup_act / fixup_add, as always
+    conv_down="hip"              each is ONE node of csrc/conv_down_train.hip with the op in front of it folded in (fixup_act +
+                                 branch_conv2, fixup_add + skip_conv): the activation in front of branch_conv2, the largest tensor
+                                 of a step, is never written.  Odd H or W and channel counts outside the kernels' rule take the
+                                 torch route, counted in stats["conv_down_fallbacks"]; stats["conv_down_hip"] counts the nodes.
+With both keywords at their defaults the graph is op for op the one described above.
+The 3x3 convs, the stems and the quantiser's projections stay with torch.
 
     block_forward(block, x)      one block, NCHW in and out, any of the four modes, with or without a skip_conv
     forward_train(model, x)      VQAE.forward (vq_ae/model.py:41-48) over a vqae_amd.model.VQAE mirror -> (out, (vq_loss,))
     step(model, batch, loss_f)   VQAE.step (vq_ae/model.py:114-122) -> (out, recon_loss, (vq_loss,))
     conv1x1(x, w, a, b)          the fused node on [B, H, W, Ci]
+    conv_down(x, w, a, b)        the fused 2x2, stride-2 node: [B, H, W, Ci] -> [B, H/2, W/2, Co]
 
 The functional ops (fixup_act, fixup_add, fixup_out, bicubic_up2) take channel-last tensors [B, H, W, C], like every other
 op of the package.  The graph stays channel-last throughout (the reference trains in channels_last: model.py:124-126): a conv
@@ -23,8 +32,9 @@ sees the NCHW-shaped view of an NHWC tensor, and a conv result that comes back i
 
 The one-element parameters (bias1a .. bias4, scale, bias1c / bias1d) are read by the kernels from device memory and their
 gradients are written to device tensors by fixed-order fp64 sums: a step never synchronises the host for them, and two runs
-of any op here give the same bits -- under conv1x1="hip" the 1x1 convs and their weight gradients included.  (A whole step
-also runs MIOpen's gradients of the remaining convs, for which no such claim is made.)
+of any op here give the same bits -- under conv1x1="hip" the 1x1 convs and their weight gradients included, under
+conv_down="hip" the 2x2, stride-2 ones.  (A whole step also runs MIOpen's gradients of the remaining convs -- the 3x3 ones,
+the stems, the quantiser's projections -- for which no such claim is made.)
 
 Each Function has a restatement in plain torch ops, taken when its tensors are on the CPU: the same forward, and the SAME
 hand-derived backward (the gather-fold of the halo, the bicubic adjoint, the fixed-order sums), which is what
@@ -41,8 +51,10 @@ from . import ops
 from .layers.conv_block import PreActFixupResBlock
 from .layers.vq import ProjectedEMAVectorQuantizer2d
 
-stats = {"layout_checks": 0, "layout_copies": 0, "conv1x1_hip": 0, "conv1x1_fallbacks": 0}
+stats = {"layout_checks": 0, "layout_copies": 0, "conv1x1_hip": 0, "conv1x1_fallbacks": 0, "conv_down_hip": 0,
+         "conv_down_fallbacks": 0}
 CONV1X1_ROUTES = ("torch", "hip")
+CONV_DOWN_ROUTES = ("torch", "hip")
 
 _W75 = (-0.03515625, 0.26171875, 0.87890625, -0.10546875)     # even outputs: inputs m-2 .. m+1, m = o >> 1
 _W25 = (-0.10546875, 0.87890625, 0.26171875, -0.03515625)     # odd outputs:  inputs m-1 .. m+2
@@ -268,6 +280,65 @@ def conv1x1(x, w, a=None, b=None):
     return _Conv1x1Fn.apply(x, w, a, b)
 
 
+def _space_to_depth(t):
+    """[B, H, W, C] (H, W even) -> [B H/2 W/2, 4 C], column (kh, kw, c): the rows of the 2x2, stride-2 conv's GEMM."""
+    B, H, W, C = t.shape
+    return t.reshape(B, H // 2, 2, W // 2, 2, C).permute(0, 1, 3, 2, 4, 5).reshape(-1, 4 * C)
+
+
+def _depth_to_space(m, B, OH, OW):
+    """The inverse (and, the map being a permutation, the adjoint) of _space_to_depth."""
+    C = m.shape[-1] // 4
+    return m.reshape(B, OH, OW, 2, 2, C).permute(0, 1, 3, 2, 4, 5).reshape(B, 2 * OH, 2 * OW, C)
+
+
+class _ConvDownFn(torch.autograd.Function):
+    """y [B, H/2, W/2, Co] = the 2x2, stride-2 conv (no padding, no bias) of u [B, H, W, Ci] with w [Co, Ci, 2, 2], the op in
+    front of the conv folded in as in _Conv1x1Fn.  Saves x, w, a, b -- not u.  The four taps do not overlap, so the backward is
+    two matmuls on the space-to-depth form: g_u = depth_to_space(g . w2), g_w = g^T . space_to_depth(u), w2 [Co, (kh, kw, ci)]."""
+
+    @staticmethod
+    def forward(ctx, x, w, a, b):
+        if x.is_cuda:
+            y = ops.conv_down_train_forward(x.float(), w, a, b)
+        else:
+            y = to_nhwc(F.conv2d(to_nchw(_pre_op_torch(x, a, b)), w, stride=2))
+        ctx.save_for_backward(x, w, *(t for t in (a, b) if t is not None))
+        ctx.has = (a is not None, b is not None)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, w, *ab = ctx.saved_tensors
+        a = ab[0] if ctx.has[0] else None
+        b = ab[-1] if ctx.has[1] else None
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if g.is_cuda:
+            g_x, g_w, g_a, g_b = ops.conv_down_train_backward(_dense(g.float()), x.float(), w, a, b, need_x, need_w)
+        else:
+            B, OH, OW, Co = g.shape
+            g2 = g.reshape(-1, Co)
+            g_u = _depth_to_space(g2 @ w.permute(0, 2, 3, 1).reshape(Co, -1), B, OH, OW)
+            g_x = g_u * elu_grad(x + a) if a is not None else g_u
+            g_a, g_b = g_x.sum(), g_u.sum()
+            g_w = None
+            if need_w:
+                g_w = (g2.t() @ _space_to_depth(_pre_op_torch(x, a, b))).reshape(Co, 2, 2, -1).permute(0, 3, 1, 2)
+                if w.is_contiguous():
+                    g_w = g_w.contiguous()
+        return (g_x if need_x else None, g_w.to(w.dtype) if need_w else None, _like(g_a, a) if a is not None else None,
+                _like(g_b, b) if b is not None else None)
+
+
+def conv_down(x, w, a=None, b=None):
+    """The 2x2, stride-2 conv on [B, H, W, Ci] (H, W even) -> [B, H/2, W/2, Co], w [Co, Ci, 2, 2], of ELU(x + a) + b (a None:
+    of x + b; both None: of x) as ONE node: csrc/conv_down_train.hip on the device, a plain-torch restatement on CPU tensors."""
+    assert a is None or b is not None
+    assert x.shape[1] % 2 == 0 and x.shape[2] % 2 == 0, x.shape
+    return _ConvDownFn.apply(x, w, a, b)
+
+
 def fixup_act(x, a, b, halo=0):
     """ELU(x + a) + b on [B, H, W, C]; halo = 1: [B, H + 2, W + 2, C] with the circular wrap written."""
     return _ActFn.apply(x, a, b, int(halo))
@@ -310,19 +381,39 @@ def _pre_conv1x1(hip, x, a, b, w):
     return _conv(x, w)
 
 
-def block_forward_nhwc(block, x, conv1x1="torch"):
+def _route_down(conv_down):
+    if conv_down not in CONV_DOWN_ROUTES:
+        raise ValueError(f"conv_down must be one of {CONV_DOWN_ROUTES}, not {conv_down!r}")
+    return conv_down == "hip"
+
+
+def _pre_conv_down(hip, x, a, b, w):
+    """The 2x2, stride-2 conv of ELU(x + a) + b (a None: x + b).  hip: one fused node where the kernels take the shape (even
+    H and W, their channel rule); any other shape takes the torch route and is counted."""
+    if hip:
+        if (tuple(w.shape[2:]) == (2, 2) and x.shape[1] % 2 == 0 and x.shape[2] % 2 == 0
+                and ops.conv_down_train_supported(w.shape[1], w.shape[0])):
+            stats["conv_down_hip"] += 1
+            return conv_down(x, w, a, b)
+        stats["conv_down_fallbacks"] += 1
+    x = fixup_add(x, b) if a is None else fixup_act(x, a, b)
+    return _conv(x, w, stride=2)
+
+
+def block_forward_nhwc(block, x, conv1x1="torch", conv_down="torch"):
     """conv_block.py:196-216 on [B, H, W, C] with a graph: the fused ops around F.conv2d.  conv1x1 = "hip": every 1x1, stride-1
-    conv the kernels support is one node with the op in front of it (csrc/conv1x1_train.hip); "torch": F.conv2d throughout."""
+    conv the kernels support is one node with the op in front of it (csrc/conv1x1_train.hip); conv_down = "hip": so is each
+    2x2, stride-2 conv of a 'down' block (csrc/conv_down_train.hip); "torch": F.conv2d."""
     if not isinstance(block, PreActFixupResBlock):
         raise NotImplementedError(f"training is implemented for Fixup blocks only (no MBConv / BatchNorm training), not "
                                   f"{type(block).__name__}")
-    hip = _route(conv1x1)
+    hip, down = _route(conv1x1), _route_down(conv_down)
     mode = block.mode
     t = _pre_conv1x1(hip, x, block.bias1a, block.bias1b, block.branch_conv1.weight)
     if mode in ("same", "out"):                         # 3x3 circular: the activation writes the wrap, the conv pads nothing
         t = _conv(fixup_act(t, block.bias2a, block.bias2b, halo=1), block.branch_conv2.weight)
     elif mode == "down":
-        t = _conv(fixup_act(t, block.bias2a, block.bias2b), block.branch_conv2.weight, stride=2)
+        t = _pre_conv_down(down, t, block.bias2a, block.bias2b, block.branch_conv2.weight)
     else:                                               # ResizeConv2D: bicubic x2, then 1x1
         t = _pre_conv1x1(hip, bicubic_up2(fixup_act(t, block.bias2a, block.bias2b)), None, None, block.branch_conv2.weight)
     t = _pre_conv1x1(hip, t, block.bias3a, block.bias3b, block.branch_conv3.weight)
@@ -332,7 +423,7 @@ def block_forward_nhwc(block, x, conv1x1="torch"):
     if mode == "up":
         skip = _pre_conv1x1(hip, bicubic_up2(x, block.bias1c), None, None, w)
     elif mode == "down":
-        skip = _conv(fixup_add(x, block.bias1c), w, stride=2)
+        skip = _pre_conv_down(down, x, None, block.bias1c, w)
     elif mode == "same":
         skip = _pre_conv1x1(hip, x, None, block.bias1c, w)
     else:                                               # out2d: 3x3, zero padding
@@ -345,9 +436,9 @@ def _compute_dtype(x):
     return x if x.dtype == torch.float64 and not x.is_cuda else x.float()
 
 
-def block_forward(block, x, conv1x1="torch"):
+def block_forward(block, x, conv1x1="torch", conv_down="torch"):
     """One PreActFixupResBlock mirror on an NCHW-shaped tensor (channels_last preferred: no copy) -> NCHW-shaped, with a graph."""
-    return to_nchw(block_forward_nhwc(block, to_nhwc(_compute_dtype(x)), conv1x1=conv1x1))
+    return to_nchw(block_forward_nhwc(block, to_nhwc(_compute_dtype(x)), conv1x1=conv1x1, conv_down=conv_down))
 
 
 def block_forward_torch(block, x):
@@ -403,34 +494,36 @@ def _quantize_torch(vq, inputs):
     return q, idx.reshape(cl.shape[:-1]), loss
 
 
-def forward_train(model, x, return_indices=False, conv1x1="torch"):
+def forward_train(model, x, return_indices=False, conv1x1="torch", conv_down="torch"):
     """VQAE.forward (vq_ae/model.py:41-48) over a vqae_amd.model.VQAE mirror, with a graph: -> (out, (vq_loss,)), out NCHW-shaped
     (channels_last).  The stems are F.conv2d, the blocks block_forward, the quantiser its own trainable mirror (its EMA buffers
-    are updated in training mode, as in the reference).  conv1x1: the route of the blocks' 1x1 convs (block_forward_nhwc)."""
+    are updated in training mode, as in the reference).  conv1x1 / conv_down: the routes of the blocks' 1x1 and 2x2, stride-2
+    convs (block_forward_nhwc)."""
     _route(conv1x1)
+    _route_down(conv_down)
     enc, dec = model.encoder, model.decoder
     h = to_nhwc(_compute_dtype(x))
     h = _conv(h, enc.in_stem.weight, enc.in_stem.bias, padding=1)
     for level in enc.down_layers[0].layers:
         for blk in level.layers:
-            h = block_forward_nhwc(blk, h, conv1x1=conv1x1)
+            h = block_forward_nhwc(blk, h, conv1x1=conv1x1, conv_down=conv_down)
     for blk in enc.pre_enc_layers[0]:
-        h = block_forward_nhwc(blk, h, conv1x1=conv1x1)
+        h = block_forward_nhwc(blk, h, conv1x1=conv1x1, conv_down=conv_down)
     vq = enc.vq_layers[0]
     q, idx, vq_loss = vq(to_nchw(h)) if h.is_cuda else _quantize_torch(vq, to_nchw(h))
     h = to_nhwc(q)
     for blk in dec.post_enc_layers[0]:
-        h = block_forward_nhwc(blk, h, conv1x1=conv1x1)
+        h = block_forward_nhwc(blk, h, conv1x1=conv1x1, conv_down=conv_down)
     for level in dec.up_layers[0].layers:
         for blk in level.layers:
-            h = block_forward_nhwc(blk, h, conv1x1=conv1x1)
+            h = block_forward_nhwc(blk, h, conv1x1=conv1x1, conv_down=conv_down)
     out = to_nchw(_conv(h, dec.out_stem.weight, dec.out_stem.bias, padding=1))
     if return_indices:
         return out, (vq_loss,), (idx,)
     return out, (vq_loss,)
 
 
-def step(model, batch, loss_f=F.huber_loss, conv1x1="torch"):
+def step(model, batch, loss_f=F.huber_loss, conv1x1="torch", conv_down="torch"):
     """VQAE.step (vq_ae/model.py:114-122): -> (out, recon_loss, (vq_loss,)); the caller backpropagates recon_loss + sum(vq_loss)."""
-    out, encoding_loss = forward_train(model, batch, conv1x1=conv1x1)
+    out, encoding_loss = forward_train(model, batch, conv1x1=conv1x1, conv_down=conv_down)
     return out, loss_f(input=out, target=batch), encoding_loss
