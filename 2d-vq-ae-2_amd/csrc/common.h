@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 
 #include "../../include/vqae_hip.h"
 
@@ -89,6 +90,11 @@ __device__ __forceinline__ float elu_act(float v) {
     return __builtin_amdgcn_fmed3f(v, e - 1.0f, 0.0f);
 }
 
+// The training kernels' ELU(alpha = 1), with expm1's relative accuracy on the negative side, and its derivative: the parity
+// bar of the training path is a few fp32 roundings, and elu_act above is 1 ulp of 1.0 absolute.
+__device__ __forceinline__ float elu_train(float v) { return v > 0.f ? v : expm1f(v); }
+__device__ __forceinline__ float elu_grad(float v) { return v > 0.f ? 1.f : expf(v); }
+
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains the vector-memory counter
 // (s_waitcnt vmcnt(0)): every global load in flight -- prefetched weight fragments, residual rows, the next tile's input
 // rows -- has to land before each phase boundary.  For kernels whose waves exchange data through LDS only (each lane
@@ -127,6 +133,13 @@ __device__ __forceinline__ float wave_max(float v) {
 inline int64_t env_int(const char* name, int64_t dflt) {
     const char* e = getenv(name);
     return e ? atoll(e) : dflt;
+}
+
+// true where every pointer of the list (NULL included) is 16-byte aligned
+inline bool aligned16(std::initializer_list<const void*> ps) {
+    uintptr_t m = 0;
+    for (const void* p : ps) m |= (uintptr_t)p;
+    return (m & 15) == 0;
 }
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }

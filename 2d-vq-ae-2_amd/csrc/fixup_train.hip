@@ -45,11 +45,6 @@ inline int ft_grid(int64_t items) {
     return (int)std::min<int64_t>(FT_MAX_WG, std::max<int64_t>(1, ceil_div(items, FT_THREADS)));
 }
 
-// ELU(alpha = 1) with expm1's relative accuracy on the negative side: the parity bar of the training path is a few fp32
-// roundings, and elu_act of common.h is 1 ulp of 1.0 absolute.
-__device__ __forceinline__ float elu_train(float v) { return v > 0.f ? v : expm1f(v); }
-__device__ __forceinline__ float elu_grad(float v) { return v > 0.f ? 1.f : expf(v); }
-
 // The workgroup's FT_SUMS sums -> its row of the workspace.  Called by every thread of the workgroup.
 __device__ __forceinline__ void ft_block_partials(double s0, double s1, double* __restrict__ partials) {
     __shared__ double red[FT_SUMS][FT_THREADS / 64];
@@ -374,12 +369,6 @@ void ft_bicubic_bwd(const float* __restrict__ g, int B, int H, int W, int C, flo
         *reinterpret_cast<P*>(g_x + i * VEC) = acc;
     }
     ft_block_partials(s0, 0.0, partials);
-}
-
-inline bool aligned16(std::initializer_list<const void*> ps) {
-    uintptr_t m = 0;
-    for (const void* p : ps) m |= (uintptr_t)p;
-    return (m & 15) == 0;
 }
 
 // dims of a [B][H][W][C] tensor: each >= 1 and the element count (of the LARGEST tensor of the op, `grow` elements per

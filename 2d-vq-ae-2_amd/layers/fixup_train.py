@@ -3,8 +3,8 @@ builds a graph (vqae_amd.train.block_forward: fused HIP forward / backward for e
 torch's conv2d for the convolutions).  Select through Hydra in the reference's stock Encoder / Decoder with
     _target_: vqae_amd.layers.fixup_train.PreActFixupResBlock
 The keyword `conv1x1` ("torch", the default, or "hip") is train.block_forward's: "hip" runs the 1x1, stride-1 convs and the op
-in front of each as one fused HIP node (csrc/conv1x1_train.hip).  The independent keyword `conv_down` ("torch" | "hip") does the
-same for the two 2x2, stride-2 convs of a 'down' block (csrc/conv_down_train.hip).
+in front of each as one fused HIP node (csrc/conv_train.hip).  The independent keyword `conv_down` ("torch" | "hip") does the
+same for the two 2x2, stride-2 convs of a 'down' block (csrc/conv_train.hip).
 The inference mirror of conv_block.py is unchanged and still runs under no_grad.
 """
 import torch

@@ -4,7 +4,7 @@ is a fused HIP forward / backward (csrc/fixup_train.hip) behind a torch.autograd
 per block (conv1, conv2, conv3, skip_conv) the 1x1, stride-1 ones have a kernel of ours behind the keyword `conv1x1`:
 
     conv1x1="torch"  (default)   every conv is F.conv2d: the graph this module has always built, op for op
-    conv1x1="hip"                every 1x1, stride-1 conv whose channel counts csrc/conv1x1_train.hip takes (multiples of 8 up
+    conv1x1="hip"                every 1x1, stride-1 conv whose channel counts csrc/conv_train.hip takes (multiples of 8 up
                                  to 256) is ONE node together with the op in front of it: fixup_act + conv1 / conv3,
                                  fixup_add + the skip conv of a 'same' block, the 1x1 after the bicubic of an 'up' block.
                                  Other shapes (Co = 3 of an 'out' block) take the torch route, counted in
@@ -12,7 +12,7 @@ per block (conv1, conv2, conv3, skip_conv) the 1x1, stride-1 ones have a kernel 
 The 2x2, stride-2 convs of a 'down' block (branch_conv2, skip_conv) have one behind the independent keyword `conv_down`:
 
     conv_down="torch" (default)  F.conv2d(..., stride=2) behind fixup_act / fixup_add, as always
-    conv_down="hip"              each is ONE node of csrc/conv_down_train.hip with the op in front of it folded in (fixup_act +
+    conv_down="hip"              each is ONE node of csrc/conv_train.hip with the op in front of it folded in (fixup_act +
                                  branch_conv2, fixup_add + skip_conv): the activation in front of branch_conv2, the largest tensor
                                  of a step, is never written.  Odd H or W and channel counts outside the kernels' rule take the
                                  torch route, counted in stats["conv_down_fallbacks"]; stats["conv_down_hip"] counts the nodes.
@@ -231,51 +231,61 @@ class _BicubicFn(torch.autograd.Function):
         return g_x, _like(g_pb, ctx.pb) if ctx.pb is not None else None
 
 
-class _Conv1x1Fn(torch.autograd.Function):
-    """y = u . w^T on [B, H, W, Ci], w [Co, Ci, 1, 1], with the op in front of the conv folded in: u = x (a, b None), x + b
-    (a None) or ELU(x + a) + b.  Saves x, a, b, w -- not u: the backward recomputes it for g_w and takes ELU' from x + a."""
-
-    @staticmethod
-    def forward(ctx, x, w, a, b):
-        if x.is_cuda:
-            y = ops.conv1x1_train_forward(x.float(), w, a, b)
-        else:
-            y = to_nhwc(F.conv2d(to_nchw(_pre_op_torch(x, a, b)), w))
-        ctx.save_for_backward(x, w, *(t for t in (a, b) if t is not None))
-        ctx.has = (a is not None, b is not None)
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g):
-        x, w, *ab = ctx.saved_tensors
-        a = ab[0] if ctx.has[0] else None
-        b = ab[-1] if ctx.has[1] else None
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if g.is_cuda:
-            g_x, g_w, g_a, g_b = ops.conv1x1_train_backward(_dense(g.float()), x.float(), w, a, b, need_x, need_w)
-        else:
-            w2 = w.reshape(w.shape[0], w.shape[1])
-            g_u = g @ w2
-            g_x = g_u * elu_grad(x + a) if a is not None else g_u
-            g_a, g_b = g_x.sum(), g_u.sum()
-            g_w = None
-            if need_w:
-                u = _pre_op_torch(x, a, b)
-                g_w = (g.reshape(-1, g.shape[-1]).t() @ u.reshape(-1, u.shape[-1])).reshape(w.shape)
-        return (g_x if need_x else None, g_w.to(w.dtype) if need_w else None, _like(g_a, a) if a is not None else None,
-                _like(g_b, b) if b is not None else None)
-
-
 def _pre_op_torch(x, a, b):
     if b is None:
         return x
     return x + b if a is None else F.elu(x + a) + b
 
 
+class _PreConvFn(torch.autograd.Function):
+    """The ctx plumbing of a conv node with the op in front of it folded in: u = x (a, b None), x + b (a None) or
+    ELU(x + a) + b.  Saves x, w and whichever of a, b exist -- not u: the backward recomputes it for g_w and takes ELU' from
+    x + a.  A node states _forward(x, w, a, b) -> y and _backward(g, x, w, a, b, need_x, need_w) -> (g_x, g_w, g_a, g_b)."""
+
+    @classmethod
+    def forward(cls, ctx, x, w, a, b):
+        ctx.save_for_backward(x, w, *(t for t in (a, b) if t is not None))
+        ctx.has = (a is not None, b is not None)
+        return cls._forward(x, w, a, b)
+
+    @classmethod
+    @once_differentiable
+    def backward(cls, ctx, g):
+        x, w, *ab = ctx.saved_tensors
+        a = ab[0] if ctx.has[0] else None
+        b = ab[-1] if ctx.has[1] else None
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        g_x, g_w, g_a, g_b = cls._backward(g, x, w, a, b, need_x, need_w)
+        return (g_x if need_x else None, g_w.to(w.dtype) if need_w else None, _like(g_a, a) if a is not None else None,
+                _like(g_b, b) if b is not None else None)
+
+
+class _Conv1x1Fn(_PreConvFn):
+    """y = u . w^T on [B, H, W, Ci], w [Co, Ci, 1, 1]."""
+
+    @staticmethod
+    def _forward(x, w, a, b):
+        if x.is_cuda:
+            return ops.conv1x1_train_forward(x.float(), w, a, b)
+        return to_nhwc(F.conv2d(to_nchw(_pre_op_torch(x, a, b)), w))
+
+    @staticmethod
+    def _backward(g, x, w, a, b, need_x, need_w):
+        if g.is_cuda:
+            return ops.conv1x1_train_backward(_dense(g.float()), x.float(), w, a, b, need_x, need_w)
+        w2 = w.reshape(w.shape[0], w.shape[1])
+        g_u = g @ w2
+        g_x = g_u * elu_grad(x + a) if a is not None else g_u
+        g_w = None
+        if need_w:
+            u = _pre_op_torch(x, a, b)
+            g_w = (g.reshape(-1, g.shape[-1]).t() @ u.reshape(-1, u.shape[-1])).reshape(w.shape)
+        return g_x, g_w, g_x.sum(), g_u.sum()
+
+
 def conv1x1(x, w, a=None, b=None):
     """A 1x1, stride-1 conv on [B, H, W, Ci] -> [B, H, W, Co], w [Co, Ci, 1, 1], of ELU(x + a) + b (a None: of x + b; both
-    None: of x) as ONE node: csrc/conv1x1_train.hip on the device, a plain-torch restatement on CPU tensors."""
+    None: of x) as ONE node: csrc/conv_train.hip on the device, a plain-torch restatement on CPU tensors."""
     assert a is None or b is not None
     return _Conv1x1Fn.apply(x, w, a, b)
 
@@ -292,48 +302,36 @@ def _depth_to_space(m, B, OH, OW):
     return m.reshape(B, OH, OW, 2, 2, C).permute(0, 1, 3, 2, 4, 5).reshape(B, 2 * OH, 2 * OW, C)
 
 
-class _ConvDownFn(torch.autograd.Function):
-    """y [B, H/2, W/2, Co] = the 2x2, stride-2 conv (no padding, no bias) of u [B, H, W, Ci] with w [Co, Ci, 2, 2], the op in
-    front of the conv folded in as in _Conv1x1Fn.  Saves x, w, a, b -- not u.  The four taps do not overlap, so the backward is
-    two matmuls on the space-to-depth form: g_u = depth_to_space(g . w2), g_w = g^T . space_to_depth(u), w2 [Co, (kh, kw, ci)]."""
+class _ConvDownFn(_PreConvFn):
+    """y [B, H/2, W/2, Co] = the 2x2, stride-2 conv (no padding, no bias) of u [B, H, W, Ci] with w [Co, Ci, 2, 2].  The four
+    taps do not overlap, so the backward is two matmuls on the space-to-depth form: g_u = depth_to_space(g . w2),
+    g_w = g^T . space_to_depth(u), w2 [Co, (kh, kw, ci)]."""
 
     @staticmethod
-    def forward(ctx, x, w, a, b):
+    def _forward(x, w, a, b):
         if x.is_cuda:
-            y = ops.conv_down_train_forward(x.float(), w, a, b)
-        else:
-            y = to_nhwc(F.conv2d(to_nchw(_pre_op_torch(x, a, b)), w, stride=2))
-        ctx.save_for_backward(x, w, *(t for t in (a, b) if t is not None))
-        ctx.has = (a is not None, b is not None)
-        return y
+            return ops.conv_down_train_forward(x.float(), w, a, b)
+        return to_nhwc(F.conv2d(to_nchw(_pre_op_torch(x, a, b)), w, stride=2))
 
     @staticmethod
-    @once_differentiable
-    def backward(ctx, g):
-        x, w, *ab = ctx.saved_tensors
-        a = ab[0] if ctx.has[0] else None
-        b = ab[-1] if ctx.has[1] else None
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    def _backward(g, x, w, a, b, need_x, need_w):
         if g.is_cuda:
-            g_x, g_w, g_a, g_b = ops.conv_down_train_backward(_dense(g.float()), x.float(), w, a, b, need_x, need_w)
-        else:
-            B, OH, OW, Co = g.shape
-            g2 = g.reshape(-1, Co)
-            g_u = _depth_to_space(g2 @ w.permute(0, 2, 3, 1).reshape(Co, -1), B, OH, OW)
-            g_x = g_u * elu_grad(x + a) if a is not None else g_u
-            g_a, g_b = g_x.sum(), g_u.sum()
-            g_w = None
-            if need_w:
-                g_w = (g2.t() @ _space_to_depth(_pre_op_torch(x, a, b))).reshape(Co, 2, 2, -1).permute(0, 3, 1, 2)
-                if w.is_contiguous():
-                    g_w = g_w.contiguous()
-        return (g_x if need_x else None, g_w.to(w.dtype) if need_w else None, _like(g_a, a) if a is not None else None,
-                _like(g_b, b) if b is not None else None)
+            return ops.conv_down_train_backward(_dense(g.float()), x.float(), w, a, b, need_x, need_w)
+        B, OH, OW, Co = g.shape
+        g2 = g.reshape(-1, Co)
+        g_u = _depth_to_space(g2 @ w.permute(0, 2, 3, 1).reshape(Co, -1), B, OH, OW)
+        g_x = g_u * elu_grad(x + a) if a is not None else g_u
+        g_w = None
+        if need_w:
+            g_w = (g2.t() @ _space_to_depth(_pre_op_torch(x, a, b))).reshape(Co, 2, 2, -1).permute(0, 3, 1, 2)
+            if w.is_contiguous():
+                g_w = g_w.contiguous()
+        return g_x, g_w, g_x.sum(), g_u.sum()
 
 
 def conv_down(x, w, a=None, b=None):
     """The 2x2, stride-2 conv on [B, H, W, Ci] (H, W even) -> [B, H/2, W/2, Co], w [Co, Ci, 2, 2], of ELU(x + a) + b (a None:
-    of x + b; both None: of x) as ONE node: csrc/conv_down_train.hip on the device, a plain-torch restatement on CPU tensors."""
+    of x + b; both None: of x) as ONE node: csrc/conv_train.hip on the device, a plain-torch restatement on CPU tensors."""
     assert a is None or b is not None
     assert x.shape[1] % 2 == 0 and x.shape[2] % 2 == 0, x.shape
     return _ConvDownFn.apply(x, w, a, b)
@@ -362,10 +360,10 @@ def _conv(t, w, bias=None, stride=1, padding=0):
     return to_nhwc(F.conv2d(to_nchw(t), w, bias, stride=stride, padding=padding))
 
 
-def _route(conv1x1):
-    if conv1x1 not in CONV1X1_ROUTES:
-        raise ValueError(f"conv1x1 must be one of {CONV1X1_ROUTES}, not {conv1x1!r}")
-    return conv1x1 == "hip"
+def _route(keyword, value, routes):
+    if value not in routes:
+        raise ValueError(f"{keyword} must be one of {routes}, not {value!r}")
+    return value == "hip"
 
 
 def _pre_conv1x1(hip, x, a, b, w):
@@ -379,12 +377,6 @@ def _pre_conv1x1(hip, x, a, b, w):
     if b is not None:
         x = fixup_add(x, b) if a is None else fixup_act(x, a, b)
     return _conv(x, w)
-
-
-def _route_down(conv_down):
-    if conv_down not in CONV_DOWN_ROUTES:
-        raise ValueError(f"conv_down must be one of {CONV_DOWN_ROUTES}, not {conv_down!r}")
-    return conv_down == "hip"
 
 
 def _pre_conv_down(hip, x, a, b, w):
@@ -402,12 +394,12 @@ def _pre_conv_down(hip, x, a, b, w):
 
 def block_forward_nhwc(block, x, conv1x1="torch", conv_down="torch"):
     """conv_block.py:196-216 on [B, H, W, C] with a graph: the fused ops around F.conv2d.  conv1x1 = "hip": every 1x1, stride-1
-    conv the kernels support is one node with the op in front of it (csrc/conv1x1_train.hip); conv_down = "hip": so is each
-    2x2, stride-2 conv of a 'down' block (csrc/conv_down_train.hip); "torch": F.conv2d."""
+    conv the kernels support is one node with the op in front of it (csrc/conv_train.hip); conv_down = "hip": so is each
+    2x2, stride-2 conv of a 'down' block (csrc/conv_train.hip); "torch": F.conv2d."""
     if not isinstance(block, PreActFixupResBlock):
         raise NotImplementedError(f"training is implemented for Fixup blocks only (no MBConv / BatchNorm training), not "
                                   f"{type(block).__name__}")
-    hip, down = _route(conv1x1), _route_down(conv_down)
+    hip, down = _route("conv1x1", conv1x1, CONV1X1_ROUTES), _route("conv_down", conv_down, CONV_DOWN_ROUTES)
     mode = block.mode
     t = _pre_conv1x1(hip, x, block.bias1a, block.bias1b, block.branch_conv1.weight)
     if mode in ("same", "out"):                         # 3x3 circular: the activation writes the wrap, the conv pads nothing
@@ -499,8 +491,8 @@ def forward_train(model, x, return_indices=False, conv1x1="torch", conv_down="to
     (channels_last).  The stems are F.conv2d, the blocks block_forward, the quantiser its own trainable mirror (its EMA buffers
     are updated in training mode, as in the reference).  conv1x1 / conv_down: the routes of the blocks' 1x1 and 2x2, stride-2
     convs (block_forward_nhwc)."""
-    _route(conv1x1)
-    _route_down(conv_down)
+    _route("conv1x1", conv1x1, CONV1X1_ROUTES)
+    _route("conv_down", conv_down, CONV_DOWN_ROUTES)
     enc, dec = model.encoder, model.decoder
     h = to_nhwc(_compute_dtype(x))
     h = _conv(h, enc.in_stem.weight, enc.in_stem.bias, padding=1)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times the trainable 1x1 conv kernels (csrc/conv1x1_train.hip, the conv1x1="hip" route of vqae_amd.train) on one GPU
+"""Times the trainable 1x1 conv kernels (csrc/conv_train.hip, the conv1x1="hip" route of vqae_amd.train) on one GPU
 against the "torch" route -- the fused element-wise ops of csrc/fixup_train.hip around F.conv2d, which is what train.py ran
 before the keyword existed.  The method is tools/bench_fixup_train.py's: HIP events around `reps` calls, the sides
 alternating inside every round after a warm-up, median (min - max) over the rounds.

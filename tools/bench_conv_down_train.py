@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times the trainable 2x2, stride-2 conv kernels (csrc/conv_down_train.hip, the conv_down="hip" route of vqae_amd.train) on
+"""Times the trainable 2x2, stride-2 conv kernels (csrc/conv_train.hip, the conv_down="hip" route of vqae_amd.train) on
 one GPU against the "torch" route -- fixup_act / fixup_add of csrc/fixup_train.hip in front of F.conv2d(stride=2), which is what
 train.py ran before the keyword existed.  The method is tools/bench_conv1x1_train.py's: HIP events around `reps` calls, the
 sides alternating inside every round after a warm-up, median (min - max) over the rounds.
