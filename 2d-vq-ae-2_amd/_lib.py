@@ -212,6 +212,14 @@ SYMBOLS = {
     "vqae_conv_down_train_backward_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64,
                                                   c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                   c_void_p]),
+    "vqae_conv3x3_train_supported": (c_int, [c_int, c_int]),
+    "vqae_conv3x3_train_wgrad_run": (c_int, []),
+    "vqae_conv3x3_train_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int, c_int]),
+    "vqae_conv3x3_train_forward_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int,
+                                               c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "vqae_conv3x3_train_backward_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64,
+                                                c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                c_void_p]),
     "vqae_code_histogram_workspace_bytes": (c_size_t, [c_int, c_int64, c_int, c_int]),
     "vqae_code_histogram": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                     c_void_p, c_void_p]),

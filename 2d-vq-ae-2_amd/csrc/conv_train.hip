@@ -1,10 +1,10 @@
-// Trainable convolutions of a Fixup block that are plain GEMMs (conv_block.py:196-216), fp32, NHWC, no bias, with the
+// Trainable convolutions of a Fixup block as GEMMs over (gathered) rows (conv_block.py:196-216), fp32, NHWC, no bias, with the
 // element-wise op in front of the conv folded in:
 //     y [M][Co] = u [M][N] . w^T,    N = TAPS Ci columns, w [Co][N] k-contiguous against a row of u
 //     pre = 0: u = x        pre = 1: u = x + *b        pre = 2: u = ELU(x + *a) + *b        (a, b read from DEVICE memory)
-// u is never written to memory.  All products run on v_mfma_f32_32x32x2_f32.  ONE scheme serves two nodes, which differ in how
-// a row of the activation operand is addressed (the policies Dense and Down2x2 below) and in nothing the kernels branch on at
-// run time:
+// u is never written to memory.  All products run on v_mfma_f32_32x32x2_f32.  ONE scheme serves three nodes, which differ in how
+// a row of the activation operand is addressed (the policies Dense, Down2x2 and Circ3x3 below) and in nothing the kernels branch
+// on at run time:
 //
 //   Dense    the 1x1, stride-1 conv (proj2d.yaml), vqae_conv1x1_train_*: M = B H W, TAPS = 1, row m starts at m Ci and column
 //            k is at + k;  w [Co][Ci] as torch stores [Co, Ci, 1, 1].
@@ -17,6 +17,16 @@
 //            w_layout 1 = [Co][2][2][Ci] is used as it lies; w_layout 0 = [Co][Ci][2][2] (contiguous) is permuted into the
 //            workspace by ct_permute_w first (every call: the weight changes every step).  g_w is written in the layout the
 //            weight has.
+//   Circ3x3  the 3x3, stride-1 conv with circular padding 1 of a 'same' / 'out' block (same2d.yaml, out2d.yaml: branch_conv2),
+//            vqae_conv3x3_train_*: x [B][H][W][Ci], any H, W >= 1, M = B H W, TAPS = 9: row m = (b, h, w), column
+//            k = (kh, kw, ci) is u[b][(h + kh - 1) mod H][(w + kw - 1) mod W][ci].  Neither u nor a halo is written: the centre tap
+//            of row m is at m Ci, a neighbour is (dh W + dw) Ci away with dh, dw in -1 .. 1 corrected by +-H, +-W at an image
+//            edge -- two compare-and-selects per axis on the (h, w) a row keeps, no division per load.  w_layout 1 =
+//            [Co][3][3][Ci] as it lies, w_layout 0 = [Co][Ci][3][3] through ct_permute_w.  The taps OVERLAP, so the data
+//            gradient cannot scatter without atomics: it is the same gather applied to g,
+//                g_u[b][h][w][ci] = sum_{kh,kw,co} g[b][(h + kh - 1) mod H][(w + kw - 1) mod W][co] wt[ci][kh][kw][co],
+//                wt[ci][kh][kw][co] = w[co][ci][2 - kh][2 - kw]   (ct_flip_w, from either layout, every call),
+//            i.e. the forward's loop with K = 9 Co, N = Ci, followed by Dense's epilogue (g_u [M][Ci] lies densely).
 //
 // Three kernels, all shape-generic (Ci, Co multiples of 8 up to 256, any M; in the M, K and N tails the operands are zero and
 // the stores range-checked; templates choose tile COUNTS, never a shape).  The backward is two launches -- data gradient, then
@@ -24,19 +34,21 @@
 // (at 256 x 256 that is 64 K + 32 K floats per workgroup, more than the register file of a CU), and either output may be
 // NULL.  The price is that g and x are read twice.
 //
-//   ct_gemm<Addr, NT, false>   forward.   A workgroup of 4 waves owns 128 rows x all Co columns (wave = 32 rows x NT 32-column
+//   ct_gemm<.., BWD = false>   forward.   A workgroup of 4 waves owns 128 rows x all Co columns (wave = 32 rows x NT 32-column
 //                        tiles, NT = 1 / 2 / 4 / 8 by Co), K = N walked in chunks of 32: the x chunk is staged to LDS with the
 //                        pre-op applied ONCE per element (fp32 MFMA and VALU do not co-execute, so no expm1f in the MFMA loop),
 //                        the w chunk next to it; both k-contiguous, row stride 36 floats: a lane reads 4 consecutive k of its
 //                        row with one 128-bit LDS read and feeds 4 MFMAs (the same k permutation on both operands).  The row
-//                        bases of a tile are computed once per tile (Down2x2: one 64-bit division per thread).
-//   ct_gemm<Addr, NT, true>    data gradient  g_u [M][N] = g [M][Co] . w [Co][N], the same loop with A = g, K = Co and w staged
+//                        bases of a tile are computed once per tile (Down2x2: one 64-bit division per thread; Circ3x3: two,
+//                        and two 32-bit ones per further row).
+//   ct_gemm<.., BWD = true>    data gradient  g_u [M][N] = g [M][Co] . w [Co][N], the same loop with A = g, K = Co and w staged
 //                        TRANSPOSED (w [k][n] is n-contiguous), in pieces of at most 256 columns (blockIdx.y; a piece is 32 NT
 //                        columns, NT from min(N, 256); Dense has one piece).  The epilogue writes column n of row m to the
 //                        input element it came from: g_x = g_u * ELU'(x + *a) (ELU'(v) = v > 0 ? 1 : exp(v)) with x read
 //                        there.  (m, n) -> element is one to one and onto (Down2x2: H, W even): every element of g_x is
 //                        written exactly once, by a plain store.  fp64 sums of g_x and g_u per thread in a fixed order.
-//                        Both forms load the next chunk into registers while the MFMAs of the current one run.
+//                        (Circ3x3: the gather form above, w = wt staged as in the forward, the same epilogue at dense
+//                        addresses.)  Both forms load the next chunk into registers while the MFMAs of the current one run.
 //   ct_wgrad<Addr, ..>   weight gradient  g_w [co][n] = sum_m g[m][co] u[m][n], u recomputed from x.  Grid (P, output tiles of
 //                        up to 64 co x 64 n).  Rows are cut into blocks of 64; workgroup p takes blocks p, p + P, ...; its four
 //                        waves split the rows of a block and each accumulates the whole tile in fp32, operands straight from
@@ -54,7 +66,9 @@
 // Workspace: P slots of N Co doubles with P <= 256 and P N Co <= Addr::SLOT_ELEMS + 1024 Addr::MAX_PIECES rows of two doubles
 // for the scalar sums + 256 bytes of slack.  Dense: [slots][partials], 2^20 slot elements: at most 8 MiB of slots whatever M
 // is.  Down2x2: [permuted weight, 16-byte aligned][slots][partials]: the weight (4 Ci Co floats, at most 1 MiB) + 2^21 slot
-// elements (at most 16 MiB) + 4096 rows: below 17.2 MiB in all.
+// elements (at most 16 MiB) + 4096 rows: below 17.2 MiB in all.  Circ3x3: [permuted weight][flipped weight][slots][partials]:
+// two weights of 9 Ci Co floats (at most 2.25 MiB each) + 2^22 slot elements (at most 32 MiB; one slot of 9 Ci Co doubles is at
+// most 4.5 MiB, so P >= 7) + 1024 rows: below 36.6 MiB in all.
 #include <algorithm>
 
 #include "kernels.h"
@@ -75,22 +89,32 @@ constexpr int CT_PG = 8;                 // row pairs a ct_wgrad wave loads ahea
 constexpr int CT_SLOTS = 256;            // P <= CT_SLOTS and P N Co <= Addr::SLOT_ELEMS (P >= 1)
 constexpr int CT_MAXC = 256;
 
-// ---- the two addressings of the activation operand ---------------------------------------------------------------------------
-// Row: the position of a row m;  row_base(p, d): offset of the row d >= 0 (small) after p;  col_off(n): offset of column n inside
-// a row;  x_ptr(x, p, d, c): the element at column offset c of row d after p, for ct_wgrad's per-lane loads.
+// ---- the three addressings of the activation operand -------------------------------------------------------------------------
+// Geo: what a policy needs of the image: W is the length of a line of rows (Down2x2: OW; Circ3x3: W), H the lines per image
+// (Circ3x3 alone).  Row: the position of a row m;  row_ref(p, d): what ct_gemm keeps of the row d >= 0 (small) after p;
+// col_off(n): column n inside a row;  at(r, c): the offset of column c of row r -- r + c, except at an image edge of Circ3x3;
+// x_ptr(x, p, d, c): the element at column c of row d after p, for ct_wgrad's per-lane loads.  row_base(p, d), SUMS_ROW_OUTER
+// and MAX_PIECES serve the data gradient's epilogue, which writes one element per (row, column): Dense and Down2x2.
+struct Geo { int H, W; };
+
 struct Dense {
     static constexpr int TAPS = 1;                        // columns of the operand per input channel
     static constexpr int MAX_PIECES = 1;                  // data gradient: N = Ci <= 256 is one piece
     static constexpr bool SUMS_ROW_OUTER = false;         // data gradient's per-thread sums walk tile t outer, row r inner
     static constexpr int64_t SLOT_ELEMS = 1 << 20;        // at most 8 MiB of fp64 partials
     static constexpr bool KEEPS_ROW_BASES = false;        // ct_gemm: a row base is one multiply, recomputed per chunk
+    static constexpr bool GATHERS_GRAD = false;           // data gradient: column n of row m IS one element of g_x
     using Col = int;
+    using RowRef = int64_t;
     struct Row { int64_t m; };
-    static __device__ __forceinline__ Row row_pos(int64_t m, int) { return Row{m}; }
-    static __device__ __forceinline__ int64_t row_base(Row p, int64_t d, int, int Ci) { return (p.m + d) * Ci; }
+    static __device__ __forceinline__ int64_t row_stride(Geo, int) { return 0; }
+    static __device__ __forceinline__ Row row_pos(int64_t m, Geo) { return Row{m}; }
+    static __device__ __forceinline__ int64_t row_base(Row p, int64_t d, Geo, int Ci) { return (p.m + d) * Ci; }
+    static __device__ __forceinline__ RowRef row_ref(Row p, int64_t d, Geo g, int Ci) { return row_base(p, d, g, Ci); }
     static __device__ __forceinline__ Col col_off(int n, int, int64_t) { return n; }
+    static __device__ __forceinline__ int64_t at(RowRef r, Col c, Geo, int) { return r + c; }
     // one 64-bit base per block (uniform), 32-bit offsets per load
-    static __device__ __forceinline__ const float* x_ptr(const float* x, Row p, unsigned d, Col c, int, int Ci) {
+    static __device__ __forceinline__ const float* x_ptr(const float* x, Row p, unsigned d, Col c, Geo, int Ci) {
         return x + p.m * Ci + (d * (unsigned)Ci + (unsigned)c);
     }
 };
@@ -101,26 +125,79 @@ struct Down2x2 {
     static constexpr bool SUMS_ROW_OUTER = true;          // row r outer, tile t inner
     static constexpr int64_t SLOT_ELEMS = 1 << 21;        // at most 16 MiB of fp64 partials
     static constexpr bool KEEPS_ROW_BASES = true;         // ct_gemm: a row base costs a division, kept in registers per tile
+    static constexpr bool GATHERS_GRAD = false;
     using Col = int64_t;
+    using RowRef = int64_t;
+    static __device__ __forceinline__ int64_t row_stride(Geo g, int Ci) { return (int64_t)2 * g.W * Ci; }      // W Ci
     // Row m = q OW + ow (q = b OH + oh: input row pair 2 q, 2 q + 1 of the [B H][W][Ci] array) -> offset of pixel (2 q, 2 ow).
     struct Row { int64_t q; unsigned ow; };
-    static __device__ __forceinline__ Row row_pos(int64_t m, int OW) {
+    static __device__ __forceinline__ Row row_pos(int64_t m, Geo g) {
         Row p;
-        p.q = m / OW;
-        p.ow = (unsigned)(m - p.q * OW);
+        p.q = m / g.W;
+        p.ow = (unsigned)(m - p.q * g.W);
         return p;
     }
-    static __device__ __forceinline__ int64_t row_base(Row p, unsigned d, int OW, int Ci) {
-        const unsigned t = p.ow + d, dq = t / (unsigned)OW, ow = t - dq * (unsigned)OW;
-        return ((p.q + dq) * 4 * OW + 2 * (int64_t)ow) * Ci;
+    static __device__ __forceinline__ int64_t row_base(Row p, unsigned d, Geo g, int Ci) {
+        const unsigned t = p.ow + d, dq = t / (unsigned)g.W, ow = t - dq * (unsigned)g.W;
+        return ((p.q + dq) * 4 * g.W + 2 * (int64_t)ow) * Ci;
     }
+    static __device__ __forceinline__ RowRef row_ref(Row p, unsigned d, Geo g, int Ci) { return row_base(p, d, g, Ci); }
     // column n = (kh, kw, ci) of [0, 4 Ci) inside a row's 2 x 2 window;  row_stride = W Ci
     static __device__ __forceinline__ Col col_off(int n, int Ci, int64_t row_stride) {
         const int kh = n >= 2 * Ci ? 1 : 0;
         return kh * row_stride + (n - kh * 2 * Ci);
     }
-    static __device__ __forceinline__ const float* x_ptr(const float* x, Row p, unsigned d, Col c, int OW, int Ci) {
-        return x + row_base(p, d, OW, Ci) + c;
+    static __device__ __forceinline__ int64_t at(RowRef r, Col c, Geo, int) { return r + c; }
+    static __device__ __forceinline__ const float* x_ptr(const float* x, Row p, unsigned d, Col c, Geo g, int Ci) {
+        return x + row_base(p, d, g, Ci) + c;
+    }
+};
+
+// The 3x3, stride-1 conv with circular padding 1: row m = (b, h, w) of [B][H][W][C], column (kh, kw, c) is the pixel
+// ((h + kh - 1) mod H, (w + kw - 1) mod W) of the same image.  The centre tap of row m is at m C; a neighbour is a whole number of
+// pixels away, and WHICH number depends on the row at an image edge, so a row keeps (h, w) next to its base and the wrap is two
+// compare-and-selects per axis in at().  For H = 1 (W = 1) all three kh (kw) land on the row itself, as F.pad(circular) has it.
+struct Circ3x3 {
+    static constexpr int TAPS = 9;
+    static constexpr int MAX_PIECES = 1;                  // its data gradient is a gather that ends in Dense's epilogue
+    static constexpr int64_t SLOT_ELEMS = 1 << 22;        // at most 32 MiB of fp64 partials
+    static constexpr bool KEEPS_ROW_BASES = true;         // ct_gemm: (h, w) of a row cost divisions, kept in registers per tile
+    static constexpr bool GATHERS_GRAD = true;            // nine columns of nine rows meet in one element: gather, never scatter
+    struct Col { int dh, dw, c; };                        // tap (dh, dw) in -1 .. 1, channel c
+    struct Row { int64_t m; unsigned h, w; };
+    struct RowRef { int64_t base; int h, w; };
+    static __device__ __forceinline__ int64_t row_stride(Geo, int) { return 0; }
+    static __device__ __forceinline__ Row row_pos(int64_t m, Geo g) {
+        const int64_t q = m / g.W;                        // b H + h
+        Row p;
+        p.m = m;
+        p.w = (unsigned)(m - q * g.W);
+        p.h = (unsigned)(q % g.H);
+        return p;
+    }
+    // d rows on: 32-bit divisions (a tile may cross many image lines when W is small, and images when H W is)
+    static __device__ __forceinline__ RowRef row_ref(Row p, unsigned d, Geo g, int C) {
+        const unsigned t = p.w + d, dq = t / (unsigned)g.W, hq = p.h + dq;
+        RowRef r;
+        r.base = (p.m + d) * C;
+        r.w = (int)(t - dq * (unsigned)g.W);
+        r.h = (int)(hq % (unsigned)g.H);
+        return r;
+    }
+    static __device__ __forceinline__ Col col_off(int n, int C, int64_t) {
+        const int tap = n / C, kh = tap / 3;
+        return Col{kh - 1, tap - 3 * kh - 1, n - tap * C};
+    }
+    static __device__ __forceinline__ int64_t at(RowRef r, Col c, Geo g, int C) {
+        int h = r.h + c.dh, w = r.w + c.dw;
+        h = h < 0 ? h + g.H : h;
+        h = h >= g.H ? h - g.H : h;
+        w = w < 0 ? w + g.W : w;
+        w = w >= g.W ? w - g.W : w;
+        return r.base + ((int64_t)(h - r.h) * g.W + (w - r.w)) * C + c.c;
+    }
+    static __device__ __forceinline__ const float* x_ptr(const float* x, Row p, unsigned d, Col c, Geo g, int C) {
+        return x + at(row_ref(p, d, g, C), c, g, C);
     }
 };
 
@@ -135,32 +212,49 @@ __device__ __forceinline__ f32x4 pre_op(f32x4 v, int pre, float a, float b) {
     return v;
 }
 
-// w [Co][Ci][2][2] -> wp [Co][2][2][Ci]
+// w [Co][Ci][taps] -> wp [Co][taps][Ci]
 __global__ __launch_bounds__(CT_THREADS)
-void ct_permute_w(const float* __restrict__ w, int Ci, int n, float* __restrict__ wp) {
+void ct_permute_w(const float* __restrict__ w, int Ci, int taps, int n, float* __restrict__ wp) {
     const int i = blockIdx.x * CT_THREADS + threadIdx.x;
     if (i >= n) return;
-    const int co = i / (4 * Ci), r = i - co * 4 * Ci, tap = r / Ci, ci = r - tap * Ci;
-    wp[i] = w[(int64_t)co * 4 * Ci + ci * 4 + tap];
+    const int co = i / (taps * Ci), r = i - co * taps * Ci, tap = r / Ci, ci = r - tap * Ci;
+    wp[i] = w[(int64_t)co * taps * Ci + ci * taps + tap];
 }
 
-// BWD false:  out [M][N] = pre(x rows [M][K]) . w [N][K]^T                             (forward: K = TAPS Ci, N = Co, one piece)
-// BWD true:   g_x = (A [M][K] . w [K][piece of N]) * ELU'(xe + a) at x's addresses, sums  (data gradient: K = Co, N = TAPS Ci)
-// N is the number of columns in all (the row stride of w for BWD), blockIdx.y * 32 NT the first column of this piece.  OW is
-// read by Down2x2 alone.
-template <class Addr, int NT, bool BWD>
+// Circ3x3's data gradient is the same gather applied to g with the flipped, transposed weight:
+// wt [Ci][3][3][Co],  wt[ci][kh][kw][co] = w[co][ci][2 - kh][2 - kw];  tap 3 kh + kw <- tap 8 - (3 kh + kw).  Either layout of w.
+__global__ __launch_bounds__(CT_THREADS)
+void ct_flip_w(const float* __restrict__ w, int Ci, int Co, int w_layout, int n, float* __restrict__ wt) {
+    const int i = blockIdx.x * CT_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const int ci = i / (9 * Co), r = i - ci * 9 * Co, tap = r / Co, co = r - tap * Co, src = 8 - tap;
+    wt[i] = w[w_layout == 0 ? ((int64_t)co * Ci + ci) * 9 + src : ((int64_t)co * 9 + src) * Ci + ci];
+}
+
+// Three things vary, each a template argument: AA, how the rows of the A operand [M][K = AA::TAPS Ca] are addressed (Ca its
+// channels per tap);  BWD, which epilogue runs;  WT, how w lies.
+// BWD false:  out [M][N] = pre(A rows) . w^T, stored densely                                        (a forward: N = Co)
+// BWD true:   g_x = (A rows . w) * ELU'(xe + a) at the addresses of EA (channels Ci), with the sums; no pre-op on A = g
+// WT false:   w [N][K], k-contiguous against a row of A (one piece)
+// WT true:    w [K][N], n-contiguous: staged transposed, in pieces of 32 NT columns, blockIdx.y * 32 NT the first of this piece
+//   forward        <Addr, Dense, ., false, false>  K = TAPS Ci (EA is not used)
+//   data gradient  <Dense, Addr, ., true, true>    Dense, Down2x2: A = g [M][Co] in dense rows, N = TAPS Ci columns scattered
+//                                                  one to one onto x's elements
+//                  <Circ3x3, Dense, ., true, false>  Circ3x3: the taps overlap, so g_u is GATHERED: the forward's loop over
+//                                                  A = g with Ca = Co, K = 9 Co, w = ct_flip_w's wt [Ci][K], N = Ci dense columns
+template <class AA, class EA, int NT, bool BWD, bool WT>
 __global__ __launch_bounds__(CT_THREADS)
 void ct_gemm(const float* __restrict__ A, const float* __restrict__ xe, const float* __restrict__ pa,
-             const float* __restrict__ pb, int pre, const float* __restrict__ w, int64_t M, int OW, int Ci, int K, int N,
+             const float* __restrict__ pb, int pre, const float* __restrict__ w, int64_t M, Geo geo, int Ca, int Ci, int K, int N,
              float* __restrict__ out, double* __restrict__ partials) {
     __shared__ __attribute__((aligned(16))) float Al[CT_BM * CT_LD];
     __shared__ __attribute__((aligned(16))) float Wl[NT * 32 * CT_LD];
     __shared__ double red[2][CT_THREADS / 64];
+    constexpr bool KEEP = AA::KEEPS_ROW_BASES || (BWD && EA::KEEPS_ROW_BASES);    // a tile that pays a division anyway
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, hh = lane >> 5;
     const float a = pre == 2 ? *pa : 0.f, b = (!BWD && pre >= 1) ? *pb : 0.f;
     const int64_t n_tiles = (M + CT_BM - 1) / CT_BM;
-    const int64_t row_stride = (int64_t)2 * OW * Ci;                      // Down2x2: W Ci
-    const int n0 = (BWD && Addr::MAX_PIECES > 1) ? (int)blockIdx.y * NT * 32 : 0;
+    const int n0 = (WT && EA::MAX_PIECES > 1) ? (int)blockIdx.y * NT * 32 : 0;
     double s0 = 0.0, s1 = 0.0;
     // One chunk = 128 rows x 32 k of A (4 16-byte groups per thread, all with the same k) and NT * 32 columns x 32 k of w (NT
     // groups per thread), zero where a row, a column or k is out of range (Ci % 8 == 0, Co % 8 == 0: a group is in or out as a
@@ -170,32 +264,27 @@ void ct_gemm(const float* __restrict__ A, const float* __restrict__ xe, const fl
     // chunk to LDS.  rows() sets the offsets of this thread's four rows of a tile.
     constexpr int AG = CT_BM * (CT_KC / 4) / CT_THREADS;
     f32x4 ra[AG], rw[NT];
-    int64_t rb[AG];
+    typename AA::RowRef rb[AG];
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     auto rows = [&](int64_t m0) __attribute__((always_inline)) {
         const int64_t mf = std::min(m0 + (tid >> 3), M - 1);
-        if (!BWD) {
-            const typename Addr::Row p = Addr::row_pos(mf, OW);
+        const typename AA::Row p = AA::row_pos(mf, geo);
 #pragma unroll
-            for (int j = 0; j < AG; ++j) {
-                const int64_t m = std::min(m0 + (tid >> 3) + 32 * j, M - 1);
-                rb[j] = Addr::row_base(p, m - mf, OW, Ci);                 // 0 <= m - mf <= 96
-            }
-        } else {                         // A = g: dense rows of K
-#pragma unroll
-            for (int j = 0; j < AG; ++j) rb[j] = std::min(m0 + (tid >> 3) + 32 * j, M - 1) * K;
+        for (int j = 0; j < AG; ++j) {
+            const int64_t m = std::min(m0 + (tid >> 3) + 32 * j, M - 1);
+            rb[j] = AA::row_ref(p, m - mf, geo, Ca);                       // 0 <= m - mf <= 96
         }
     };
     auto fetch = [&](int64_t m0, int k0, bool new_tile) __attribute__((always_inline)) {
-        if (new_tile || !Addr::KEEPS_ROW_BASES) rows(m0);
+        if (new_tile || !KEEP) rows(m0);
         const int k = std::min(k0 + 4 * (tid & 7), K - 4);
-        const int64_t ko = BWD ? (int64_t)k : (int64_t)Addr::col_off(k, Ci, row_stride);
+        const typename AA::Col ko = AA::col_off(k, Ca, AA::row_stride(geo, Ca));
 #pragma unroll
-        for (int j = 0; j < AG; ++j) ra[j] = *reinterpret_cast<const f32x4*>(A + rb[j] + ko);
+        for (int j = 0; j < AG; ++j) ra[j] = *reinterpret_cast<const f32x4*>(A + AA::at(rb[j], ko, geo, Ca));
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
             const int i = tid + j * CT_THREADS;
-            if (!BWD) {                  // w [n][k]: k-contiguous
+            if (!WT) {                   // w [n][k]: k-contiguous
                 const int n = i >> 3;
                 rw[j] = *reinterpret_cast<const f32x4*>(w + (int64_t)std::min(n, N - 1) * K + k);
             } else {                     // w [k][n]: n-contiguous, row stride N
@@ -216,7 +305,7 @@ void ct_gemm(const float* __restrict__ A, const float* __restrict__ xe, const fl
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
             const int i = tid + j * CT_THREADS;
-            if (!BWD) {
+            if (!WT) {
                 *reinterpret_cast<f32x4*>(Wl + (i >> 3) * CT_LD + 4 * (i & 7)) = ((i >> 3) < N && k0 + 4 * (i & 7) < K) ? rw[j] : zero4;
             } else {                     // transposed into the k-contiguous LDS rows
                 const int kk = i / (NT * 8), n = 4 * (i % (NT * 8));
@@ -225,10 +314,10 @@ void ct_gemm(const float* __restrict__ A, const float* __restrict__ xe, const fl
             }
         }
     };
-    typename Addr::Col co[NT];                           // data gradient: this lane's columns inside a row
+    typename EA::Col co[NT];                             // data gradient: this lane's columns inside a row
     if (BWD) {
 #pragma unroll
-        for (int t = 0; t < NT; ++t) co[t] = Addr::col_off(std::min(n0 + t * 32 + li, N - 1), Ci, row_stride);
+        for (int t = 0; t < NT; ++t) co[t] = EA::col_off(std::min(n0 + t * 32 + li, N - 1), Ci, EA::row_stride(geo, Ci));
     }
     if ((int64_t)blockIdx.x < n_tiles) fetch((int64_t)blockIdx.x * CT_BM, 0, true);
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
@@ -273,7 +362,7 @@ void ct_gemm(const float* __restrict__ A, const float* __restrict__ xe, const fl
         } else {
             const int64_t mf = m0 + wave * 32 + 4 * hh;                    // this lane's first row: rows mf + 8 (r / 4) + r % 4
             if (mf < M) {
-                const typename Addr::Row p = Addr::row_pos(mf, OW);
+                const typename EA::Row p = EA::row_pos(mf, geo);
                 // one element of the row at `base`; the order of the calls is the order of the fp64 sums, which defines the
                 // bits of g_a and g_b
                 auto element = [&](int t, int r, int64_t base) __attribute__((always_inline)) {
@@ -285,11 +374,11 @@ void ct_gemm(const float* __restrict__ A, const float* __restrict__ xe, const fl
                     if (out) out[e] = v;
                 };
                 auto row_d = [](int r) __attribute__((always_inline)) { return (unsigned)(8 * (r >> 2) + (r & 3)); };
-                if constexpr (Addr::SUMS_ROW_OUTER) {    // the row's base (Down2x2: a division) once per row
+                if constexpr (EA::SUMS_ROW_OUTER) {    // the row's base (Down2x2: a division) once per row
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         if (mf + row_d(r) < M) {
-                            const int64_t base = Addr::row_base(p, row_d(r), OW, Ci);
+                            const int64_t base = EA::row_base(p, row_d(r), geo, Ci);
 #pragma unroll
                             for (int t = 0; t < NT; ++t)
                                 if (n0 + t * 32 + li < N) element(t, r, base);
@@ -301,7 +390,7 @@ void ct_gemm(const float* __restrict__ A, const float* __restrict__ xe, const fl
                     for (int t = 0; t < NT; ++t)
 #pragma unroll
                         for (int r = 0; r < 16; ++r)
-                            if (n0 + t * 32 + li < N && mf + row_d(r) < M) element(t, r, Addr::row_base(p, row_d(r), OW, Ci));
+                            if (n0 + t * 32 + li < N && mf + row_d(r) < M) element(t, r, EA::row_base(p, row_d(r), geo, Ci));
                 }
             }
         }
@@ -312,7 +401,7 @@ void ct_gemm(const float* __restrict__ A, const float* __restrict__ xe, const fl
         if (lane == 0) { red[0][wave] = s0; red[1][wave] = s1; }
         __syncthreads();
         if (tid == 0) {
-            const int64_t row = Addr::MAX_PIECES > 1 ? (int64_t)blockIdx.y * gridDim.x + blockIdx.x : (int64_t)blockIdx.x;
+            const int64_t row = (WT && EA::MAX_PIECES > 1) ? (int64_t)blockIdx.y * gridDim.x + blockIdx.x : (int64_t)blockIdx.x;
             partials[row * 2 + 0] = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
             partials[row * 2 + 1] = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
         }
@@ -352,7 +441,7 @@ void ct_sum_final(const double* __restrict__ partials, int n_rows, float* __rest
 template <class Addr, int NCO, int NCN, int PRE>
 __global__ __launch_bounds__(CT_THREADS)
 void ct_wgrad(const float* __restrict__ g, const float* __restrict__ x, const float* __restrict__ pa,
-              const float* __restrict__ pb, int64_t M, int OW, int Ci, int Co, double* __restrict__ slots) {
+              const float* __restrict__ pb, int64_t M, Geo geo, int Ci, int Co, double* __restrict__ slots) {
     static_assert(CT_WM == 8 * CT_PG && CT_RUN % CT_WM == 0 && (CT_RUN / CT_WM) % 2 == 0, "a block is one load group per wave");
     __shared__ float red[NCO * NCN * 16 * 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, hh = lane >> 5;
@@ -361,7 +450,7 @@ void ct_wgrad(const float* __restrict__ g, const float* __restrict__ x, const fl
     const int co0 = (blockIdx.y / tiles_n) * 32 * NCO, n0 = (blockIdx.y % tiles_n) * 32 * NCN;
     const float a = PRE == 2 ? *pa : 0.f, b = PRE >= 1 ? *pb : 0.f;
     const int64_t n_blocks = (M + CT_WM - 1) / CT_WM;
-    const int64_t row_stride = (int64_t)2 * OW * Ci;
+    const int64_t row_stride = Addr::row_stride(geo, Ci);
     const int P = gridDim.x;
     int cg[NCO];                                          // this lane's channels / column offsets, clamped for the loads
     typename Addr::Col cx[NCN];
@@ -390,14 +479,14 @@ void ct_wgrad(const float* __restrict__ g, const float* __restrict__ x, const fl
         const int64_t base = std::min(base_of(blk), (n_blocks - 1) * CT_WM);
         const int last = (int)std::min<int64_t>(CT_WM - 1, M - 1 - base);
         const float* gb = g + base * Co;
-        const typename Addr::Row p = Addr::row_pos(base, OW);
+        const typename Addr::Row p = Addr::row_pos(base, geo);
 #pragma unroll
         for (int q = 0; q < CT_PG; ++q) {
             const unsigned r = (unsigned)std::min(row_in(q), last);
 #pragma unroll
             for (int s = 0; s < NCO; ++s) bg[buf][q][s] = gb[r * (unsigned)Co + (unsigned)cg[s]];
 #pragma unroll
-            for (int t = 0; t < NCN; ++t) bx[buf][q][t] = *Addr::x_ptr(x, p, r, cx[t], OW, Ci);
+            for (int t = 0; t < NCN; ++t) bx[buf][q][t] = *Addr::x_ptr(x, p, r, cx[t], geo, Ci);
         }
     };
     auto compute = [&](int blk, int buf) __attribute__((always_inline)) {
@@ -475,9 +564,9 @@ void ct_wgrad(const float* __restrict__ g, const float* __restrict__ x, const fl
 }
 
 // slots [P][n], n = Co N elements in the kernels' order [Co][taps][Ci] -> g_w in the weight's own layout: w_layout 1 is that
-// order (Dense always; Down2x2's [Co][2][2][Ci]), w_layout 0 is Down2x2's [Co][Ci][2][2].
+// order (Dense always; [Co][2][2][Ci], [Co][3][3][Ci]), w_layout 0 is [Co][Ci][taps] (Down2x2: taps = 4, Circ3x3: 9).
 __global__ __launch_bounds__(CT_THREADS)
-void ct_wgrad_final(const double* __restrict__ slots, int P, int n, int Ci, int w_layout, float* __restrict__ g_w) {
+void ct_wgrad_final(const double* __restrict__ slots, int P, int n, int Ci, int taps, int w_layout, float* __restrict__ g_w) {
     const int i = blockIdx.x * CT_THREADS + threadIdx.x;
     if (i >= n) return;
     // index order, 32 loads in flight at a time (a slot past the end reads the last one and is not added)
@@ -491,13 +580,13 @@ void ct_wgrad_final(const double* __restrict__ slots, int P, int n, int Ci, int 
     }
     int o = i;
     if (w_layout == 0) {
-        const int co = i / (4 * Ci), r = i - co * 4 * Ci, tap = r / Ci, ci = r - tap * Ci;
-        o = co * 4 * Ci + ci * 4 + tap;
+        const int co = i / (taps * Ci), r = i - co * taps * Ci, tap = r / Ci, ci = r - tap * Ci;
+        o = co * taps * Ci + ci * taps + tap;
     }
     g_w[o] = (float)s;
 }
 
-// ---- host: plans, the launch ladders, the backward both nodes share ---------------------------------------------------------
+// ---- host: plans, the launch ladders, the backward all nodes share ----------------------------------------------------------
 inline bool supported(int cin, int cout) {
     return cin >= 8 && cout >= 8 && cin <= CT_MAXC && cout <= CT_MAXC && cin % 8 == 0 && cout % 8 == 0;
 }
@@ -519,96 +608,130 @@ inline size_t slots_and_partials_bytes(const WgradPlan& p, int cin, int cout) {
     return (size_t)p.P * Addr::TAPS * cin * cout * sizeof(double) + (size_t)CT_MAX_WG * Addr::MAX_PIECES * 2 * sizeof(double) + 256;
 }
 
-template <class Addr, bool BWD>
+template <class AA, class EA, bool BWD, bool WT>
 inline void launch_gemm(int nt, dim3 grid, hipStream_t stream, const float* A, const float* xe, const float* pa, const float* pb,
-                        int pre, const float* w, int64_t M, int OW, int Ci, int K, int N, float* out, double* partials) {
-    if (nt == 1) ct_gemm<Addr, 1, BWD><<<grid, CT_THREADS, 0, stream>>>(A, xe, pa, pb, pre, w, M, OW, Ci, K, N, out, partials);
-    else if (nt == 2) ct_gemm<Addr, 2, BWD><<<grid, CT_THREADS, 0, stream>>>(A, xe, pa, pb, pre, w, M, OW, Ci, K, N, out, partials);
-    else if (nt == 4) ct_gemm<Addr, 4, BWD><<<grid, CT_THREADS, 0, stream>>>(A, xe, pa, pb, pre, w, M, OW, Ci, K, N, out, partials);
-    else ct_gemm<Addr, 8, BWD><<<grid, CT_THREADS, 0, stream>>>(A, xe, pa, pb, pre, w, M, OW, Ci, K, N, out, partials);
+                        int pre, const float* w, int64_t M, Geo geo, int Ca, int Ci, int K, int N, float* out, double* partials) {
+    if (nt == 1) ct_gemm<AA, EA, 1, BWD, WT><<<grid, CT_THREADS, 0, stream>>>(A, xe, pa, pb, pre, w, M, geo, Ca, Ci, K, N, out, partials);
+    else if (nt == 2) ct_gemm<AA, EA, 2, BWD, WT><<<grid, CT_THREADS, 0, stream>>>(A, xe, pa, pb, pre, w, M, geo, Ca, Ci, K, N, out, partials);
+    else if (nt == 4) ct_gemm<AA, EA, 4, BWD, WT><<<grid, CT_THREADS, 0, stream>>>(A, xe, pa, pb, pre, w, M, geo, Ca, Ci, K, N, out, partials);
+    else ct_gemm<AA, EA, 8, BWD, WT><<<grid, CT_THREADS, 0, stream>>>(A, xe, pa, pb, pre, w, M, geo, Ca, Ci, K, N, out, partials);
 }
 
 template <class Addr, int NCO, int NCN>
 inline void launch_wgrad_pre(int pre, dim3 grid, hipStream_t stream, const float* g, const float* x, const float* a, const float* b,
-                             int64_t m, int ow, int cin, int cout, double* slots) {
-    if (pre == 0) ct_wgrad<Addr, NCO, NCN, 0><<<grid, CT_THREADS, 0, stream>>>(g, x, a, b, m, ow, cin, cout, slots);
-    else if (pre == 1) ct_wgrad<Addr, NCO, NCN, 1><<<grid, CT_THREADS, 0, stream>>>(g, x, a, b, m, ow, cin, cout, slots);
-    else ct_wgrad<Addr, NCO, NCN, 2><<<grid, CT_THREADS, 0, stream>>>(g, x, a, b, m, ow, cin, cout, slots);
+                             int64_t m, Geo geo, int cin, int cout, double* slots) {
+    if (pre == 0) ct_wgrad<Addr, NCO, NCN, 0><<<grid, CT_THREADS, 0, stream>>>(g, x, a, b, m, geo, cin, cout, slots);
+    else if (pre == 1) ct_wgrad<Addr, NCO, NCN, 1><<<grid, CT_THREADS, 0, stream>>>(g, x, a, b, m, geo, cin, cout, slots);
+    else ct_wgrad<Addr, NCO, NCN, 2><<<grid, CT_THREADS, 0, stream>>>(g, x, a, b, m, geo, cin, cout, slots);
 }
 
 template <class Addr>
 inline void launch_wgrad(int nco, int ncn, int pre, dim3 grid, hipStream_t stream, const float* g, const float* x, const float* a,
-                         const float* b, int64_t m, int ow, int cin, int cout, double* slots) {
-    if (nco == 1 && ncn == 1) launch_wgrad_pre<Addr, 1, 1>(pre, grid, stream, g, x, a, b, m, ow, cin, cout, slots);
-    else if (nco == 1) launch_wgrad_pre<Addr, 1, 2>(pre, grid, stream, g, x, a, b, m, ow, cin, cout, slots);
-    else if (ncn == 1) launch_wgrad_pre<Addr, 2, 1>(pre, grid, stream, g, x, a, b, m, ow, cin, cout, slots);
-    else launch_wgrad_pre<Addr, 2, 2>(pre, grid, stream, g, x, a, b, m, ow, cin, cout, slots);
+                         const float* b, int64_t m, Geo geo, int cin, int cout, double* slots) {
+    if (nco == 1 && ncn == 1) launch_wgrad_pre<Addr, 1, 1>(pre, grid, stream, g, x, a, b, m, geo, cin, cout, slots);
+    else if (nco == 1) launch_wgrad_pre<Addr, 1, 2>(pre, grid, stream, g, x, a, b, m, geo, cin, cout, slots);
+    else if (ncn == 1) launch_wgrad_pre<Addr, 2, 1>(pre, grid, stream, g, x, a, b, m, geo, cin, cout, slots);
+    else launch_wgrad_pre<Addr, 2, 2>(pre, grid, stream, g, x, a, b, m, geo, cin, cout, slots);
 }
 
 inline int tiles_for(int n) { return n <= 32 ? 1 : n <= 64 ? 2 : n <= 128 ? 4 : 8; }
 inline int gemm_grid(int64_t m) { return (int)std::min<int64_t>(CT_MAX_WG, ceil_div(m, CT_BM)); }
+inline int blocks_for(int n) { return (n + CT_THREADS - 1) / CT_THREADS; }
 
+// w [Co][TAPS Ci]: k-contiguous against the operand's rows
 template <class Addr>
-inline int forward(const float* x, const float* a, const float* b, int pre, const float* w, int64_t m, int ow, int cin, int cout,
+inline int forward(const float* x, const float* a, const float* b, int pre, const float* w, int64_t m, Geo geo, int cin, int cout,
                    float* y, hipStream_t stream) {
-    launch_gemm<Addr, false>(tiles_for(cout), dim3(gemm_grid(m)), stream, x, nullptr, a, b, pre, w, m, ow, cin, Addr::TAPS * cin,
-                             cout, y, nullptr);
+    launch_gemm<Addr, Dense, false, false>(tiles_for(cout), dim3(gemm_grid(m)), stream, x, nullptr, a, b, pre, w, m, geo, cin, cin,
+                                          Addr::TAPS * cin, cout, y, nullptr);
     VQAE_LAUNCH_CHECK();
     return VQAE_OK;
 }
 
-// w is k-contiguous against the operand's rows unless w_layout == 0, in which case wp receives that form first (Down2x2 alone).
+// The workspace of the nodes with a weight of more than one tap: [wp][wt][slots][partials], 16-byte aligned.  wp: the weight
+// of w_layout 0 in the k-contiguous order (ct_permute_w);  wt: Circ3x3's flipped, transposed weight (ct_flip_w; no bytes for
+// Down2x2).
+struct Workspace { float* wp; float* wt; double* slots; double* partials; };
 template <class Addr>
-inline int backward(const float* g, const float* x, const float* a, const float* b, int pre, const float* w, int w_layout, float* wp,
-                    const WgradPlan& plan, int64_t m, int ow, int cin, int cout, float* g_x, float* g_w, float* g_a, float* g_b,
-                    double* slots, double* partials, hipStream_t stream) {
+inline size_t weight_bytes(int cin, int cout) { return (size_t)round_up((int64_t)Addr::TAPS * cin * cout * sizeof(float), 256); }
+template <class Addr>
+inline size_t workspace_bytes(int64_t m, int cin, int cout) {
+    return (Addr::GATHERS_GRAD ? 2 : 1) * weight_bytes<Addr>(cin, cout)
+           + slots_and_partials_bytes<Addr>(wgrad_plan<Addr>(m, cin, cout), cin, cout);
+}
+template <class Addr>
+inline Workspace carve(void* ws, const WgradPlan& plan, int cin, int cout) {
+    Workspace o;
+    char* p = (char*)(((uintptr_t)ws + 15) & ~(uintptr_t)15);
+    o.wp = (float*)p;
+    p += weight_bytes<Addr>(cin, cout);
+    o.wt = (float*)p;
+    if (Addr::GATHERS_GRAD) p += weight_bytes<Addr>(cin, cout);
+    o.slots = (double*)p;
+    o.partials = o.slots + (size_t)plan.P * Addr::TAPS * cin * cout;
+    return o;
+}
+
+// w is k-contiguous against the operand's rows unless w_layout == 0.  The scattering data gradient (Dense, Down2x2) then reads
+// ct_permute_w's copy in wk.wp; the gathering one (Circ3x3) reads ct_flip_w's wk.wt, made from either layout.
+template <class Addr>
+inline int backward(const float* g, const float* x, const float* a, const float* b, int pre, const float* w, int w_layout,
+                    const Workspace& wk, const WgradPlan& plan, int64_t m, Geo geo, int cin, int cout, float* g_x, float* g_w,
+                    float* g_a, float* g_b, hipStream_t stream) {
     const int n_all = Addr::TAPS * cin;
     float* o_a = pre == 2 ? g_a : nullptr;
     float* o_b = pre >= 1 ? g_b : nullptr;
     if (g_x || o_a || o_b) {
-        if (w_layout == 0) {
-            ct_permute_w<<<(n_all * cout + CT_THREADS - 1) / CT_THREADS, CT_THREADS, 0, stream>>>(w, cin, n_all * cout, wp);
+        dim3 grid(gemm_grid(m));
+        if constexpr (Addr::GATHERS_GRAD) {
+            ct_flip_w<<<blocks_for(n_all * cout), CT_THREADS, 0, stream>>>(w, cin, cout, w_layout, n_all * cout, wk.wt);
             VQAE_LAUNCH_CHECK();
+            launch_gemm<Addr, Dense, true, false>(tiles_for(cin), grid, stream, g, x, a, b, pre, wk.wt, m, geo, cout, cin,
+                                                  Addr::TAPS * cout, cin, g_x, wk.partials);
+        } else {
+            if (w_layout == 0) {
+                ct_permute_w<<<blocks_for(n_all * cout), CT_THREADS, 0, stream>>>(w, cin, Addr::TAPS, n_all * cout, wk.wp);
+                VQAE_LAUNCH_CHECK();
+            }
+            const int nt = tiles_for(std::min(n_all, 256));
+            grid.y = (unsigned)ceil_div(n_all, 32 * nt);
+            launch_gemm<Dense, Addr, true, true>(nt, grid, stream, g, x, a, b, pre, w_layout == 0 ? wk.wp : w, m, geo, cout, cin,
+                                                 cout, n_all, g_x, wk.partials);
         }
-        const int nt = tiles_for(std::min(n_all, 256));
-        const dim3 grid(gemm_grid(m), (unsigned)ceil_div(n_all, 32 * nt));
-        launch_gemm<Addr, true>(nt, grid, stream, g, x, a, b, pre, w_layout == 0 ? wp : w, m, ow, cin, cout, n_all, g_x, partials);
         VQAE_LAUNCH_CHECK();
         if (o_a || o_b) {
-            ct_sum_final<<<1, CT_THREADS, 0, stream>>>(partials, (int)(grid.x * grid.y), o_a, o_b);
+            ct_sum_final<<<1, CT_THREADS, 0, stream>>>(wk.partials, (int)(grid.x * grid.y), o_a, o_b);
             VQAE_LAUNCH_CHECK();
         }
     }
     if (g_w) {
         const dim3 grid(plan.P, plan.tiles);
-        launch_wgrad<Addr>(plan.nco, plan.ncn, pre, grid, stream, g, x, a, b, m, ow, cin, cout, slots);
+        launch_wgrad<Addr>(plan.nco, plan.ncn, pre, grid, stream, g, x, a, b, m, geo, cin, cout, wk.slots);
         VQAE_LAUNCH_CHECK();
         const int n = n_all * cout;
-        ct_wgrad_final<<<(n + CT_THREADS - 1) / CT_THREADS, CT_THREADS, 0, stream>>>(slots, plan.P, n, cin, w_layout, g_w);
+        ct_wgrad_final<<<blocks_for(n), CT_THREADS, 0, stream>>>(wk.slots, plan.P, n, cin, Addr::TAPS, w_layout, g_w);
         VQAE_LAUNCH_CHECK();
     }
     return VQAE_OK;
 }
 
-// Down2x2: rows M = b (h / 2) (w / 2) when the geometry is valid and M < 2^40, else 0
-inline int64_t down_rows(int64_t b, int h, int w) {
-    if (b < 1 || h < 2 || w < 2 || (h & 1) || (w & 1)) return 0;
-    const int64_t per = (int64_t)(h / 2) * (w / 2);
-    if (per >= (1ll << 40) || b >= (1ll << 40) / per + 1) return 0;
+// b * per rows when b >= 1, per >= 1 and the product is below 2^40, else 0
+inline int64_t rows_below_2_40(int64_t b, int64_t per) {
+    if (b < 1 || per < 1 || per >= (1ll << 40) || b >= (1ll << 40) / per + 1) return 0;
     const int64_t m = b * per;
     return m < (1ll << 40) ? m : 0;
 }
 
-// Down2x2's workspace: [permuted weight, 16-byte aligned][slots][partials]
-struct DownWorkspace { float* wp; double* slots; double* partials; };
-inline size_t wp_bytes(int cin, int cout) { return (size_t)round_up((int64_t)4 * cin * cout * sizeof(float), 256); }
-inline DownWorkspace carve(void* ws, const WgradPlan& plan, int cin, int cout) {
-    DownWorkspace o;
-    char* p = (char*)(((uintptr_t)ws + 15) & ~(uintptr_t)15);
-    o.wp = (float*)p;
-    o.slots = (double*)(p + wp_bytes(cin, cout));
-    o.partials = o.slots + (size_t)plan.P * 4 * cin * cout;
-    return o;
+// Down2x2: rows M = b (h / 2) (w / 2) when the geometry is valid and M < 2^40, else 0
+inline int64_t down_rows(int64_t b, int h, int w) {
+    if (h < 2 || w < 2 || (h & 1) || (w & 1)) return 0;
+    return rows_below_2_40(b, (int64_t)(h / 2) * (w / 2));
+}
+
+// Circ3x3: rows M = b h w when b, h, w >= 1 and M < 2^40, else 0
+inline int64_t circ_rows(int64_t b, int h, int w) {
+    if (h < 1 || w < 1) return 0;
+    return rows_below_2_40(b, (int64_t)h * w);
 }
 
 }  // namespace
@@ -631,7 +754,7 @@ extern "C" int vqae_conv1x1_train_forward_f32(const float* x, const float* a, co
     VQAE_REQUIRE(supported(cin, cout), VQAE_ERR_UNSUPPORTED,
                  "conv1x1_train_forward: cin %d cout %d (multiples of 8, 8 .. %d)", cin, cout, CT_MAXC);
     VQAE_REQUIRE(aligned16({x, w, y}), VQAE_ERR_INVALID, "conv1x1_train_forward: x, w and y must be 16-byte aligned");
-    return forward<Dense>(x, a, b, pre, w, m, 0, cin, cout, y, (hipStream_t)stream_);
+    return forward<Dense>(x, a, b, pre, w, m, Geo{0, 0}, cin, cout, y, (hipStream_t)stream_);
 }
 
 extern "C" int vqae_conv1x1_train_backward_f32(const float* g, const float* x, const float* a, const float* b, int pre,
@@ -646,8 +769,8 @@ extern "C" int vqae_conv1x1_train_backward_f32(const float* g, const float* x, c
                  "conv1x1_train_backward: tensors must be 16-byte aligned, the workspace 8-byte aligned");
     const WgradPlan plan = wgrad_plan<Dense>(m, cin, cout);
     double* slots = (double*)ws;                                               // the workspace: [slots][partials]
-    return backward<Dense>(g, x, a, b, pre, w, 1, nullptr, plan, m, 0, cin, cout, g_x, g_w, g_a, g_b, slots,
-                           slots + (size_t)plan.P * cin * cout, (hipStream_t)stream_);
+    const Workspace wk = {nullptr, nullptr, slots, slots + (size_t)plan.P * cin * cout};
+    return backward<Dense>(g, x, a, b, pre, w, 1, wk, plan, m, Geo{0, 0}, cin, cout, g_x, g_w, g_a, g_b, (hipStream_t)stream_);
 }
 
 // ---- the 2x2, stride-2 node ------------------------------------------------------------------------------------------------
@@ -658,7 +781,7 @@ extern "C" int vqae_conv_down_train_wgrad_run(void) { return CT_RUN; }
 extern "C" size_t vqae_conv_down_train_workspace_bytes(int64_t b, int h, int w, int cin, int cout) {
     const int64_t m = down_rows(b, h, w);
     if (m < 1 || !supported(cin, cout)) return 0;
-    return wp_bytes(cin, cout) + slots_and_partials_bytes<Down2x2>(wgrad_plan<Down2x2>(m, cin, cout), cin, cout);
+    return workspace_bytes<Down2x2>(m, cin, cout);
 }
 
 extern "C" int vqae_conv_down_train_forward_f32(const float* x, const float* a, const float* b, int pre, const float* w,
@@ -679,13 +802,13 @@ extern "C" int vqae_conv_down_train_forward_f32(const float* x, const float* a, 
                  (long long)batch, h / 2, wd / 2);
     VQAE_REQUIRE(aligned16({x, w, y}) && ((uintptr_t)ws & 7) == 0, VQAE_ERR_INVALID,
                  "conv_down_train_forward: x, w and y must be 16-byte aligned, the workspace 8-byte aligned");
-    const DownWorkspace wk = carve(ws, wgrad_plan<Down2x2>(m, cin, cout), cin, cout);
+    const Workspace wk = carve<Down2x2>(ws, wgrad_plan<Down2x2>(m, cin, cout), cin, cout);
     if (w_layout == 0) {
         const int n = 4 * cin * cout;
-        ct_permute_w<<<(n + CT_THREADS - 1) / CT_THREADS, CT_THREADS, 0, stream>>>(w, cin, n, wk.wp);
+        ct_permute_w<<<blocks_for(n), CT_THREADS, 0, stream>>>(w, cin, 4, n, wk.wp);
         VQAE_LAUNCH_CHECK();
     }
-    return forward<Down2x2>(x, a, b, pre, w_layout == 0 ? wk.wp : w, m, wd / 2, cin, cout, y, stream);
+    return forward<Down2x2>(x, a, b, pre, w_layout == 0 ? wk.wp : w, m, Geo{0, wd / 2}, cin, cout, y, stream);
 }
 
 extern "C" int vqae_conv_down_train_backward_f32(const float* g, const float* x, const float* a, const float* b, int pre,
@@ -705,7 +828,62 @@ extern "C" int vqae_conv_down_train_backward_f32(const float* g, const float* x,
     VQAE_REQUIRE(aligned16({g, x, w, g_x, g_w}) && ((uintptr_t)ws & 7) == 0, VQAE_ERR_INVALID,
                  "conv_down_train_backward: tensors must be 16-byte aligned, the workspace 8-byte aligned");
     const WgradPlan plan = wgrad_plan<Down2x2>(m, cin, cout);
-    const DownWorkspace wk = carve(ws, plan, cin, cout);
-    return backward<Down2x2>(g, x, a, b, pre, w, w_layout, wk.wp, plan, m, wd / 2, cin, cout, g_x, g_w, g_a, g_b, wk.slots,
-                             wk.partials, (hipStream_t)stream_);
+    const Workspace wk = carve<Down2x2>(ws, plan, cin, cout);
+    return backward<Down2x2>(g, x, a, b, pre, w, w_layout, wk, plan, m, Geo{0, wd / 2}, cin, cout, g_x, g_w, g_a, g_b,
+                             (hipStream_t)stream_);
+}
+
+// ---- the circular 3x3, stride-1 node ----------------------------------------------------------------------------------------
+extern "C" int vqae_conv3x3_train_supported(int cin, int cout) { return supported(cin, cout) ? 1 : 0; }
+
+extern "C" int vqae_conv3x3_train_wgrad_run(void) { return CT_RUN; }
+
+extern "C" size_t vqae_conv3x3_train_workspace_bytes(int64_t b, int h, int w, int cin, int cout) {
+    const int64_t m = circ_rows(b, h, w);
+    if (m < 1 || !supported(cin, cout)) return 0;
+    return workspace_bytes<Circ3x3>(m, cin, cout);
+}
+
+extern "C" int vqae_conv3x3_train_forward_f32(const float* x, const float* a, const float* b, int pre, const float* w, int w_layout,
+                                              int64_t batch, int h, int wd, int cin, int cout, float* y, void* ws, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    VQAE_REQUIRE(batch >= 1 && h >= 1 && wd >= 1, VQAE_ERR_INVALID, "conv3x3_train_forward: batch %lld h %d w %d",
+                 (long long)batch, h, wd);
+    VQAE_REQUIRE(pre >= 0 && pre <= 2, VQAE_ERR_INVALID, "conv3x3_train_forward: pre %d", pre);
+    VQAE_REQUIRE(w_layout >= 0 && w_layout <= 1, VQAE_ERR_INVALID, "conv3x3_train_forward: w_layout %d", w_layout);
+    VQAE_REQUIRE(x && w && y && (ws || w_layout == 1) && (pre < 1 || b) && (pre < 2 || a), VQAE_ERR_INVALID,
+                 "conv3x3_train_forward: null pointer");                   // the forward uses the workspace for w_layout 0 only
+    VQAE_REQUIRE(supported(cin, cout), VQAE_ERR_UNSUPPORTED,
+                 "conv3x3_train_forward: cin %d cout %d (multiples of 8, 8 .. %d)", cin, cout, CT_MAXC);
+    const int64_t m = circ_rows(batch, h, wd);
+    VQAE_REQUIRE(m >= 1, VQAE_ERR_INVALID, "conv3x3_train_forward: batch %lld x %d x %d rows exceed 2^40", (long long)batch, h, wd);
+    VQAE_REQUIRE(aligned16({x, w, y}) && ((uintptr_t)ws & 7) == 0, VQAE_ERR_INVALID,
+                 "conv3x3_train_forward: x, w and y must be 16-byte aligned, the workspace 8-byte aligned");
+    const Workspace wk = carve<Circ3x3>(ws, wgrad_plan<Circ3x3>(m, cin, cout), cin, cout);
+    if (w_layout == 0) {
+        const int n = 9 * cin * cout;
+        ct_permute_w<<<blocks_for(n), CT_THREADS, 0, stream>>>(w, cin, 9, n, wk.wp);
+        VQAE_LAUNCH_CHECK();
+    }
+    return forward<Circ3x3>(x, a, b, pre, w_layout == 0 ? wk.wp : w, m, Geo{h, wd}, cin, cout, y, stream);
+}
+
+extern "C" int vqae_conv3x3_train_backward_f32(const float* g, const float* x, const float* a, const float* b, int pre,
+                                               const float* w, int w_layout, int64_t batch, int h, int wd, int cin, int cout,
+                                               float* g_x, float* g_w, float* g_a, float* g_b, void* ws, void* stream_) {
+    VQAE_REQUIRE(batch >= 1 && h >= 1 && wd >= 1, VQAE_ERR_INVALID, "conv3x3_train_backward: batch %lld h %d w %d",
+                 (long long)batch, h, wd);
+    VQAE_REQUIRE(pre >= 0 && pre <= 2, VQAE_ERR_INVALID, "conv3x3_train_backward: pre %d", pre);
+    VQAE_REQUIRE(w_layout >= 0 && w_layout <= 1, VQAE_ERR_INVALID, "conv3x3_train_backward: w_layout %d", w_layout);
+    VQAE_REQUIRE(g && x && w && ws && (pre < 1 || b) && (pre < 2 || a), VQAE_ERR_INVALID, "conv3x3_train_backward: null pointer");
+    VQAE_REQUIRE(supported(cin, cout), VQAE_ERR_UNSUPPORTED,
+                 "conv3x3_train_backward: cin %d cout %d (multiples of 8, 8 .. %d)", cin, cout, CT_MAXC);
+    const int64_t m = circ_rows(batch, h, wd);
+    VQAE_REQUIRE(m >= 1, VQAE_ERR_INVALID, "conv3x3_train_backward: batch %lld x %d x %d rows exceed 2^40", (long long)batch, h, wd);
+    VQAE_REQUIRE(aligned16({g, x, w, g_x, g_w}) && ((uintptr_t)ws & 7) == 0, VQAE_ERR_INVALID,
+                 "conv3x3_train_backward: tensors must be 16-byte aligned, the workspace 8-byte aligned");
+    const WgradPlan plan = wgrad_plan<Circ3x3>(m, cin, cout);
+    const Workspace wk = carve<Circ3x3>(ws, plan, cin, cout);
+    return backward<Circ3x3>(g, x, a, b, pre, w, w_layout, wk, plan, m, Geo{h, wd}, cin, cout, g_x, g_w, g_a, g_b,
+                             (hipStream_t)stream_);
 }

@@ -4,7 +4,8 @@ torch's conv2d for the convolutions).  Select through Hydra in the reference's s
     _target_: vqae_amd.layers.fixup_train.PreActFixupResBlock
 The keyword `conv1x1` ("torch", the default, or "hip") is train.block_forward's: "hip" runs the 1x1, stride-1 convs and the op
 in front of each as one fused HIP node (csrc/conv_train.hip).  The independent keyword `conv_down` ("torch" | "hip") does the
-same for the two 2x2, stride-2 convs of a 'down' block (csrc/conv_train.hip).
+same for the two 2x2, stride-2 convs of a 'down' block, the independent keyword `conv3x3` ("torch" | "hip") for the circular
+3x3 conv of a 'same' or 'out' block (csrc/conv_train.hip).
 The inference mirror of conv_block.py is unchanged and still runs under no_grad.
 """
 import torch
@@ -14,13 +15,15 @@ from .conv_block import PreActFixupResBlock as _InferenceBlock
 
 
 class PreActFixupResBlock(_InferenceBlock):
-    def __init__(self, *args, conv1x1: str = "torch", conv_down: str = "torch", **kwargs):
+    def __init__(self, *args, conv1x1: str = "torch", conv_down: str = "torch", conv3x3: str = "torch", **kwargs):
         super().__init__(*args, **kwargs)
         if conv1x1 not in train.CONV1X1_ROUTES:
             raise ValueError(f"conv1x1 must be one of {train.CONV1X1_ROUTES}, not {conv1x1!r}")
         if conv_down not in train.CONV_DOWN_ROUTES:
             raise ValueError(f"conv_down must be one of {train.CONV_DOWN_ROUTES}, not {conv_down!r}")
-        self.conv1x1, self.conv_down = conv1x1, conv_down
+        if conv3x3 not in train.CONV3X3_ROUTES:
+            raise ValueError(f"conv3x3 must be one of {train.CONV3X3_ROUTES}, not {conv3x3!r}")
+        self.conv1x1, self.conv_down, self.conv3x3 = conv1x1, conv_down, conv3x3
 
     def forward(self, inp: torch.Tensor):
-        return train.block_forward(self, inp, conv1x1=self.conv1x1, conv_down=self.conv_down)
+        return train.block_forward(self, inp, conv1x1=self.conv1x1, conv_down=self.conv_down, conv3x3=self.conv3x3)

@@ -340,13 +340,13 @@ def conv_down_train_wgrad_run():
     return int(L.lib().vqae_conv_down_train_wgrad_run())
 
 
-def _conv_down_args(x, w, a, b):
-    """-> (w as the library reads it, w_layout, cin, cout, pre).  A channels_last [Co, Ci, 2, 2] weight is [Co][2][2][Ci] in
+def _conv_down_args(x, w, a, b, kernel=(2, 2)):
+    """-> (w as the library reads it, w_layout, cin, cout, pre).  A channels_last [Co, Ci, kh, kw] weight is [Co][kh][kw][Ci] in
     memory and is passed as it lies (w_layout 1); anything else is made contiguous (w_layout 0).  No copy for either of the
     two ways torch stores a dense fp32 weight."""
     w = w.detach().float()
     cout, cin = w.shape[0], w.shape[1]
-    assert x.dim() == 4 and tuple(w.shape[2:]) == (2, 2) and x.shape[-1] == cin, (x.shape, w.shape)
+    assert x.dim() == 4 and tuple(w.shape[2:]) == kernel and x.shape[-1] == cin, (x.shape, w.shape)
     assert a is None or b is not None, "pre-op: none (a, b None), x + b (a None), ELU(x + a) + b"
     if w.is_contiguous(memory_format=torch.channels_last) and not w.is_contiguous():
         layout = 1
@@ -392,6 +392,57 @@ def conv_down_train_backward(g, x, w, a=None, b=None, need_x=True, need_w=True):
     ws = _conv_down_ws(x, cin, cout)
     L.check(L.lib().vqae_conv_down_train_backward_f32(_p(g), _p(x), _p(_scalar(a)), _p(_scalar(b)), pre, _p(wc), layout, B, H, W,
                                                       cin, cout, _p(g_x), _p(g_w), _p(g_a), _p(g_b), _p(ws), _stream()))
+    return g_x, g_w, g_a, g_b
+
+
+def conv3x3_train_supported(cin, cout):
+    """Whether the trainable circular 3x3 conv kernels take (cin, cout); any H, W >= 1.  Needs no GPU."""
+    return bool(L.lib().vqae_conv3x3_train_supported(int(cin), int(cout)))
+
+
+def conv3x3_train_wgrad_run():
+    """R: the longest fp32 accumulation run of the weight gradient, in rows."""
+    return int(L.lib().vqae_conv3x3_train_wgrad_run())
+
+
+def _conv3x3_ws(x, cin, cout):
+    B, H, W, _ = x.shape
+    return torch.empty(L.lib().vqae_conv3x3_train_workspace_bytes(B, H, W, cin, cout), dtype=torch.uint8, device=x.device)
+
+
+def conv3x3_train_forward(x, w, a=None, b=None):
+    """y [B, H, W, Co] = the 3x3, stride-1 conv with circular padding 1 of u [B, H, W, Ci] with w [Co, Ci, 3, 3] (contiguous or
+    channels_last, read in place); u = x (a, b None), x + b (a None) or ELU(x + a) + b, with a, b one-element device tensors.
+    Neither u nor its halo is materialised."""
+    _need_gpu(x, w)
+    x = x.contiguous()
+    wc, layout, cin, cout, pre = _conv_down_args(x, w, a, b, kernel=(3, 3))
+    B, H, W, _ = x.shape
+    y = torch.empty((B, H, W, cout), dtype=torch.float32, device=x.device)
+    ws = _conv3x3_ws(x, cin, cout) if layout == 0 else None
+    L.check(L.lib().vqae_conv3x3_train_forward_f32(_p(x), _p(_scalar(a)), _p(_scalar(b)), pre, _p(wc), layout, B, H, W, cin,
+                                                   cout, _p(y), _p(ws), _stream()))
+    return y
+
+
+def conv3x3_train_backward(g, x, w, a=None, b=None, need_x=True, need_w=True):
+    """-> (g_x [B, H, W, Ci] | None, g_w (w's shape and memory format) | None, g_a [1] | None, g_b [1] | None) from
+    g [B, H, W, Co] and the forward's x, w, a, b: g_u = the data gradient (gathered: the circular 3x3 of g with the flipped,
+    transposed weight), g_x = g_u * ELU'(x + a) (g_u without an activation), g_a = sum g_x, g_b = sum g_u, g_w = the weight
+    gradient with u recomputed from x."""
+    _need_gpu(g, x, w)
+    g, x = g.contiguous(), x.contiguous()
+    wc, layout, cin, cout, pre = _conv_down_args(x, w, a, b, kernel=(3, 3))
+    B, H, W, _ = x.shape
+    assert tuple(g.shape) == (B, H, W, cout), (g.shape, x.shape, w.shape)
+    dev = g.device
+    g_x = torch.empty_like(x) if need_x else None
+    g_w = torch.empty_like(wc) if need_w else None              # dense: the same strides, i.e. the same layout
+    g_a = torch.empty(1, dtype=torch.float32, device=dev) if pre == 2 else None
+    g_b = torch.empty(1, dtype=torch.float32, device=dev) if pre >= 1 else None
+    ws = _conv3x3_ws(x, cin, cout)
+    L.check(L.lib().vqae_conv3x3_train_backward_f32(_p(g), _p(x), _p(_scalar(a)), _p(_scalar(b)), pre, _p(wc), layout, B, H, W,
+                                                    cin, cout, _p(g_x), _p(g_w), _p(g_a), _p(g_b), _p(ws), _stream()))
     return g_x, g_w, g_a, g_b
 
 

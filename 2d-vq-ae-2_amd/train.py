@@ -16,14 +16,24 @@ The 2x2, stride-2 convs of a 'down' block (branch_conv2, skip_conv) have one beh
                                  branch_conv2, fixup_add + skip_conv): the activation in front of branch_conv2, the largest tensor
                                  of a step, is never written.  Odd H or W and channel counts outside the kernels' rule take the
                                  torch route, counted in stats["conv_down_fallbacks"]; stats["conv_down_hip"] counts the nodes.
-With both keywords at their defaults the graph is op for op the one described above.
-The 3x3 convs, the stems and the quantiser's projections stay with torch.
+The circular 3x3 conv of a 'same' or 'out' block (branch_conv2, 9/11 of a trunk block's FLOPs) has one behind the independent
+keyword `conv3x3`:
+
+    conv3x3="torch" (default)    fixup_act(..., halo=1) writes ELU(t + bias2a) + bias2b with its circular halo,
+                                 [B, H + 2, W + 2, C], and F.conv2d runs on that, as always
+    conv3x3="hip"                ONE node of csrc/conv_train.hip: the activation is folded into the operand staging and the wrap
+                                 into the operand addressing, so neither the activation nor its halo is written or kept.  Channel
+                                 counts outside the kernels' rule take the torch route, counted in stats["conv3x3_fallbacks"];
+                                 stats["conv3x3_hip"] counts the nodes.
+With all three keywords at their defaults the graph is op for op the one described above.
+The zero-padded 3x3 skip_conv of an 'out' block, the stems and the quantiser's projections stay with torch.
 
     block_forward(block, x)      one block, NCHW in and out, any of the four modes, with or without a skip_conv
     forward_train(model, x)      VQAE.forward (vq_ae/model.py:41-48) over a vqae_amd.model.VQAE mirror -> (out, (vq_loss,))
     step(model, batch, loss_f)   VQAE.step (vq_ae/model.py:114-122) -> (out, recon_loss, (vq_loss,))
     conv1x1(x, w, a, b)          the fused node on [B, H, W, Ci]
     conv_down(x, w, a, b)        the fused 2x2, stride-2 node: [B, H, W, Ci] -> [B, H/2, W/2, Co]
+    conv3x3(x, w, a, b)          the fused circular 3x3 node: [B, H, W, Ci] -> [B, H, W, Co]
 
 The functional ops (fixup_act, fixup_add, fixup_out, bicubic_up2) take channel-last tensors [B, H, W, C], like every other
 op of the package.  The graph stays channel-last throughout (the reference trains in channels_last: model.py:124-126): a conv
@@ -33,8 +43,10 @@ sees the NCHW-shaped view of an NHWC tensor, and a conv result that comes back i
 The one-element parameters (bias1a .. bias4, scale, bias1c / bias1d) are read by the kernels from device memory and their
 gradients are written to device tensors by fixed-order fp64 sums: a step never synchronises the host for them, and two runs
 of any op here give the same bits -- under conv1x1="hip" the 1x1 convs and their weight gradients included, under
-conv_down="hip" the 2x2, stride-2 ones.  (A whole step also runs MIOpen's gradients of the remaining convs -- the 3x3 ones,
-the stems, the quantiser's projections -- for which no such claim is made.)
+conv_down="hip" the 2x2, stride-2 ones, under conv3x3="hip" the circular 3x3 ones: under conv1x1="hip", conv3x3="hip" no conv
+of a 'same' block is MIOpen's, and every gradient of the block repeats bit for bit.  (A whole step also runs MIOpen's gradients
+of the remaining convs -- the zero-padded 3x3 skip of 'out' blocks, the stems, the quantiser's projections -- for which no such
+claim is made.)
 
 Each Function has a restatement in plain torch ops, taken when its tensors are on the CPU: the same forward, and the SAME
 hand-derived backward (the gather-fold of the halo, the bicubic adjoint, the fixed-order sums), which is what
@@ -52,9 +64,10 @@ from .layers.conv_block import PreActFixupResBlock
 from .layers.vq import ProjectedEMAVectorQuantizer2d
 
 stats = {"layout_checks": 0, "layout_copies": 0, "conv1x1_hip": 0, "conv1x1_fallbacks": 0, "conv_down_hip": 0,
-         "conv_down_fallbacks": 0}
+         "conv_down_fallbacks": 0, "conv3x3_hip": 0, "conv3x3_fallbacks": 0}
 CONV1X1_ROUTES = ("torch", "hip")
 CONV_DOWN_ROUTES = ("torch", "hip")
+CONV3X3_ROUTES = ("torch", "hip")
 
 _W75 = (-0.03515625, 0.26171875, 0.87890625, -0.10546875)     # even outputs: inputs m-2 .. m+1, m = o >> 1
 _W25 = (-0.10546875, 0.87890625, 0.26171875, -0.03515625)     # odd outputs:  inputs m-1 .. m+2
@@ -337,6 +350,41 @@ def conv_down(x, w, a=None, b=None):
     return _ConvDownFn.apply(x, w, a, b)
 
 
+class _Conv3x3Fn(_PreConvFn):
+    """y [B, H, W, Co] = the 3x3, stride-1 conv with circular padding 1 (no bias) of u [B, H, W, Ci] with w [Co, Ci, 3, 3].  The
+    taps overlap: the data gradient is the fold of the padded one (the adjoint of the wrap), g_w a matmul on the unfolded
+    patches of the padded u."""
+
+    @staticmethod
+    def _forward(x, w, a, b):
+        if x.is_cuda:
+            return ops.conv3x3_train_forward(x.float(), w, a, b)
+        return to_nhwc(F.conv2d(to_nchw(pad_circular_nhwc(_pre_op_torch(x, a, b))), w))
+
+    @staticmethod
+    def _backward(g, x, w, a, b, need_x, need_w):
+        if g.is_cuda:
+            return ops.conv3x3_train_backward(_dense(g.float()), x.float(), w, a, b, need_x, need_w)
+        Co = g.shape[-1]
+        # the padded data gradient [B, H + 2, W + 2, Ci]: pixel (p, q) collects g[p - kh][q - kw] . w[:, :, kh, kw]
+        g_u = fold_circular_nhwc(F.conv_transpose2d(to_nchw(g), w).permute(0, 2, 3, 1))
+        g_x = g_u * elu_grad(x + a) if a is not None else g_u
+        g_w = None
+        if need_w:
+            patches = pad_circular_nhwc(_pre_op_torch(x, a, b)).unfold(1, 3, 1).unfold(2, 3, 1)      # [B, H, W, Ci, kh, kw]
+            g_w = (g.reshape(-1, Co).t() @ patches.reshape(-1, 9 * x.shape[-1])).reshape(w.shape)
+            if not w.is_contiguous() and w.is_contiguous(memory_format=torch.channels_last):
+                g_w = g_w.contiguous(memory_format=torch.channels_last)
+        return g_x, g_w, g_x.sum(), g_u.sum()
+
+
+def conv3x3(x, w, a=None, b=None):
+    """The 3x3, stride-1, circular-padding-1 conv on [B, H, W, Ci] -> [B, H, W, Co], w [Co, Ci, 3, 3], of ELU(x + a) + b (a
+    None: of x + b; both None: of x) as ONE node: csrc/conv_train.hip on the device, a plain-torch restatement on CPU tensors."""
+    assert a is None or b is not None
+    return _Conv3x3Fn.apply(x, w, a, b)
+
+
 def fixup_act(x, a, b, halo=0):
     """ELU(x + a) + b on [B, H, W, C]; halo = 1: [B, H + 2, W + 2, C] with the circular wrap written."""
     return _ActFn.apply(x, a, b, int(halo))
@@ -392,18 +440,31 @@ def _pre_conv_down(hip, x, a, b, w):
     return _conv(x, w, stride=2)
 
 
-def block_forward_nhwc(block, x, conv1x1="torch", conv_down="torch"):
+def _pre_conv3x3(hip, x, a, b, w):
+    """The circular 3x3 conv of ELU(x + a) + b.  hip: one fused node where the kernels take the channel counts; any other
+    shape takes the torch route -- the activation writes the wrap, the conv pads nothing -- and is counted."""
+    if hip:
+        if tuple(w.shape[2:]) == (3, 3) and ops.conv3x3_train_supported(w.shape[1], w.shape[0]):
+            stats["conv3x3_hip"] += 1
+            return conv3x3(x, w, a, b)
+        stats["conv3x3_fallbacks"] += 1
+    return _conv(fixup_act(x, a, b, halo=1), w)
+
+
+def block_forward_nhwc(block, x, conv1x1="torch", conv_down="torch", conv3x3="torch"):
     """conv_block.py:196-216 on [B, H, W, C] with a graph: the fused ops around F.conv2d.  conv1x1 = "hip": every 1x1, stride-1
     conv the kernels support is one node with the op in front of it (csrc/conv_train.hip); conv_down = "hip": so is each
-    2x2, stride-2 conv of a 'down' block (csrc/conv_train.hip); "torch": F.conv2d."""
+    2x2, stride-2 conv of a 'down' block; conv3x3 = "hip": so is the circular 3x3 of a 'same' or 'out' block; "torch":
+    F.conv2d."""
     if not isinstance(block, PreActFixupResBlock):
         raise NotImplementedError(f"training is implemented for Fixup blocks only (no MBConv / BatchNorm training), not "
                                   f"{type(block).__name__}")
     hip, down = _route("conv1x1", conv1x1, CONV1X1_ROUTES), _route("conv_down", conv_down, CONV_DOWN_ROUTES)
+    circ = _route("conv3x3", conv3x3, CONV3X3_ROUTES)
     mode = block.mode
     t = _pre_conv1x1(hip, x, block.bias1a, block.bias1b, block.branch_conv1.weight)
-    if mode in ("same", "out"):                         # 3x3 circular: the activation writes the wrap, the conv pads nothing
-        t = _conv(fixup_act(t, block.bias2a, block.bias2b, halo=1), block.branch_conv2.weight)
+    if mode in ("same", "out"):                         # 3x3 circular
+        t = _pre_conv3x3(circ, t, block.bias2a, block.bias2b, block.branch_conv2.weight)
     elif mode == "down":
         t = _pre_conv_down(down, t, block.bias2a, block.bias2b, block.branch_conv2.weight)
     else:                                               # ResizeConv2D: bicubic x2, then 1x1
@@ -428,9 +489,10 @@ def _compute_dtype(x):
     return x if x.dtype == torch.float64 and not x.is_cuda else x.float()
 
 
-def block_forward(block, x, conv1x1="torch", conv_down="torch"):
+def block_forward(block, x, conv1x1="torch", conv_down="torch", conv3x3="torch"):
     """One PreActFixupResBlock mirror on an NCHW-shaped tensor (channels_last preferred: no copy) -> NCHW-shaped, with a graph."""
-    return to_nchw(block_forward_nhwc(block, to_nhwc(_compute_dtype(x)), conv1x1=conv1x1, conv_down=conv_down))
+    return to_nchw(block_forward_nhwc(block, to_nhwc(_compute_dtype(x)), conv1x1=conv1x1, conv_down=conv_down,
+                                      conv3x3=conv3x3))
 
 
 def block_forward_torch(block, x):
@@ -486,36 +548,38 @@ def _quantize_torch(vq, inputs):
     return q, idx.reshape(cl.shape[:-1]), loss
 
 
-def forward_train(model, x, return_indices=False, conv1x1="torch", conv_down="torch"):
+def forward_train(model, x, return_indices=False, conv1x1="torch", conv_down="torch", conv3x3="torch"):
     """VQAE.forward (vq_ae/model.py:41-48) over a vqae_amd.model.VQAE mirror, with a graph: -> (out, (vq_loss,)), out NCHW-shaped
     (channels_last).  The stems are F.conv2d, the blocks block_forward, the quantiser its own trainable mirror (its EMA buffers
-    are updated in training mode, as in the reference).  conv1x1 / conv_down: the routes of the blocks' 1x1 and 2x2, stride-2
-    convs (block_forward_nhwc)."""
+    are updated in training mode, as in the reference).  conv1x1 / conv_down / conv3x3: the routes of the blocks' 1x1, 2x2
+    stride-2 and circular 3x3 convs (block_forward_nhwc)."""
     _route("conv1x1", conv1x1, CONV1X1_ROUTES)
     _route("conv_down", conv_down, CONV_DOWN_ROUTES)
+    _route("conv3x3", conv3x3, CONV3X3_ROUTES)
+    routes = dict(conv1x1=conv1x1, conv_down=conv_down, conv3x3=conv3x3)
     enc, dec = model.encoder, model.decoder
     h = to_nhwc(_compute_dtype(x))
     h = _conv(h, enc.in_stem.weight, enc.in_stem.bias, padding=1)
     for level in enc.down_layers[0].layers:
         for blk in level.layers:
-            h = block_forward_nhwc(blk, h, conv1x1=conv1x1, conv_down=conv_down)
+            h = block_forward_nhwc(blk, h, **routes)
     for blk in enc.pre_enc_layers[0]:
-        h = block_forward_nhwc(blk, h, conv1x1=conv1x1, conv_down=conv_down)
+        h = block_forward_nhwc(blk, h, **routes)
     vq = enc.vq_layers[0]
     q, idx, vq_loss = vq(to_nchw(h)) if h.is_cuda else _quantize_torch(vq, to_nchw(h))
     h = to_nhwc(q)
     for blk in dec.post_enc_layers[0]:
-        h = block_forward_nhwc(blk, h, conv1x1=conv1x1, conv_down=conv_down)
+        h = block_forward_nhwc(blk, h, **routes)
     for level in dec.up_layers[0].layers:
         for blk in level.layers:
-            h = block_forward_nhwc(blk, h, conv1x1=conv1x1, conv_down=conv_down)
+            h = block_forward_nhwc(blk, h, **routes)
     out = to_nchw(_conv(h, dec.out_stem.weight, dec.out_stem.bias, padding=1))
     if return_indices:
         return out, (vq_loss,), (idx,)
     return out, (vq_loss,)
 
 
-def step(model, batch, loss_f=F.huber_loss, conv1x1="torch", conv_down="torch"):
+def step(model, batch, loss_f=F.huber_loss, conv1x1="torch", conv_down="torch", conv3x3="torch"):
     """VQAE.step (vq_ae/model.py:114-122): -> (out, recon_loss, (vq_loss,)); the caller backpropagates recon_loss + sum(vq_loss)."""
-    out, encoding_loss = forward_train(model, batch, conv1x1=conv1x1, conv_down=conv_down)
+    out, encoding_loss = forward_train(model, batch, conv1x1=conv1x1, conv_down=conv_down, conv3x3=conv3x3)
     return out, loss_f(input=out, target=batch), encoding_loss

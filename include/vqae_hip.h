@@ -851,6 +851,46 @@ int vqae_conv_down_train_backward_f32(const float* g_dev, const float* x_dev, co
                                       void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * 6e. Trainable circular 3x3 convolution of a Fixup 'same' / 'out' block (conv_block.py:196-216: branch_conv2;
+ *     conf/model/layers/conv_layer/same2d.yaml: kernel 3, stride 1, padding 1, padding_mode circular, no bias), fp32, NHWC, with
+ *     the element-wise op in front of the conv folded into the operand load as in 6c:
+ *         x [batch][h][w][cin];  y [batch][h][w][cout];  m = batch h w rows
+ *         y[b][i][j][co] = sum_{kh,kw,ci} u[b][(i + kh - 1) mod h][(j + kw - 1) mod w][ci] w[co][ci][kh][kw],   u from x by `pre`
+ *         w_layout 0: w [cout][cin][3][3] (a contiguous torch weight)    1: w [cout][3][3][cin] (a channels_last one)
+ *     Neither u nor its circular halo is written to memory: the wrap is done in the operand addressing.  For h = 1 (w = 1) all
+ *     three kh (kw) read the row (column) itself, as F.pad(mode="circular") does.  Neither layout is copied on the torch
+ *     side; gradients of w come back in the layout given.  A GEMM with K = 9 cin over gathered rows on the fp32-input MFMA.
+ *     Grids depend on (batch, h, w, cin, cout) only, no floating-point atomics: bit-identical run to run.
+ *     Supported: cin, cout multiples of 8 in 8 .. 256, any batch, h, w >= 1 with m < 2^40; tensors 16-byte, the workspace 8-byte
+ *     aligned.
+ *     Errors, before any HIP call: null pointers, batch / h / w < 1, m >= 2^40, pre outside 0 .. 2, w_layout outside 0 .. 1,
+ *     misaligned pointers -> VQAE_ERR_INVALID; any other cin / cout -> VQAE_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------------- */
+int vqae_conv3x3_train_supported(int cin, int cout);
+/* R: the longest fp32 accumulation run of g_w, in rows.  Longer row ranges are added run by run in fp64. */
+int vqae_conv3x3_train_wgrad_run(void);
+/* Bytes of workspace (0 for an unsupported shape): the permuted weight of w_layout 0 and the flipped, transposed weight of the
+ * data gradient (9 cin cout floats each, together at most 4.5 MiB), P fp64 partials of g_w with P <= 256 and
+ * P 9 cin cout <= 2^22 (P = 1 above that: at most 32 MiB whatever m is), 1024 rows of the scalar sums: below 36.6 MiB. */
+size_t vqae_conv3x3_train_workspace_bytes(int64_t batch, int h, int w, int cin, int cout);
+/* workspace_dev may be NULL for w_layout 1 (the forward uses it for the permuted weight only). */
+int vqae_conv3x3_train_forward_f32(const float* x_dev, const float* a_dev, const float* b_dev, int pre, const float* w_dev,
+                                   int w_layout, int64_t batch, int h, int w, int cin, int cout, float* y_dev,
+                                   void* workspace_dev, void* stream);
+/* From g [batch][h][w][cout] and the forward's x, a, b, w:
+ *   g_u[b][i][j][ci] = sum_{kh,kw,co} g[b][(i - kh + 1) mod h][(j - kw + 1) mod w][co] w[co][ci][kh][kw], GATHERED (the same
+ *   circular 3x3 over g with the flipped, transposed weight, written to the workspace on every call), never scattered;
+ *   g_x [batch][h][w][cin] = g_u * ELU'(x + *a) for pre = 2, g_u otherwise, every element written once by a plain store;
+ *   *g_a = sum g_x (pre = 2);   *g_b = sum g_u (pre >= 1);
+ *   g_w (w's layout) = sum_m g[m][co] u[b][(i + kh - 1) mod h][(j + kw - 1) mod w][ci], u recomputed from x.
+ * g_x, g_w, g_a, g_b may each be NULL.  g_w: fp32 accumulation over runs of at most R rows, the runs added in fp64 in index
+ * order, rounded to fp32 once; the scalar sums in fp64 in a fixed order, rounded once. */
+int vqae_conv3x3_train_backward_f32(const float* g_dev, const float* x_dev, const float* a_dev, const float* b_dev, int pre,
+                                    const float* w_dev, int w_layout, int64_t batch, int h, int w, int cin, int cout,
+                                    float* g_x_dev, float* g_w_dev, float* g_a_dev, float* g_b_dev, void* workspace_dev,
+                                    void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * 7. Counts of stored code grids -- produces what the reference commits as data under scripts/create_wsi_histograms/
  *    (embedding_idx_histogram_{K}_{split}.npy, histogram_{split}.npy; it ships no program for them) and reads its loss
  *    weights from (conf/model/optional_overrides/loss_f/bce_with_logits_loss_camelyon16_embeddings.yaml: "values taken
