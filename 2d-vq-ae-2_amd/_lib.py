@@ -197,29 +197,6 @@ SYMBOLS = {
                                             c_void_p, c_void_p]),
     "vqae_bicubic_up2_bias_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "vqae_bicubic_up2_backward_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "vqae_conv1x1_train_supported": (c_int, [c_int, c_int]),
-    "vqae_conv1x1_train_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
-    "vqae_conv1x1_train_wgrad_run": (c_int, []),
-    "vqae_conv1x1_train_forward_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p,
-                                               c_void_p]),
-    "vqae_conv1x1_train_backward_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,
-                                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "vqae_conv_down_train_supported": (c_int, [c_int, c_int]),
-    "vqae_conv_down_train_wgrad_run": (c_int, []),
-    "vqae_conv_down_train_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int, c_int]),
-    "vqae_conv_down_train_forward_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int,
-                                                 c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "vqae_conv_down_train_backward_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64,
-                                                  c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                  c_void_p]),
-    "vqae_conv3x3_train_supported": (c_int, [c_int, c_int]),
-    "vqae_conv3x3_train_wgrad_run": (c_int, []),
-    "vqae_conv3x3_train_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int, c_int]),
-    "vqae_conv3x3_train_forward_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int,
-                                               c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "vqae_conv3x3_train_backward_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64,
-                                                c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                c_void_p]),
     "vqae_code_histogram_workspace_bytes": (c_size_t, [c_int, c_int64, c_int, c_int]),
     "vqae_code_histogram": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                     c_void_p, c_void_p]),
@@ -227,6 +204,22 @@ SYMBOLS = {
     "vqae_prof_begin": (c_int, [c_int, c_int]),
     "vqae_prof_end": (c_int, [POINTER(c_double), POINTER(c_int), POINTER(c_double)]),
 }
+
+# The trainable convs of csrc/conv_train.hip: node -> (ABI stem, kernel size, stride, image).  image: the node is called with
+# (batch, h, w), a weight layout and a forward workspace; without it, with its rows M as given and a [Co, Ci] weight.
+CONV_TRAIN = {"conv1x1": ("vqae_conv1x1_train", 1, 1, False), "conv_down": ("vqae_conv_down_train", 2, 2, True),
+              "conv3x3": ("vqae_conv3x3_train", 3, 1, True)}
+for _stem, _, _, _image in CONV_TRAIN.values():
+    _geo, _lay = ([c_int64, c_int, c_int], [c_int]) if _image else ([c_int64], [])
+    SYMBOLS.update({
+        _stem + "_supported": (c_int, [c_int, c_int]),
+        _stem + "_wgrad_run": (c_int, []),
+        _stem + "_workspace_bytes": (c_size_t, _geo + [c_int, c_int]),
+        # x a b pre w [w_layout] geometry cin cout y [ws] stream;  g x a b pre w [..] geometry cin cout g_x g_w g_a g_b ws stream
+        _stem + "_forward_f32": (c_int, [c_void_p] * 3 + [c_int, c_void_p] + _lay + _geo + [c_int, c_int]
+                                 + [c_void_p] * (3 if _image else 2)),
+        _stem + "_backward_f32": (c_int, [c_void_p] * 4 + [c_int, c_void_p] + _lay + _geo + [c_int, c_int] + [c_void_p] * 6),
+    })
 
 _lib = None
 

@@ -648,29 +648,9 @@ inline int forward(const float* x, const float* a, const float* b, int pre, cons
     return VQAE_OK;
 }
 
-// The workspace of the nodes with a weight of more than one tap: [wp][wt][slots][partials], 16-byte aligned.  wp: the weight
-// of w_layout 0 in the k-contiguous order (ct_permute_w);  wt: Circ3x3's flipped, transposed weight (ct_flip_w; no bytes for
-// Down2x2).
+// What a launch uses of the workspace (carve below).  wp: the weight of w_layout 0 in the k-contiguous order (ct_permute_w);
+// wt: Circ3x3's flipped, transposed weight (ct_flip_w).
 struct Workspace { float* wp; float* wt; double* slots; double* partials; };
-template <class Addr>
-inline size_t weight_bytes(int cin, int cout) { return (size_t)round_up((int64_t)Addr::TAPS * cin * cout * sizeof(float), 256); }
-template <class Addr>
-inline size_t workspace_bytes(int64_t m, int cin, int cout) {
-    return (Addr::GATHERS_GRAD ? 2 : 1) * weight_bytes<Addr>(cin, cout)
-           + slots_and_partials_bytes<Addr>(wgrad_plan<Addr>(m, cin, cout), cin, cout);
-}
-template <class Addr>
-inline Workspace carve(void* ws, const WgradPlan& plan, int cin, int cout) {
-    Workspace o;
-    char* p = (char*)(((uintptr_t)ws + 15) & ~(uintptr_t)15);
-    o.wp = (float*)p;
-    p += weight_bytes<Addr>(cin, cout);
-    o.wt = (float*)p;
-    if (Addr::GATHERS_GRAD) p += weight_bytes<Addr>(cin, cout);
-    o.slots = (double*)p;
-    o.partials = o.slots + (size_t)plan.P * Addr::TAPS * cin * cout;
-    return o;
-}
 
 // w is k-contiguous against the operand's rows unless w_layout == 0.  The scattering data gradient (Dense, Down2x2) then reads
 // ct_permute_w's copy in wk.wp; the gathering one (Circ3x3) reads ct_flip_w's wk.wt, made from either layout.
@@ -715,175 +695,174 @@ inline int backward(const float* g, const float* x, const float* a, const float*
     return VQAE_OK;
 }
 
-// b * per rows when b >= 1, per >= 1 and the product is below 2^40, else 0
-inline int64_t rows_below_2_40(int64_t b, int64_t per) {
-    if (b < 1 || per < 1 || per >= (1ll << 40) || b >= (1ll << 40) / per + 1) return 0;
-    const int64_t m = b * per;
-    return m < (1ll << 40) ? m : 0;
+// ---- host: the nodes ---------------------------------------------------------------------------------------------------------
+// What the C ABI states of a node, once: its policy, its name in messages, its stride (rows M = batch (h / STRIDE) (w / STRIDE);
+// h and w must be multiples of it), the Geo its kernels take, and whether it is called with an image (batch, h, w), a weight
+// layout and a forward workspace -- or, Dense, with M rows as given, its weight always k-contiguous.  WEIGHT_COPIES: the weights
+// (of round_up(TAPS Ci Co floats, 256) bytes each) in front of [slots][partials] in the workspace, wp then wt; with any, the
+// workspace starts at the next 16-byte boundary, with none at the pointer as given.
+struct Conv1x1 {
+    using Addr = Dense;
+    static constexpr const char* NAME = "conv1x1_train";
+    static constexpr int STRIDE = 1, WEIGHT_COPIES = 0;
+    static constexpr bool IMAGE = false;
+    static Geo geo(int, int) { return Geo{0, 0}; }
+};
+struct ConvDown {
+    using Addr = Down2x2;
+    static constexpr const char* NAME = "conv_down_train";
+    static constexpr int STRIDE = 2, WEIGHT_COPIES = 1;
+    static constexpr bool IMAGE = true;
+    static Geo geo(int, int w) { return Geo{0, w / 2}; }
+};
+struct Conv3x3 {
+    using Addr = Circ3x3;
+    static constexpr const char* NAME = "conv3x3_train";
+    static constexpr int STRIDE = 1, WEIGHT_COPIES = 2;
+    static constexpr bool IMAGE = true;
+    static Geo geo(int h, int w) { return Geo{h, w}; }
+};
+
+// rows M when the geometry is valid and M < 2^40, else 0
+template <class Node>
+inline int64_t rows(int64_t b, int h, int w) {
+    if (b < 1 || h < 1 || w < 1 || h % Node::STRIDE || w % Node::STRIDE) return 0;
+    const int64_t per = (int64_t)(h / Node::STRIDE) * (w / Node::STRIDE);              // >= 1, < 2^62
+    return per < (1ll << 40) && b <= (1ll << 40) / per && b * per < (1ll << 40) ? b * per : 0;
 }
 
-// Down2x2: rows M = b (h / 2) (w / 2) when the geometry is valid and M < 2^40, else 0
-inline int64_t down_rows(int64_t b, int h, int w) {
-    if (h < 2 || w < 2 || (h & 1) || (w & 1)) return 0;
-    return rows_below_2_40(b, (int64_t)(h / 2) * (w / 2));
+template <class Node>
+inline size_t weight_bytes(int cin, int cout) {
+    return (size_t)round_up((int64_t)Node::Addr::TAPS * cin * cout * sizeof(float), 256);
+}
+template <class Node>
+inline Workspace carve(void* ws, const WgradPlan& plan, int cin, int cout) {
+    char* p = (char*)ws;
+    if (Node::WEIGHT_COPIES) p = (char*)(((uintptr_t)ws + 15) & ~(uintptr_t)15);
+    Workspace o;
+    o.wp = (float*)p;
+    o.wt = Node::WEIGHT_COPIES > 1 ? (float*)(p + weight_bytes<Node>(cin, cout)) : nullptr;
+    o.slots = (double*)(p + Node::WEIGHT_COPIES * weight_bytes<Node>(cin, cout));
+    o.partials = o.slots + (size_t)plan.P * Node::Addr::TAPS * cin * cout;
+    return o;
 }
 
-// Circ3x3: rows M = b h w when b, h, w >= 1 and M < 2^40, else 0
-inline int64_t circ_rows(int64_t b, int h, int w) {
-    if (h < 1 || w < 1) return 0;
-    return rows_below_2_40(b, (int64_t)h * w);
+template <class Node>
+inline size_t entry_workspace_bytes(int64_t b, int h, int w, int cin, int cout) {
+    const int64_t m = Node::IMAGE ? rows<Node>(b, h, w) : b;                          // rows as given have a size past 2^40 too
+    if (m < 1 || !supported(cin, cout)) return 0;
+    return Node::WEIGHT_COPIES * weight_bytes<Node>(cin, cout)
+           + slots_and_partials_bytes<typename Node::Addr>(wgrad_plan<typename Node::Addr>(m, cin, cout), cin, cout);
+}
+
+// The checks both entries share, in the order that decides which code a call with two faults returns; *m: the rows.  A node
+// without an image passes its rows as batch, h = w = 1 and w_layout = 1.
+template <class Node>
+inline int entry_checks(const char* op, bool pointers, int pre, int w_layout, const float* a, const float* b, int64_t batch, int h,
+                        int wd, int cin, int cout, int64_t* m) {
+    *m = rows<Node>(batch, h, wd);
+    if (Node::IMAGE)
+        VQAE_REQUIRE(batch >= 1 && h >= 1 && wd >= 1, VQAE_ERR_INVALID, "%s_%s: batch %lld h %d w %d", Node::NAME, op,
+                     (long long)batch, h, wd);
+    else
+        VQAE_REQUIRE(*m >= 1, VQAE_ERR_INVALID, "%s_%s: %lld rows", Node::NAME, op, (long long)batch);
+    VQAE_REQUIRE(pre >= 0 && pre <= 2, VQAE_ERR_INVALID, "%s_%s: pre %d", Node::NAME, op, pre);
+    VQAE_REQUIRE(w_layout >= 0 && w_layout <= 1, VQAE_ERR_INVALID, "%s_%s: w_layout %d", Node::NAME, op, w_layout);
+    VQAE_REQUIRE(pointers && (pre < 1 || b) && (pre < 2 || a), VQAE_ERR_INVALID, "%s_%s: null pointer", Node::NAME, op);
+    VQAE_REQUIRE(supported(cin, cout), VQAE_ERR_UNSUPPORTED, "%s_%s: cin %d cout %d (multiples of 8, 8 .. %d)", Node::NAME, op, cin,
+                 cout, CT_MAXC);
+    VQAE_REQUIRE(h % Node::STRIDE == 0 && wd % Node::STRIDE == 0, VQAE_ERR_UNSUPPORTED, "%s_%s: h %d w %d must be even",
+                 Node::NAME, op, h, wd);
+    VQAE_REQUIRE(*m >= 1, VQAE_ERR_INVALID, "%s_%s: batch %lld x %d x %d %srows exceed 2^40", Node::NAME, op, (long long)batch,
+                 h / Node::STRIDE, wd / Node::STRIDE, Node::STRIDE > 1 ? "output " : "");
+    return VQAE_OK;
+}
+
+// the forward uses the workspace for w_layout 0 only
+template <class Node>
+inline int entry_forward(const float* x, const float* a, const float* b, int pre, const float* w, int w_layout, int64_t batch,
+                         int h, int wd, int cin, int cout, float* y, void* ws, void* stream_) {
+    using Addr = typename Node::Addr;
+    hipStream_t stream = (hipStream_t)stream_;
+    int64_t m;
+    if (const int e = entry_checks<Node>("forward", x && w && y && (ws || w_layout == 1), pre, w_layout, a, b, batch, h, wd, cin,
+                                         cout, &m))
+        return e;
+    VQAE_REQUIRE(aligned16({x, w, y}) && ((uintptr_t)ws & 7) == 0, VQAE_ERR_INVALID,
+                 Node::IMAGE ? "%s_forward: x, w and y must be 16-byte aligned, the workspace 8-byte aligned"
+                             : "%s_forward: x, w and y must be 16-byte aligned", Node::NAME);
+    if (w_layout == 0) {
+        const Workspace wk = carve<Node>(ws, wgrad_plan<Addr>(m, cin, cout), cin, cout);
+        const int n = Addr::TAPS * cin * cout;
+        ct_permute_w<<<blocks_for(n), CT_THREADS, 0, stream>>>(w, cin, Addr::TAPS, n, wk.wp);
+        VQAE_LAUNCH_CHECK();
+        w = wk.wp;
+    }
+    return forward<Addr>(x, a, b, pre, w, m, Node::geo(h, wd), cin, cout, y, stream);
+}
+
+template <class Node>
+inline int entry_backward(const float* g, const float* x, const float* a, const float* b, int pre, const float* w, int w_layout,
+                          int64_t batch, int h, int wd, int cin, int cout, float* g_x, float* g_w, float* g_a, float* g_b,
+                          void* ws, void* stream_) {
+    using Addr = typename Node::Addr;
+    int64_t m;
+    if (const int e = entry_checks<Node>("backward", g && x && w && ws, pre, w_layout, a, b, batch, h, wd, cin, cout, &m)) return e;
+    VQAE_REQUIRE(aligned16({g, x, w, g_x, g_w}) && ((uintptr_t)ws & 7) == 0, VQAE_ERR_INVALID,
+                 "%s_backward: tensors must be 16-byte aligned, the workspace 8-byte aligned", Node::NAME);
+    const WgradPlan plan = wgrad_plan<Addr>(m, cin, cout);
+    return backward<Addr>(g, x, a, b, pre, w, w_layout, carve<Node>(ws, plan, cin, cout), plan, m, Node::geo(h, wd), cin, cout, g_x,
+                          g_w, g_a, g_b, (hipStream_t)stream_);
 }
 
 }  // namespace
 
-// ---- the 1x1, stride-1 node ------------------------------------------------------------------------------------------------
+// ---- the C ABI ---------------------------------------------------------------------------------------------------------------
+// the 1x1, stride-1 node
 extern "C" int vqae_conv1x1_train_supported(int cin, int cout) { return supported(cin, cout) ? 1 : 0; }
-
 extern "C" int vqae_conv1x1_train_wgrad_run(void) { return CT_RUN; }
-
 extern "C" size_t vqae_conv1x1_train_workspace_bytes(int64_t m, int cin, int cout) {
-    if (m < 1 || !supported(cin, cout)) return 0;
-    return slots_and_partials_bytes<Dense>(wgrad_plan<Dense>(m, cin, cout), cin, cout);
+    return entry_workspace_bytes<Conv1x1>(m, 1, 1, cin, cout);
 }
-
 extern "C" int vqae_conv1x1_train_forward_f32(const float* x, const float* a, const float* b, int pre, const float* w, int64_t m,
-                                              int cin, int cout, float* y, void* stream_) {
-    VQAE_REQUIRE(m >= 1 && m < (1ll << 40), VQAE_ERR_INVALID, "conv1x1_train_forward: %lld rows", (long long)m);
-    VQAE_REQUIRE(pre >= 0 && pre <= 2, VQAE_ERR_INVALID, "conv1x1_train_forward: pre %d", pre);
-    VQAE_REQUIRE(x && w && y && (pre < 1 || b) && (pre < 2 || a), VQAE_ERR_INVALID, "conv1x1_train_forward: null pointer");
-    VQAE_REQUIRE(supported(cin, cout), VQAE_ERR_UNSUPPORTED,
-                 "conv1x1_train_forward: cin %d cout %d (multiples of 8, 8 .. %d)", cin, cout, CT_MAXC);
-    VQAE_REQUIRE(aligned16({x, w, y}), VQAE_ERR_INVALID, "conv1x1_train_forward: x, w and y must be 16-byte aligned");
-    return forward<Dense>(x, a, b, pre, w, m, Geo{0, 0}, cin, cout, y, (hipStream_t)stream_);
+                                              int cin, int cout, float* y, void* stream) {
+    return entry_forward<Conv1x1>(x, a, b, pre, w, 1, m, 1, 1, cin, cout, y, nullptr, stream);
 }
-
 extern "C" int vqae_conv1x1_train_backward_f32(const float* g, const float* x, const float* a, const float* b, int pre,
                                                const float* w, int64_t m, int cin, int cout, float* g_x, float* g_w, float* g_a,
-                                               float* g_b, void* ws, void* stream_) {
-    VQAE_REQUIRE(m >= 1 && m < (1ll << 40), VQAE_ERR_INVALID, "conv1x1_train_backward: %lld rows", (long long)m);
-    VQAE_REQUIRE(pre >= 0 && pre <= 2, VQAE_ERR_INVALID, "conv1x1_train_backward: pre %d", pre);
-    VQAE_REQUIRE(g && x && w && ws && (pre < 1 || b) && (pre < 2 || a), VQAE_ERR_INVALID, "conv1x1_train_backward: null pointer");
-    VQAE_REQUIRE(supported(cin, cout), VQAE_ERR_UNSUPPORTED,
-                 "conv1x1_train_backward: cin %d cout %d (multiples of 8, 8 .. %d)", cin, cout, CT_MAXC);
-    VQAE_REQUIRE(aligned16({g, x, w, g_x, g_w}) && ((uintptr_t)ws & 7) == 0, VQAE_ERR_INVALID,
-                 "conv1x1_train_backward: tensors must be 16-byte aligned, the workspace 8-byte aligned");
-    const WgradPlan plan = wgrad_plan<Dense>(m, cin, cout);
-    double* slots = (double*)ws;                                               // the workspace: [slots][partials]
-    const Workspace wk = {nullptr, nullptr, slots, slots + (size_t)plan.P * cin * cout};
-    return backward<Dense>(g, x, a, b, pre, w, 1, wk, plan, m, Geo{0, 0}, cin, cout, g_x, g_w, g_a, g_b, (hipStream_t)stream_);
+                                               float* g_b, void* ws, void* stream) {
+    return entry_backward<Conv1x1>(g, x, a, b, pre, w, 1, m, 1, 1, cin, cout, g_x, g_w, g_a, g_b, ws, stream);
 }
 
-// ---- the 2x2, stride-2 node ------------------------------------------------------------------------------------------------
+// the 2x2, stride-2 node
 extern "C" int vqae_conv_down_train_supported(int cin, int cout) { return supported(cin, cout) ? 1 : 0; }
-
 extern "C" int vqae_conv_down_train_wgrad_run(void) { return CT_RUN; }
-
 extern "C" size_t vqae_conv_down_train_workspace_bytes(int64_t b, int h, int w, int cin, int cout) {
-    const int64_t m = down_rows(b, h, w);
-    if (m < 1 || !supported(cin, cout)) return 0;
-    return workspace_bytes<Down2x2>(m, cin, cout);
+    return entry_workspace_bytes<ConvDown>(b, h, w, cin, cout);
 }
-
 extern "C" int vqae_conv_down_train_forward_f32(const float* x, const float* a, const float* b, int pre, const float* w,
                                                 int w_layout, int64_t batch, int h, int wd, int cin, int cout, float* y, void* ws,
-                                                void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    VQAE_REQUIRE(batch >= 1 && h >= 1 && wd >= 1, VQAE_ERR_INVALID, "conv_down_train_forward: batch %lld h %d w %d",
-                 (long long)batch, h, wd);
-    VQAE_REQUIRE(pre >= 0 && pre <= 2, VQAE_ERR_INVALID, "conv_down_train_forward: pre %d", pre);
-    VQAE_REQUIRE(w_layout >= 0 && w_layout <= 1, VQAE_ERR_INVALID, "conv_down_train_forward: w_layout %d", w_layout);
-    VQAE_REQUIRE(x && w && y && (ws || w_layout == 1) && (pre < 1 || b) && (pre < 2 || a), VQAE_ERR_INVALID,
-                 "conv_down_train_forward: null pointer");                 // the forward uses the workspace for w_layout 0 only
-    VQAE_REQUIRE(supported(cin, cout), VQAE_ERR_UNSUPPORTED,
-                 "conv_down_train_forward: cin %d cout %d (multiples of 8, 8 .. %d)", cin, cout, CT_MAXC);
-    VQAE_REQUIRE(h % 2 == 0 && wd % 2 == 0, VQAE_ERR_UNSUPPORTED, "conv_down_train_forward: h %d w %d must be even", h, wd);
-    const int64_t m = down_rows(batch, h, wd);
-    VQAE_REQUIRE(m >= 1, VQAE_ERR_INVALID, "conv_down_train_forward: batch %lld x %d x %d output rows exceed 2^40",
-                 (long long)batch, h / 2, wd / 2);
-    VQAE_REQUIRE(aligned16({x, w, y}) && ((uintptr_t)ws & 7) == 0, VQAE_ERR_INVALID,
-                 "conv_down_train_forward: x, w and y must be 16-byte aligned, the workspace 8-byte aligned");
-    const Workspace wk = carve<Down2x2>(ws, wgrad_plan<Down2x2>(m, cin, cout), cin, cout);
-    if (w_layout == 0) {
-        const int n = 4 * cin * cout;
-        ct_permute_w<<<blocks_for(n), CT_THREADS, 0, stream>>>(w, cin, 4, n, wk.wp);
-        VQAE_LAUNCH_CHECK();
-    }
-    return forward<Down2x2>(x, a, b, pre, w_layout == 0 ? wk.wp : w, m, Geo{0, wd / 2}, cin, cout, y, stream);
+                                                void* stream) {
+    return entry_forward<ConvDown>(x, a, b, pre, w, w_layout, batch, h, wd, cin, cout, y, ws, stream);
 }
-
 extern "C" int vqae_conv_down_train_backward_f32(const float* g, const float* x, const float* a, const float* b, int pre,
                                                  const float* w, int w_layout, int64_t batch, int h, int wd, int cin, int cout,
-                                                 float* g_x, float* g_w, float* g_a, float* g_b, void* ws, void* stream_) {
-    VQAE_REQUIRE(batch >= 1 && h >= 1 && wd >= 1, VQAE_ERR_INVALID, "conv_down_train_backward: batch %lld h %d w %d",
-                 (long long)batch, h, wd);
-    VQAE_REQUIRE(pre >= 0 && pre <= 2, VQAE_ERR_INVALID, "conv_down_train_backward: pre %d", pre);
-    VQAE_REQUIRE(w_layout >= 0 && w_layout <= 1, VQAE_ERR_INVALID, "conv_down_train_backward: w_layout %d", w_layout);
-    VQAE_REQUIRE(g && x && w && ws && (pre < 1 || b) && (pre < 2 || a), VQAE_ERR_INVALID, "conv_down_train_backward: null pointer");
-    VQAE_REQUIRE(supported(cin, cout), VQAE_ERR_UNSUPPORTED,
-                 "conv_down_train_backward: cin %d cout %d (multiples of 8, 8 .. %d)", cin, cout, CT_MAXC);
-    VQAE_REQUIRE(h % 2 == 0 && wd % 2 == 0, VQAE_ERR_UNSUPPORTED, "conv_down_train_backward: h %d w %d must be even", h, wd);
-    const int64_t m = down_rows(batch, h, wd);
-    VQAE_REQUIRE(m >= 1, VQAE_ERR_INVALID, "conv_down_train_backward: batch %lld x %d x %d output rows exceed 2^40",
-                 (long long)batch, h / 2, wd / 2);
-    VQAE_REQUIRE(aligned16({g, x, w, g_x, g_w}) && ((uintptr_t)ws & 7) == 0, VQAE_ERR_INVALID,
-                 "conv_down_train_backward: tensors must be 16-byte aligned, the workspace 8-byte aligned");
-    const WgradPlan plan = wgrad_plan<Down2x2>(m, cin, cout);
-    const Workspace wk = carve<Down2x2>(ws, plan, cin, cout);
-    return backward<Down2x2>(g, x, a, b, pre, w, w_layout, wk, plan, m, Geo{0, wd / 2}, cin, cout, g_x, g_w, g_a, g_b,
-                             (hipStream_t)stream_);
+                                                 float* g_x, float* g_w, float* g_a, float* g_b, void* ws, void* stream) {
+    return entry_backward<ConvDown>(g, x, a, b, pre, w, w_layout, batch, h, wd, cin, cout, g_x, g_w, g_a, g_b, ws, stream);
 }
 
-// ---- the circular 3x3, stride-1 node ----------------------------------------------------------------------------------------
+// the circular 3x3, stride-1 node
 extern "C" int vqae_conv3x3_train_supported(int cin, int cout) { return supported(cin, cout) ? 1 : 0; }
-
 extern "C" int vqae_conv3x3_train_wgrad_run(void) { return CT_RUN; }
-
 extern "C" size_t vqae_conv3x3_train_workspace_bytes(int64_t b, int h, int w, int cin, int cout) {
-    const int64_t m = circ_rows(b, h, w);
-    if (m < 1 || !supported(cin, cout)) return 0;
-    return workspace_bytes<Circ3x3>(m, cin, cout);
+    return entry_workspace_bytes<Conv3x3>(b, h, w, cin, cout);
 }
-
 extern "C" int vqae_conv3x3_train_forward_f32(const float* x, const float* a, const float* b, int pre, const float* w, int w_layout,
-                                              int64_t batch, int h, int wd, int cin, int cout, float* y, void* ws, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    VQAE_REQUIRE(batch >= 1 && h >= 1 && wd >= 1, VQAE_ERR_INVALID, "conv3x3_train_forward: batch %lld h %d w %d",
-                 (long long)batch, h, wd);
-    VQAE_REQUIRE(pre >= 0 && pre <= 2, VQAE_ERR_INVALID, "conv3x3_train_forward: pre %d", pre);
-    VQAE_REQUIRE(w_layout >= 0 && w_layout <= 1, VQAE_ERR_INVALID, "conv3x3_train_forward: w_layout %d", w_layout);
-    VQAE_REQUIRE(x && w && y && (ws || w_layout == 1) && (pre < 1 || b) && (pre < 2 || a), VQAE_ERR_INVALID,
-                 "conv3x3_train_forward: null pointer");                   // the forward uses the workspace for w_layout 0 only
-    VQAE_REQUIRE(supported(cin, cout), VQAE_ERR_UNSUPPORTED,
-                 "conv3x3_train_forward: cin %d cout %d (multiples of 8, 8 .. %d)", cin, cout, CT_MAXC);
-    const int64_t m = circ_rows(batch, h, wd);
-    VQAE_REQUIRE(m >= 1, VQAE_ERR_INVALID, "conv3x3_train_forward: batch %lld x %d x %d rows exceed 2^40", (long long)batch, h, wd);
-    VQAE_REQUIRE(aligned16({x, w, y}) && ((uintptr_t)ws & 7) == 0, VQAE_ERR_INVALID,
-                 "conv3x3_train_forward: x, w and y must be 16-byte aligned, the workspace 8-byte aligned");
-    const Workspace wk = carve<Circ3x3>(ws, wgrad_plan<Circ3x3>(m, cin, cout), cin, cout);
-    if (w_layout == 0) {
-        const int n = 9 * cin * cout;
-        ct_permute_w<<<blocks_for(n), CT_THREADS, 0, stream>>>(w, cin, 9, n, wk.wp);
-        VQAE_LAUNCH_CHECK();
-    }
-    return forward<Circ3x3>(x, a, b, pre, w_layout == 0 ? wk.wp : w, m, Geo{h, wd}, cin, cout, y, stream);
+                                              int64_t batch, int h, int wd, int cin, int cout, float* y, void* ws, void* stream) {
+    return entry_forward<Conv3x3>(x, a, b, pre, w, w_layout, batch, h, wd, cin, cout, y, ws, stream);
 }
-
 extern "C" int vqae_conv3x3_train_backward_f32(const float* g, const float* x, const float* a, const float* b, int pre,
                                                const float* w, int w_layout, int64_t batch, int h, int wd, int cin, int cout,
-                                               float* g_x, float* g_w, float* g_a, float* g_b, void* ws, void* stream_) {
-    VQAE_REQUIRE(batch >= 1 && h >= 1 && wd >= 1, VQAE_ERR_INVALID, "conv3x3_train_backward: batch %lld h %d w %d",
-                 (long long)batch, h, wd);
-    VQAE_REQUIRE(pre >= 0 && pre <= 2, VQAE_ERR_INVALID, "conv3x3_train_backward: pre %d", pre);
-    VQAE_REQUIRE(w_layout >= 0 && w_layout <= 1, VQAE_ERR_INVALID, "conv3x3_train_backward: w_layout %d", w_layout);
-    VQAE_REQUIRE(g && x && w && ws && (pre < 1 || b) && (pre < 2 || a), VQAE_ERR_INVALID, "conv3x3_train_backward: null pointer");
-    VQAE_REQUIRE(supported(cin, cout), VQAE_ERR_UNSUPPORTED,
-                 "conv3x3_train_backward: cin %d cout %d (multiples of 8, 8 .. %d)", cin, cout, CT_MAXC);
-    const int64_t m = circ_rows(batch, h, wd);
-    VQAE_REQUIRE(m >= 1, VQAE_ERR_INVALID, "conv3x3_train_backward: batch %lld x %d x %d rows exceed 2^40", (long long)batch, h, wd);
-    VQAE_REQUIRE(aligned16({g, x, w, g_x, g_w}) && ((uintptr_t)ws & 7) == 0, VQAE_ERR_INVALID,
-                 "conv3x3_train_backward: tensors must be 16-byte aligned, the workspace 8-byte aligned");
-    const WgradPlan plan = wgrad_plan<Circ3x3>(m, cin, cout);
-    const Workspace wk = carve<Circ3x3>(ws, plan, cin, cout);
-    return backward<Circ3x3>(g, x, a, b, pre, w, w_layout, wk, plan, m, Geo{h, wd}, cin, cout, g_x, g_w, g_a, g_b,
-                             (hipStream_t)stream_);
+                                               float* g_x, float* g_w, float* g_a, float* g_b, void* ws, void* stream) {
+    return entry_backward<Conv3x3>(g, x, a, b, pre, w, w_layout, batch, h, wd, cin, cout, g_x, g_w, g_a, g_b, ws, stream);
 }

@@ -17,12 +17,7 @@ from .conv_block import PreActFixupResBlock as _InferenceBlock
 class PreActFixupResBlock(_InferenceBlock):
     def __init__(self, *args, conv1x1: str = "torch", conv_down: str = "torch", conv3x3: str = "torch", **kwargs):
         super().__init__(*args, **kwargs)
-        if conv1x1 not in train.CONV1X1_ROUTES:
-            raise ValueError(f"conv1x1 must be one of {train.CONV1X1_ROUTES}, not {conv1x1!r}")
-        if conv_down not in train.CONV_DOWN_ROUTES:
-            raise ValueError(f"conv_down must be one of {train.CONV_DOWN_ROUTES}, not {conv_down!r}")
-        if conv3x3 not in train.CONV3X3_ROUTES:
-            raise ValueError(f"conv3x3 must be one of {train.CONV3X3_ROUTES}, not {conv3x3!r}")
+        train.conv_routes(conv1x1=conv1x1, conv_down=conv_down, conv3x3=conv3x3)
         self.conv1x1, self.conv_down, self.conv3x3 = conv1x1, conv_down, conv3x3
 
     def forward(self, inp: torch.Tensor):

@@ -1,6 +1,8 @@
 """Functional wrappers over the C ABI for torch tensors living in HBM (plumbing only: pointers,
 shapes, the current HIP stream).  Activations are NHWC fp32 unless a name says otherwise."""
 import ctypes
+import functools
+import types
 
 import torch
 
@@ -280,6 +282,70 @@ def bicubic_up2_backward(g, want_bias=True):
     return g_x, g_pb
 
 
+@functools.lru_cache(maxsize=None)
+def _conv_train_node(node):
+    """L.CONV_TRAIN[node] with its entries resolved, once."""
+    stem, k, stride, image = L.CONV_TRAIN[node]
+    fns = {fn: getattr(L.lib(), f"{stem}_{fn}") for fn in ("workspace_bytes", "forward_f32", "backward_f32")}
+    return types.SimpleNamespace(kernel=(k, k), stride=stride, image=image, **fns)
+
+
+def _conv_train_args(nd, x, w, a, b):
+    """-> (w as the library reads it, the arguments between w and cin, cin, cout, y's shape, pre) for a node nd.
+    With an image: a channels_last [Co, Ci, kh, kw] weight is [Co][kh][kw][Ci] in memory and is passed as it lies (w_layout 1);
+    anything else is made contiguous (w_layout 0).  No copy for either of the two ways torch stores a dense fp32 weight.
+    Without: x [..., Ci], the weight always contiguous, no w_layout."""
+    w = w.detach().float()
+    cout, cin = w.shape[0], w.shape[1]
+    if nd.image:
+        assert x.dim() == 4 and tuple(w.shape[2:]) == nd.kernel and x.shape[-1] == cin, (x.shape, w.shape)
+        B, H, W, _ = x.shape
+        layout = int(w.is_contiguous(memory_format=torch.channels_last) and not w.is_contiguous())
+        geo, y_shape = (layout, B, H, W), (B, H // nd.stride, W // nd.stride, cout)
+    else:
+        assert w.numel() == cout * cin and x.shape[-1] == cin, (x.shape, w.shape)
+        layout, geo, y_shape = 0, (x.numel() // cin,), x.shape[:-1] + (cout,)
+    assert a is None or b is not None, "pre-op: none (a, b None), x + b (a None), ELU(x + a) + b"
+    return (w if layout else w.contiguous()), geo, cin, cout, y_shape, (0 if b is None else 1 if a is None else 2)
+
+
+def _conv_train_ws(nd, geo, cin, cout, dev):
+    return torch.empty(nd.workspace_bytes(*geo[-3:], cin, cout), dtype=torch.uint8, device=dev)         # geo without the layout
+
+
+def _conv_train_forward(node, x, w, a, b):
+    _need_gpu(x, w)
+    x = x.contiguous()
+    nd = _conv_train_node(node)
+    wc, geo, cin, cout, y_shape, pre = _conv_train_args(nd, x, w, a, b)
+    y = torch.empty(y_shape, dtype=torch.float32, device=x.device)
+    ws = _conv_train_ws(nd, geo, cin, cout, x.device) if nd.image and geo[0] == 0 else None           # layout 0 alone needs one
+    L.check(nd.forward_f32(_p(x), _p(_scalar(a)), _p(_scalar(b)), pre, _p(wc), *geo, cin, cout, _p(y),
+                           *([_p(ws)] if nd.image else []), _stream()))
+    return y
+
+
+def _conv_train_backward(node, g, x, w, a, b, need_x, need_w):
+    _need_gpu(g, x, w)
+    g, x = g.contiguous(), x.contiguous()
+    nd = _conv_train_node(node)
+    wc, geo, cin, cout, y_shape, pre = _conv_train_args(nd, x, w, a, b)
+    if nd.image:
+        assert tuple(g.shape) == y_shape, (g.shape, x.shape, w.shape)
+    else:
+        assert g.shape[-1] == cout and g.numel() == geo[0] * cout, (g.shape, x.shape, w.shape)
+    dev = g.device
+    g_x = torch.empty_like(x) if need_x else None
+    # dense: the same strides, i.e. the same layout;  without an image: contiguous in w's shape
+    g_w = (torch.empty_like(wc) if nd.image else torch.empty(w.shape, dtype=torch.float32, device=dev)) if need_w else None
+    g_a = torch.empty(1, dtype=torch.float32, device=dev) if pre == 2 else None
+    g_b = torch.empty(1, dtype=torch.float32, device=dev) if pre >= 1 else None
+    ws = _conv_train_ws(nd, geo, cin, cout, dev)
+    L.check(nd.backward_f32(_p(g), _p(x), _p(_scalar(a)), _p(_scalar(b)), pre, _p(wc), *geo, cin, cout, _p(g_x), _p(g_w), _p(g_a),
+                            _p(g_b), _p(ws), _stream()))
+    return g_x, g_w, g_a, g_b
+
+
 def conv1x1_train_supported(cin, cout):
     """Whether the trainable 1x1 conv kernels take (cin, cout).  A host-side question: needs no GPU."""
     return bool(L.lib().vqae_conv1x1_train_supported(int(cin), int(cout)))
@@ -290,44 +356,17 @@ def conv1x1_train_wgrad_run():
     return int(L.lib().vqae_conv1x1_train_wgrad_run())
 
 
-def _conv1x1_args(x, w, a, b):
-    w = w.detach().float().contiguous()
-    cout, cin = w.shape[0], w.shape[1]
-    assert w.numel() == cout * cin and x.shape[-1] == cin, (x.shape, w.shape)
-    assert a is None or b is not None, "pre-op: none (a, b None), x + b (a None), ELU(x + a) + b"
-    return w, cin, cout, (0 if b is None else 1 if a is None else 2)
-
-
 def conv1x1_train_forward(x, w, a=None, b=None):
     """y [..., Co] = u [..., Ci] . w^T, w [Co, Ci(, 1, 1)] as torch stores it; u = x (a, b None), x + b (a None) or
     ELU(x + a) + b, with a, b one-element device tensors.  u is not materialised."""
-    _need_gpu(x, w)
-    x = x.contiguous()
-    w, cin, cout, pre = _conv1x1_args(x, w, a, b)
-    y = torch.empty(x.shape[:-1] + (cout,), dtype=torch.float32, device=x.device)
-    L.check(L.lib().vqae_conv1x1_train_forward_f32(_p(x), _p(_scalar(a)), _p(_scalar(b)), pre, _p(w), x.numel() // cin, cin,
-                                                   cout, _p(y), _stream()))
-    return y
+    return _conv_train_forward("conv1x1", x, w, a, b)
 
 
 def conv1x1_train_backward(g, x, w, a=None, b=None, need_x=True, need_w=True):
     """-> (g_x [..., Ci] | None, g_w (w's shape) | None, g_a [1] | None, g_b [1] | None) from g [..., Co] and the forward's
     x, w, a, b: g_u = g . w, g_x = g_u * ELU'(x + a) (g_u without an activation), g_a = sum g_x, g_b = sum g_u,
     g_w = g^T . u with u recomputed from x."""
-    _need_gpu(g, x, w)
-    g, x = g.contiguous(), x.contiguous()
-    wc, cin, cout, pre = _conv1x1_args(x, w, a, b)
-    m = x.numel() // cin
-    assert g.shape[-1] == cout and g.numel() == m * cout, (g.shape, x.shape, w.shape)
-    dev = g.device
-    g_x = torch.empty_like(x) if need_x else None
-    g_w = torch.empty(w.shape, dtype=torch.float32, device=dev) if need_w else None
-    g_a = torch.empty(1, dtype=torch.float32, device=dev) if pre == 2 else None
-    g_b = torch.empty(1, dtype=torch.float32, device=dev) if pre >= 1 else None
-    ws = torch.empty(L.lib().vqae_conv1x1_train_workspace_bytes(m, cin, cout), dtype=torch.uint8, device=dev)
-    L.check(L.lib().vqae_conv1x1_train_backward_f32(_p(g), _p(x), _p(_scalar(a)), _p(_scalar(b)), pre, _p(wc), m, cin, cout,
-                                                    _p(g_x), _p(g_w), _p(g_a), _p(g_b), _p(ws), _stream()))
-    return g_x, g_w, g_a, g_b
+    return _conv_train_backward("conv1x1", g, x, w, a, b, need_x, need_w)
 
 
 def conv_down_train_supported(cin, cout):
@@ -340,59 +379,18 @@ def conv_down_train_wgrad_run():
     return int(L.lib().vqae_conv_down_train_wgrad_run())
 
 
-def _conv_down_args(x, w, a, b, kernel=(2, 2)):
-    """-> (w as the library reads it, w_layout, cin, cout, pre).  A channels_last [Co, Ci, kh, kw] weight is [Co][kh][kw][Ci] in
-    memory and is passed as it lies (w_layout 1); anything else is made contiguous (w_layout 0).  No copy for either of the
-    two ways torch stores a dense fp32 weight."""
-    w = w.detach().float()
-    cout, cin = w.shape[0], w.shape[1]
-    assert x.dim() == 4 and tuple(w.shape[2:]) == kernel and x.shape[-1] == cin, (x.shape, w.shape)
-    assert a is None or b is not None, "pre-op: none (a, b None), x + b (a None), ELU(x + a) + b"
-    if w.is_contiguous(memory_format=torch.channels_last) and not w.is_contiguous():
-        layout = 1
-    else:
-        w, layout = w.contiguous(), 0
-    return w, layout, cin, cout, (0 if b is None else 1 if a is None else 2)
-
-
-def _conv_down_ws(x, cin, cout):
-    B, H, W, _ = x.shape
-    return torch.empty(L.lib().vqae_conv_down_train_workspace_bytes(B, H, W, cin, cout), dtype=torch.uint8, device=x.device)
-
-
 def conv_down_train_forward(x, w, a=None, b=None):
     """y [B, H/2, W/2, Co] = the 2x2, stride-2 conv of u [B, H, W, Ci] with w [Co, Ci, 2, 2] (contiguous or channels_last, read
     in place); u = x (a, b None), x + b (a None) or ELU(x + a) + b, with a, b one-element device tensors.  u is not
     materialised."""
-    _need_gpu(x, w)
-    x = x.contiguous()
-    wc, layout, cin, cout, pre = _conv_down_args(x, w, a, b)
-    B, H, W, _ = x.shape
-    y = torch.empty((B, H // 2, W // 2, cout), dtype=torch.float32, device=x.device)
-    ws = _conv_down_ws(x, cin, cout) if layout == 0 else None
-    L.check(L.lib().vqae_conv_down_train_forward_f32(_p(x), _p(_scalar(a)), _p(_scalar(b)), pre, _p(wc), layout, B, H, W, cin,
-                                                     cout, _p(y), _p(ws), _stream()))
-    return y
+    return _conv_train_forward("conv_down", x, w, a, b)
 
 
 def conv_down_train_backward(g, x, w, a=None, b=None, need_x=True, need_w=True):
     """-> (g_x [B, H, W, Ci] | None, g_w (w's shape and memory format) | None, g_a [1] | None, g_b [1] | None) from
     g [B, H/2, W/2, Co] and the forward's x, w, a, b: g_u = the data gradient, g_x = g_u * ELU'(x + a) (g_u without an
     activation), g_a = sum g_x, g_b = sum g_u, g_w = the weight gradient with u recomputed from x."""
-    _need_gpu(g, x, w)
-    g, x = g.contiguous(), x.contiguous()
-    wc, layout, cin, cout, pre = _conv_down_args(x, w, a, b)
-    B, H, W, _ = x.shape
-    assert tuple(g.shape) == (B, H // 2, W // 2, cout), (g.shape, x.shape, w.shape)
-    dev = g.device
-    g_x = torch.empty_like(x) if need_x else None
-    g_w = torch.empty_like(wc) if need_w else None              # dense: the same strides, i.e. the same layout
-    g_a = torch.empty(1, dtype=torch.float32, device=dev) if pre == 2 else None
-    g_b = torch.empty(1, dtype=torch.float32, device=dev) if pre >= 1 else None
-    ws = _conv_down_ws(x, cin, cout)
-    L.check(L.lib().vqae_conv_down_train_backward_f32(_p(g), _p(x), _p(_scalar(a)), _p(_scalar(b)), pre, _p(wc), layout, B, H, W,
-                                                      cin, cout, _p(g_x), _p(g_w), _p(g_a), _p(g_b), _p(ws), _stream()))
-    return g_x, g_w, g_a, g_b
+    return _conv_train_backward("conv_down", g, x, w, a, b, need_x, need_w)
 
 
 def conv3x3_train_supported(cin, cout):
@@ -405,24 +403,11 @@ def conv3x3_train_wgrad_run():
     return int(L.lib().vqae_conv3x3_train_wgrad_run())
 
 
-def _conv3x3_ws(x, cin, cout):
-    B, H, W, _ = x.shape
-    return torch.empty(L.lib().vqae_conv3x3_train_workspace_bytes(B, H, W, cin, cout), dtype=torch.uint8, device=x.device)
-
-
 def conv3x3_train_forward(x, w, a=None, b=None):
     """y [B, H, W, Co] = the 3x3, stride-1 conv with circular padding 1 of u [B, H, W, Ci] with w [Co, Ci, 3, 3] (contiguous or
     channels_last, read in place); u = x (a, b None), x + b (a None) or ELU(x + a) + b, with a, b one-element device tensors.
     Neither u nor its halo is materialised."""
-    _need_gpu(x, w)
-    x = x.contiguous()
-    wc, layout, cin, cout, pre = _conv_down_args(x, w, a, b, kernel=(3, 3))
-    B, H, W, _ = x.shape
-    y = torch.empty((B, H, W, cout), dtype=torch.float32, device=x.device)
-    ws = _conv3x3_ws(x, cin, cout) if layout == 0 else None
-    L.check(L.lib().vqae_conv3x3_train_forward_f32(_p(x), _p(_scalar(a)), _p(_scalar(b)), pre, _p(wc), layout, B, H, W, cin,
-                                                   cout, _p(y), _p(ws), _stream()))
-    return y
+    return _conv_train_forward("conv3x3", x, w, a, b)
 
 
 def conv3x3_train_backward(g, x, w, a=None, b=None, need_x=True, need_w=True):
@@ -430,20 +415,7 @@ def conv3x3_train_backward(g, x, w, a=None, b=None, need_x=True, need_w=True):
     g [B, H, W, Co] and the forward's x, w, a, b: g_u = the data gradient (gathered: the circular 3x3 of g with the flipped,
     transposed weight), g_x = g_u * ELU'(x + a) (g_u without an activation), g_a = sum g_x, g_b = sum g_u, g_w = the weight
     gradient with u recomputed from x."""
-    _need_gpu(g, x, w)
-    g, x = g.contiguous(), x.contiguous()
-    wc, layout, cin, cout, pre = _conv_down_args(x, w, a, b, kernel=(3, 3))
-    B, H, W, _ = x.shape
-    assert tuple(g.shape) == (B, H, W, cout), (g.shape, x.shape, w.shape)
-    dev = g.device
-    g_x = torch.empty_like(x) if need_x else None
-    g_w = torch.empty_like(wc) if need_w else None              # dense: the same strides, i.e. the same layout
-    g_a = torch.empty(1, dtype=torch.float32, device=dev) if pre == 2 else None
-    g_b = torch.empty(1, dtype=torch.float32, device=dev) if pre >= 1 else None
-    ws = _conv3x3_ws(x, cin, cout)
-    L.check(L.lib().vqae_conv3x3_train_backward_f32(_p(g), _p(x), _p(_scalar(a)), _p(_scalar(b)), pre, _p(wc), layout, B, H, W,
-                                                    cin, cout, _p(g_x), _p(g_w), _p(g_a), _p(g_b), _p(ws), _stream()))
-    return g_x, g_w, g_a, g_b
+    return _conv_train_backward("conv3x3", g, x, w, a, b, need_x, need_w)
 
 
 def vq_forward(z_flat, embed, commitment_cost=1.0, idx_dtype=torch.int64, want_q=True, want_margin=False, p=4):

@@ -65,9 +65,8 @@ from .layers.vq import ProjectedEMAVectorQuantizer2d
 
 stats = {"layout_checks": 0, "layout_copies": 0, "conv1x1_hip": 0, "conv1x1_fallbacks": 0, "conv_down_hip": 0,
          "conv_down_fallbacks": 0, "conv3x3_hip": 0, "conv3x3_fallbacks": 0}
-CONV1X1_ROUTES = ("torch", "hip")
-CONV_DOWN_ROUTES = ("torch", "hip")
-CONV3X3_ROUTES = ("torch", "hip")
+ROUTES = ("torch", "hip")                                     # of each of the keywords conv1x1, conv_down, conv3x3
+CONV1X1_ROUTES = CONV_DOWN_ROUTES = CONV3X3_ROUTES = ROUTES
 
 _W75 = (-0.03515625, 0.26171875, 0.87890625, -0.10546875)     # even outputs: inputs m-2 .. m+1, m = o >> 1
 _W25 = (-0.10546875, 0.87890625, 0.26171875, -0.03515625)     # odd outputs:  inputs m-1 .. m+2
@@ -253,12 +252,15 @@ def _pre_op_torch(x, a, b):
 class _PreConvFn(torch.autograd.Function):
     """The ctx plumbing of a conv node with the op in front of it folded in: u = x (a, b None), x + b (a None) or
     ELU(x + a) + b.  Saves x, w and whichever of a, b exist -- not u: the backward recomputes it for g_w and takes ELU' from
-    x + a.  A node states _forward(x, w, a, b) -> y and _backward(g, x, w, a, b, need_x, need_w) -> (g_x, g_w, g_a, g_b)."""
+    x + a.  On the device it is ops.<NODE>_train_forward / _backward; a node names itself and states its restatement for CPU
+    tensors, _forward(x, w, a, b) -> y and _backward(g, x, w, a, b, need_x, need_w) -> (g_x, g_w, g_a, g_b)."""
 
     @classmethod
     def forward(cls, ctx, x, w, a, b):
         ctx.save_for_backward(x, w, *(t for t in (a, b) if t is not None))
         ctx.has = (a is not None, b is not None)
+        if x.is_cuda:
+            return getattr(ops, cls.NODE + "_train_forward")(x.float(), w, a, b)
         return cls._forward(x, w, a, b)
 
     @classmethod
@@ -268,24 +270,25 @@ class _PreConvFn(torch.autograd.Function):
         a = ab[0] if ctx.has[0] else None
         b = ab[-1] if ctx.has[1] else None
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        g_x, g_w, g_a, g_b = cls._backward(g, x, w, a, b, need_x, need_w)
+        if g.is_cuda:
+            g, x, backward = _dense(g.float()), x.float(), getattr(ops, cls.NODE + "_train_backward")
+        else:
+            backward = cls._backward
+        g_x, g_w, g_a, g_b = backward(g, x, w, a, b, need_x, need_w)
         return (g_x if need_x else None, g_w.to(w.dtype) if need_w else None, _like(g_a, a) if a is not None else None,
                 _like(g_b, b) if b is not None else None)
 
 
 class _Conv1x1Fn(_PreConvFn):
     """y = u . w^T on [B, H, W, Ci], w [Co, Ci, 1, 1]."""
+    NODE = "conv1x1"
 
     @staticmethod
     def _forward(x, w, a, b):
-        if x.is_cuda:
-            return ops.conv1x1_train_forward(x.float(), w, a, b)
         return to_nhwc(F.conv2d(to_nchw(_pre_op_torch(x, a, b)), w))
 
     @staticmethod
     def _backward(g, x, w, a, b, need_x, need_w):
-        if g.is_cuda:
-            return ops.conv1x1_train_backward(_dense(g.float()), x.float(), w, a, b, need_x, need_w)
         w2 = w.reshape(w.shape[0], w.shape[1])
         g_u = g @ w2
         g_x = g_u * elu_grad(x + a) if a is not None else g_u
@@ -319,17 +322,14 @@ class _ConvDownFn(_PreConvFn):
     """y [B, H/2, W/2, Co] = the 2x2, stride-2 conv (no padding, no bias) of u [B, H, W, Ci] with w [Co, Ci, 2, 2].  The four
     taps do not overlap, so the backward is two matmuls on the space-to-depth form: g_u = depth_to_space(g . w2),
     g_w = g^T . space_to_depth(u), w2 [Co, (kh, kw, ci)]."""
+    NODE = "conv_down"
 
     @staticmethod
     def _forward(x, w, a, b):
-        if x.is_cuda:
-            return ops.conv_down_train_forward(x.float(), w, a, b)
         return to_nhwc(F.conv2d(to_nchw(_pre_op_torch(x, a, b)), w, stride=2))
 
     @staticmethod
     def _backward(g, x, w, a, b, need_x, need_w):
-        if g.is_cuda:
-            return ops.conv_down_train_backward(_dense(g.float()), x.float(), w, a, b, need_x, need_w)
         B, OH, OW, Co = g.shape
         g2 = g.reshape(-1, Co)
         g_u = _depth_to_space(g2 @ w.permute(0, 2, 3, 1).reshape(Co, -1), B, OH, OW)
@@ -354,17 +354,14 @@ class _Conv3x3Fn(_PreConvFn):
     """y [B, H, W, Co] = the 3x3, stride-1 conv with circular padding 1 (no bias) of u [B, H, W, Ci] with w [Co, Ci, 3, 3].  The
     taps overlap: the data gradient is the fold of the padded one (the adjoint of the wrap), g_w a matmul on the unfolded
     patches of the padded u."""
+    NODE = "conv3x3"
 
     @staticmethod
     def _forward(x, w, a, b):
-        if x.is_cuda:
-            return ops.conv3x3_train_forward(x.float(), w, a, b)
         return to_nhwc(F.conv2d(to_nchw(pad_circular_nhwc(_pre_op_torch(x, a, b))), w))
 
     @staticmethod
     def _backward(g, x, w, a, b, need_x, need_w):
-        if g.is_cuda:
-            return ops.conv3x3_train_backward(_dense(g.float()), x.float(), w, a, b, need_x, need_w)
         Co = g.shape[-1]
         # the padded data gradient [B, H + 2, W + 2, Ci]: pixel (p, q) collects g[p - kh][q - kw] . w[:, :, kh, kw]
         g_u = fold_circular_nhwc(F.conv_transpose2d(to_nchw(g), w).permute(0, 2, 3, 1))
@@ -408,77 +405,69 @@ def _conv(t, w, bias=None, stride=1, padding=0):
     return to_nhwc(F.conv2d(to_nchw(t), w, bias, stride=stride, padding=padding))
 
 
-def _route(keyword, value, routes):
-    if value not in routes:
-        raise ValueError(f"{keyword} must be one of {routes}, not {value!r}")
-    return value == "hip"
+def conv_routes(conv1x1="torch", conv_down="torch", conv3x3="torch"):
+    """The three route keywords, checked -> {node: whether its convs are the fused nodes of csrc/conv_train.hip}."""
+    routes = dict(conv1x1=conv1x1, conv_down=conv_down, conv3x3=conv3x3)
+    for keyword, value in routes.items():
+        if value not in ROUTES:
+            raise ValueError(f"{keyword} must be one of {ROUTES}, not {value!r}")
+    return {node: value == "hip" for node, value in routes.items()}
 
 
-def _pre_conv1x1(hip, x, a, b, w):
-    """The 1x1, stride-1 conv of ELU(x + a) + b (a None: x + b; both None: x).  hip: one fused node where the kernels take the
-    shape; any other shape takes the torch route and is counted."""
-    if hip:
-        if tuple(w.shape[2:]) == (1, 1) and ops.conv1x1_train_supported(w.shape[1], w.shape[0]):
-            stats["conv1x1_hip"] += 1
-            return conv1x1(x, w, a, b)
-        stats["conv1x1_fallbacks"] += 1
-    if b is not None:
-        x = fixup_add(x, b) if a is None else fixup_act(x, a, b)
-    return _conv(x, w)
+def _pre_torch(x, a, b):
+    if b is None:
+        return x
+    return fixup_add(x, b) if a is None else fixup_act(x, a, b)
 
 
-def _pre_conv_down(hip, x, a, b, w):
-    """The 2x2, stride-2 conv of ELU(x + a) + b (a None: x + b).  hip: one fused node where the kernels take the shape (even
-    H and W, their channel rule); any other shape takes the torch route and is counted."""
-    if hip:
-        if (tuple(w.shape[2:]) == (2, 2) and x.shape[1] % 2 == 0 and x.shape[2] % 2 == 0
-                and ops.conv_down_train_supported(w.shape[1], w.shape[0])):
-            stats["conv_down_hip"] += 1
-            return conv_down(x, w, a, b)
-        stats["conv_down_fallbacks"] += 1
-    x = fixup_add(x, b) if a is None else fixup_act(x, a, b)
-    return _conv(x, w, stride=2)
+# node -> (the fused node, the torch route).  conv3x3's: the activation writes the wrap, the conv pads nothing.
+_NODES = {"conv1x1": (conv1x1, lambda x, a, b, w: _conv(_pre_torch(x, a, b), w)),
+          "conv_down": (conv_down, lambda x, a, b, w: _conv(_pre_torch(x, a, b), w, stride=2)),
+          "conv3x3": (conv3x3, lambda x, a, b, w: _conv(fixup_act(x, a, b, halo=1), w))}
 
 
-def _pre_conv3x3(hip, x, a, b, w):
-    """The circular 3x3 conv of ELU(x + a) + b.  hip: one fused node where the kernels take the channel counts; any other
-    shape takes the torch route -- the activation writes the wrap, the conv pads nothing -- and is counted."""
-    if hip:
-        if tuple(w.shape[2:]) == (3, 3) and ops.conv3x3_train_supported(w.shape[1], w.shape[0]):
-            stats["conv3x3_hip"] += 1
-            return conv3x3(x, w, a, b)
-        stats["conv3x3_fallbacks"] += 1
-    return _conv(fixup_act(x, a, b, halo=1), w)
+def _pre_conv(node, hip, x, a, b, w):
+    """The conv of a node of ops.L.CONV_TRAIN on ELU(x + a) + b (a None: x + b; both None: x).  hip[node]: one fused node where
+    the kernels take the shape (the node's kernel size, H and W multiples of its stride, their channel rule); any other
+    shape takes the torch route and is counted."""
+    fused, torch_route = _NODES[node]
+    if hip[node]:
+        _, k, stride, _ = ops.L.CONV_TRAIN[node]
+        if (tuple(w.shape[2:]) == (k, k) and x.shape[1] % stride == 0 and x.shape[2] % stride == 0
+                and getattr(ops, node + "_train_supported")(w.shape[1], w.shape[0])):
+            stats[node + "_hip"] += 1
+            return fused(x, w, a, b)
+        stats[node + "_fallbacks"] += 1
+    return torch_route(x, a, b, w)
 
 
-def block_forward_nhwc(block, x, conv1x1="torch", conv_down="torch", conv3x3="torch"):
-    """conv_block.py:196-216 on [B, H, W, C] with a graph: the fused ops around F.conv2d.  conv1x1 = "hip": every 1x1, stride-1
-    conv the kernels support is one node with the op in front of it (csrc/conv_train.hip); conv_down = "hip": so is each
-    2x2, stride-2 conv of a 'down' block; conv3x3 = "hip": so is the circular 3x3 of a 'same' or 'out' block; "torch":
-    F.conv2d."""
+def block_forward_nhwc(block, x, **routes):
+    """conv_block.py:196-216 on [B, H, W, C] with a graph: the fused ops around F.conv2d.  routes: the keywords of conv_routes,
+    each "torch" by default.  conv1x1 = "hip": every 1x1, stride-1 conv the kernels support is one node with the op in front
+    of it (csrc/conv_train.hip); conv_down = "hip": so is each 2x2, stride-2 conv of a 'down' block; conv3x3 = "hip": so is
+    the circular 3x3 of a 'same' or 'out' block; "torch": F.conv2d."""
     if not isinstance(block, PreActFixupResBlock):
         raise NotImplementedError(f"training is implemented for Fixup blocks only (no MBConv / BatchNorm training), not "
                                   f"{type(block).__name__}")
-    hip, down = _route("conv1x1", conv1x1, CONV1X1_ROUTES), _route("conv_down", conv_down, CONV_DOWN_ROUTES)
-    circ = _route("conv3x3", conv3x3, CONV3X3_ROUTES)
+    hip = conv_routes(**routes)
     mode = block.mode
-    t = _pre_conv1x1(hip, x, block.bias1a, block.bias1b, block.branch_conv1.weight)
+    t = _pre_conv("conv1x1", hip, x, block.bias1a, block.bias1b, block.branch_conv1.weight)
     if mode in ("same", "out"):                         # 3x3 circular
-        t = _pre_conv3x3(circ, t, block.bias2a, block.bias2b, block.branch_conv2.weight)
+        t = _pre_conv("conv3x3", hip, t, block.bias2a, block.bias2b, block.branch_conv2.weight)
     elif mode == "down":
-        t = _pre_conv_down(down, t, block.bias2a, block.bias2b, block.branch_conv2.weight)
+        t = _pre_conv("conv_down", hip, t, block.bias2a, block.bias2b, block.branch_conv2.weight)
     else:                                               # ResizeConv2D: bicubic x2, then 1x1
-        t = _pre_conv1x1(hip, bicubic_up2(fixup_act(t, block.bias2a, block.bias2b)), None, None, block.branch_conv2.weight)
-    t = _pre_conv1x1(hip, t, block.bias3a, block.bias3b, block.branch_conv3.weight)
+        t = _pre_conv("conv1x1", hip, bicubic_up2(fixup_act(t, block.bias2a, block.bias2b)), None, None, block.branch_conv2.weight)
+    t = _pre_conv("conv1x1", hip, t, block.bias3a, block.bias3b, block.branch_conv3.weight)
     if block.skip_conv is None:
         return fixup_out(t, x, block.scale, block.bias4)
     w = block.skip_conv.weight
     if mode == "up":
-        skip = _pre_conv1x1(hip, bicubic_up2(x, block.bias1c), None, None, w)
+        skip = _pre_conv("conv1x1", hip, bicubic_up2(x, block.bias1c), None, None, w)
     elif mode == "down":
-        skip = _pre_conv_down(down, x, None, block.bias1c, w)
+        skip = _pre_conv("conv_down", hip, x, None, block.bias1c, w)
     elif mode == "same":
-        skip = _pre_conv1x1(hip, x, None, block.bias1c, w)
+        skip = _pre_conv("conv1x1", hip, x, None, block.bias1c, w)
     else:                                               # out2d: 3x3, zero padding
         skip = _conv(fixup_add(x, block.bias1c), w, padding=1)
     return fixup_out(t, skip, block.scale, block.bias4, block.bias1d)
@@ -489,10 +478,10 @@ def _compute_dtype(x):
     return x if x.dtype == torch.float64 and not x.is_cuda else x.float()
 
 
-def block_forward(block, x, conv1x1="torch", conv_down="torch", conv3x3="torch"):
-    """One PreActFixupResBlock mirror on an NCHW-shaped tensor (channels_last preferred: no copy) -> NCHW-shaped, with a graph."""
-    return to_nchw(block_forward_nhwc(block, to_nhwc(_compute_dtype(x)), conv1x1=conv1x1, conv_down=conv_down,
-                                      conv3x3=conv3x3))
+def block_forward(block, x, **routes):
+    """One PreActFixupResBlock mirror on an NCHW-shaped tensor (channels_last preferred: no copy) -> NCHW-shaped, with a graph.
+    routes: conv1x1 / conv_down / conv3x3, as in block_forward_nhwc."""
+    return to_nchw(block_forward_nhwc(block, to_nhwc(_compute_dtype(x)), **routes))
 
 
 def block_forward_torch(block, x):
@@ -548,15 +537,12 @@ def _quantize_torch(vq, inputs):
     return q, idx.reshape(cl.shape[:-1]), loss
 
 
-def forward_train(model, x, return_indices=False, conv1x1="torch", conv_down="torch", conv3x3="torch"):
+def forward_train(model, x, return_indices=False, **routes):
     """VQAE.forward (vq_ae/model.py:41-48) over a vqae_amd.model.VQAE mirror, with a graph: -> (out, (vq_loss,)), out NCHW-shaped
     (channels_last).  The stems are F.conv2d, the blocks block_forward, the quantiser its own trainable mirror (its EMA buffers
-    are updated in training mode, as in the reference).  conv1x1 / conv_down / conv3x3: the routes of the blocks' 1x1, 2x2
-    stride-2 and circular 3x3 convs (block_forward_nhwc)."""
-    _route("conv1x1", conv1x1, CONV1X1_ROUTES)
-    _route("conv_down", conv_down, CONV_DOWN_ROUTES)
-    _route("conv3x3", conv3x3, CONV3X3_ROUTES)
-    routes = dict(conv1x1=conv1x1, conv_down=conv_down, conv3x3=conv3x3)
+    are updated in training mode, as in the reference).  routes: conv1x1 / conv_down / conv3x3 = "torch" (default) | "hip", the
+    routes of the blocks' 1x1, 2x2 stride-2 and circular 3x3 convs (block_forward_nhwc)."""
+    conv_routes(**routes)
     enc, dec = model.encoder, model.decoder
     h = to_nhwc(_compute_dtype(x))
     h = _conv(h, enc.in_stem.weight, enc.in_stem.bias, padding=1)
@@ -579,7 +565,8 @@ def forward_train(model, x, return_indices=False, conv1x1="torch", conv_down="to
     return out, (vq_loss,)
 
 
-def step(model, batch, loss_f=F.huber_loss, conv1x1="torch", conv_down="torch", conv3x3="torch"):
-    """VQAE.step (vq_ae/model.py:114-122): -> (out, recon_loss, (vq_loss,)); the caller backpropagates recon_loss + sum(vq_loss)."""
-    out, encoding_loss = forward_train(model, batch, conv1x1=conv1x1, conv_down=conv_down, conv3x3=conv3x3)
+def step(model, batch, loss_f=F.huber_loss, **routes):
+    """VQAE.step (vq_ae/model.py:114-122): -> (out, recon_loss, (vq_loss,)); the caller backpropagates recon_loss + sum(vq_loss).
+    routes: conv1x1 / conv_down / conv3x3, as in forward_train."""
+    out, encoding_loss = forward_train(model, batch, **routes)
     return out, loss_f(input=out, target=batch), encoding_loss

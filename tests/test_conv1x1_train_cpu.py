@@ -1,5 +1,5 @@
 """CPU: the trainable 1x1 conv node of vqae_amd.train (conv1x1 / _Conv1x1Fn) through its plain-torch restatement -- the same
-forward and the same hand-derived backward csrc/conv1x1_train.hip implements (tests/test_conv1x1_train_gpu.py runs the kernels).
+forward and the same hand-derived backward csrc/conv_train.hip implements (tests/test_conv1x1_train_gpu.py runs the kernels).
 
   * torch.autograd.gradcheck of the restatement in fp64 for pre = 0 (u = x), 1 (u = x + b) and 2 (u = ELU(x + a) + b);
   * block_forward(..., conv1x1="hip") on CPU tensors against the "torch" route on every case of tests/fixup_train_cases.py:

@@ -1,4 +1,4 @@
-"""GPU: the trainable 1x1 conv kernels (csrc/conv1x1_train.hip) behind vqae_amd.ops.conv1x1_train_* and train.conv1x1.
+"""GPU: the trainable 1x1 conv kernels (csrc/conv_train.hip) behind vqae_amd.ops.conv1x1_train_* and train.conv1x1.
 
 Shapes: M in {1, 2, 31, 32, 33, 127, 128, 129, 257, 2 R + 5, 2^17 + 3} (R = vqae_conv1x1_train_wgrad_run(); around the 32-row
 MFMA tile, the 64-row weight-gradient step, the 128-row workgroup tile, more than one fp32 run, more than one run per

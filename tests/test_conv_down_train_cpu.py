@@ -1,5 +1,5 @@
 """CPU: the trainable 2x2, stride-2 conv node of vqae_amd.train (conv_down / _ConvDownFn) through its plain-torch restatement
--- the same forward and the same hand-derived backward csrc/conv_down_train.hip implements (tests/test_conv_down_train_gpu.py
+-- the same forward and the same hand-derived backward csrc/conv_train.hip implements (tests/test_conv_down_train_gpu.py
 runs the kernels).
 
   * torch.autograd.gradcheck of the restatement in fp64 for pre = 0 (u = x), 1 (u = x + b) and 2 (u = ELU(x + a) + b), for a

@@ -1,4 +1,4 @@
-"""GPU: the trainable 2x2, stride-2 conv kernels (csrc/conv_down_train.hip) behind vqae_amd.ops.conv_down_train_* and
+"""GPU: the trainable 2x2, stride-2 conv kernels (csrc/conv_train.hip) behind vqae_amd.ops.conv_down_train_* and
 train.conv_down.  x [B, 2 OH, 2 OW, Ci], y [B, OH, OW, Co], M = B OH OW rows of a GEMM with K = 4 Ci.
 
 Shapes: (B, OH, OW) in {(1,1,1), (1,1,2), (2,3,5), (1,1,31), (1,4,8), (1,3,11), (1,1,127), (2,8,8), (1,3,43), (1,1,257),
