@@ -25,6 +25,13 @@
 // transforms, the other one's MFMAs run.  Then t2 = ELU(Y + b3a) + b3b goes to LDS as the [128 px][132] A operand of
 // the conv3 / next-conv1 tails.
 //
+// C = 32 on the exact 128-wide grid (ROWS in the kernel) has no V: the workgroup's six input rows come from global memory
+// once each, row-coalesced, into a ring of four raw rows in the same LDS bytes (rows r0 + 2 and r0 + 4 replace r0 - 1 and
+// r0 + 1 between passes, requested a pass early; LDS-only barriers).  At C = 32 every V element is consumed by exactly one
+// MFMA lane, so that lane reads the two raw rows of the pass at its tile's four columns, forms the row combinations and each
+// nu's operand itself -- the transform's expressions in its order, beside the MFMAs instead of in a phase of their own.  The
+// column-blocked grids (WIDE) and the other channel counts keep the transform described above.  DESIGN.md section 8.
+//
 // Measured (cfg B, batch 256, per-phase s_memtime stamps of a developer build, removed after f2b9d9d): a tile costs a wave
 // ~98 k cycles of MFMA issue, ~10 k of VALU (fold 576, ELU 1150, transforms 512 instructions ...; fp32 MFMA and VALU do not
 // co-execute) and ~20 k of exposed waits across its 14 barrier-separated phases; a lone workgroup per CU takes 154 k cycles
@@ -70,6 +77,14 @@ template <int C> struct WinoCfg {
     // levels move as many bytes per tile as C = 128 with 1/4 (C = 32) or 1/2 (C = 64) of the matrix work, and without it a tile
     // takes HBM time PLUS matrix time (round 3).  At C = 128 the same prefetch measured slower (section 4, negative results).
     static constexpr int PREF = C <= 64 ? 1 : 0;
+    // C = 32, exact width: a ring of four raw input rows [W][LDT] takes V's place (same bytes) and the MFMA lanes form
+    // their own operands from it.  A pixel with (px & 16) sits 4 floats into its own padding: tile columns li and li + 8
+    // of a ds_read_b128 lane group (pixel stride 2 * LDT = 72 floats, a multiple of 8) then fall on different 16-byte slots.
+    static constexpr int ROW_LDS = W * LDT;            // floats per ring slot
+    static constexpr int ring_px(int px) { return px * LDT + ((px & 16) ? 4 : 0); }
+    // ring slot of input row row0 + rel: {0, -1, 1, 3} at the start, row 2 replaces row -1 after pass 0, row 4 replaces row 1 after
+    // pass 2.  Rows two apart sit in neighbouring slots, so tile row 1 reads one slot above tile row 0 in every pass.
+    static constexpr int ring_slot(int rel) { return rel == 0 ? 0 : (rel == -1 || rel == 2 ? 1 : (rel == 3 ? 3 : 2)); }
 };
 
 // DT: autocast rounding points compiled in (16-bit modes, C = 32 only: every conv operand and conv output is rounded
@@ -94,9 +109,11 @@ void wino_trunk_kernel(const WinoK p) {
     };
     constexpr int W = K::W, PX = K::PX, TC = K::TC, NS = K::NS, KS = K::KS, C4 = K::C4, RP = K::RP, LDT = K::LDT, WN = K::WN;
     constexpr int MI = K::MI, NI = K::NI;
-    constexpr bool PREF = K::PREF && !WIDE;                           // column-blocked grids carry more geometry: no registers left for it
+    constexpr bool ROWS = C == 32 && !WIDE;                          // every input row staged once in an LDS ring (below)
+    constexpr bool PREF = K::PREF && !WIDE && !ROWS;                  // column-blocked grids carry more geometry: no registers left for it
     constexpr int STEPS = 4 * KS;                                    // k-slices per pass (4 nu)
-    extern __shared__ __attribute__((aligned(16))) float lds[];      // V[4][TILES][LDT]  /  T[PX][LDT]
+    static_assert(!ROWS || (4 * K::ROW_LDS * 4 == K::LDS_BYTES && K::NS == 1 && K::TC == 64 && K::RP * 4 == W), "ring geometry");
+    extern __shared__ __attribute__((aligned(16))) float lds[];      // V[4][TILES][LDT] (ROWS: ring[4][W][LDT])  /  T[PX][LDT]
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -165,10 +182,73 @@ void wino_trunk_kernel(const WinoK p) {
             for (int j = 0; j < 4; ++j)
                 v[2 * s_r + s_c][j] = xi == 1 ? la[s_c][j] + lb[s_c][j] : la[s_c][j] - lb[s_c][j];
     };
-    tr_load(0, 0);
-    tr_combine(0, 0);
-    tr_load(0, 1);
-    tr_combine(0, 1);
+    if constexpr (!ROWS) {
+        tr_load(0, 0);
+        tr_combine(0, 0);
+        tr_load(0, 1);
+        tr_combine(0, 1);
+    }
+
+    // ---- ROWS: each of the six input rows row0 - 1 .. row0 + 4 comes from global memory once, row-coalesced in the tails'
+    // (cg, tj0) view, into a ring of four raw rows.  Pass xi reads rows {-1, 1, 3} / {0 .. 3} / {0 .. 3} / {0, 2, 4}: row 2 takes
+    // row -1's slot after pass 0, row 4 takes row 1's after pass 2, each requested a pass early and kept in stg meanwhile.
+    // The MFMA lane (li, hh) of wave mt owns tile column 32 (mt & 1) + li of tile row mt >> 1.  Per k-slice it reads the two raw
+    // rows of the pass at its tile's columns, makes the row combinations rc (tr_combine's expressions) and from them each nu's
+    // operand (the V stores' expressions) right before its MFMAs.  Passes 0 .. 2 read all four columns in their nu = 0 steps
+    // and keep rc for the pass.  The last pass holds the residual rows and the first tail weights from nu = 2 on, so it reads
+    // only what the next nu needs (rows_need): columns {0, 2}, then {1, 2} (kept for nu = 2), then {1, 3}.
+    f32x4 stg[4], raw[2][4], rc[ROWS ? KS : 1][4];
+    const float* fr[4];                                               // this lane's four pixel columns, k-slice 0, slot 0 (tile row 1: slot 1)
+    float* ring_w;                                                    // staging: pixels tj0 + RP i of slot 0
+    if constexpr (ROWS) {
+        ring_w = lds + K::ring_px(tj0) + 4 * cg;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            fr[j] = lds + (mt >> 1) * K::ROW_LDS + K::ring_px((2 * ((mt & 1) * 32 + li) - 1 + j) & (W - 1)) + 4 * hh;
+    }
+    auto stage_load = [&](int rel, f32x4* dst) {                     // input row row0 + rel, circular in y
+        int r = row0 + rel;
+        r = r < 0 ? r + p.H : (r >= p.H ? r - p.H : r);
+        const float* const src = xim + r * (W * C) + tj0 * C + 4 * cg;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dst[i] = *reinterpret_cast<const f32x4*>(src + RP * i * C);
+    };
+    auto stage_write = [&](int rel, const f32x4* src) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            *reinterpret_cast<f32x4*>(ring_w + K::ring_slot(rel) * K::ROW_LDS + RP * i * LDT) = rnd4(src[i]);   // conv2 input cast
+    };
+    auto rows_need = [](int xi, int nu) -> int {                     // columns (bit j) that step (nu, .) of pass xi reads
+        return xi < 3 ? (nu == 0 ? 15 : 0) : (nu == 0 ? 5 : (nu == 1 ? 6 : (nu == 2 ? 0 : 10)));
+    };
+    auto rows_read = [&](int xi, int u, int cols) {                  // raw rows d[ra], d[rb] of this wave's tile row, k-slice u
+        const int ra = xi == 0 ? 0 : (xi == 2 ? 2 : 1);
+        const int rb = xi == 0 ? 2 : (xi == 1 ? 2 : (xi == 2 ? 1 : 3));
+        const int oa = K::ring_slot(ra - 1) * K::ROW_LDS + 8 * u, ob = K::ring_slot(rb - 1) * K::ROW_LDS + 8 * u;   // tile row 0's
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (cols >> j & 1) {
+                raw[0][j] = *reinterpret_cast<const f32x4*>(fr[j] + oa);
+                raw[1][j] = *reinterpret_cast<const f32x4*>(fr[j] + ob);
+            }
+    };
+    auto rows_combine = [&](int xi, int u, int cols) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (cols >> j & 1) rc[u][j] = xi == 1 ? raw[0][j] + raw[1][j] : raw[0][j] - raw[1][j];
+    };
+    auto rows_operand = [&](int nu, int u) -> f32x4 {
+        return nu == 0 ? rc[u][0] - rc[u][2] : (nu == 1 ? rc[u][1] + rc[u][2] : (nu == 2 ? rc[u][2] - rc[u][1] : rc[u][1] - rc[u][3]));
+    };
+    if constexpr (ROWS) {
+        f32x4 st[4][4];
+        constexpr int first[4] = {-1, 1, 3, 0};                       // pass 0's rows first
+#pragma unroll
+        for (int q = 0; q < 4; ++q) stage_load(first[q], st[q]);
+        stage_load(2, stg);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) stage_write(first[q], st[q]);
+    }
 
     // Tail operands requested while the last pass's MFMAs run.  vmcnt retires in order (stores included), so a load
     // issued behind a slow one waits for it: the residual rows (HBM) go out after the last weight-fragment load of
@@ -196,15 +276,22 @@ void wino_trunk_kernel(const WinoK p) {
     for (int xi = 0; xi < 4; ++xi) {
         // ---- row xi of B^T d B for all tiles and channels -> V[nu][tile][c] (v holds the row combinations) ---------
         __builtin_amdgcn_sched_barrier(0);
-        if (xi > 0) __syncthreads();                                  // every wave is done with V of pass xi - 1
+        if constexpr (ROWS) {
+            if (xi == 1 || xi == 3) {                                 // ring replacement: rows 2 / 4 over rows -1 / 1
+                vqae::lds_barrier();                                  // every wave is done with the slot's old row
+                stage_write(xi + 1, stg);
+            }
+        } else {
+            if (xi > 0) __syncthreads();                              // every wave is done with V of pass xi - 1
 #pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            const int tile = (it >> 1) * TC + tj0 + RP * (it & 1);
-            float* dst = lds + tile * LDT + 4 * cg;
-            *reinterpret_cast<f32x4*>(dst + 0 * K::TILES * LDT) = v[it][0] - v[it][2];
-            *reinterpret_cast<f32x4*>(dst + 1 * K::TILES * LDT) = v[it][1] + v[it][2];
-            *reinterpret_cast<f32x4*>(dst + 2 * K::TILES * LDT) = v[it][2] - v[it][1];
-            *reinterpret_cast<f32x4*>(dst + 3 * K::TILES * LDT) = v[it][1] - v[it][3];
+            for (int it = 0; it < 4; ++it) {
+                const int tile = (it >> 1) * TC + tj0 + RP * (it & 1);
+                float* dst = lds + tile * LDT + 4 * cg;
+                *reinterpret_cast<f32x4*>(dst + 0 * K::TILES * LDT) = v[it][0] - v[it][2];
+                *reinterpret_cast<f32x4*>(dst + 1 * K::TILES * LDT) = v[it][1] + v[it][2];
+                *reinterpret_cast<f32x4*>(dst + 2 * K::TILES * LDT) = v[it][2] - v[it][1];
+                *reinterpret_cast<f32x4*>(dst + 3 * K::TILES * LDT) = v[it][1] - v[it][3];
+            }
         }
 
         // ---- GEMM: acc = V[nu] x U[xi, nu]^T for nu = 0..3, STEPS steps of one k-slice (8 channels) each -------------
@@ -214,10 +301,18 @@ void wino_trunk_kernel(const WinoK p) {
 #pragma unroll
         for (int s = 0; s < BPF; ++s)                                  // first B fragments: in flight across the barrier
             bq[s] = *reinterpret_cast<const f32x4*>(ux + WB(s));
-        __syncthreads();
-        if (PREF && xi < 3) tr_load(xi + 1, 0);                     // in flight under this pass's MFMAs (v is dead until then)
         f32x4 aq[2];
-        aq[0] = *reinterpret_cast<const f32x4*>(af);
+        if constexpr (ROWS) {
+            // LDS-only barriers: the weight ring and the staged row stay in flight across them.  Pass 2 reads pass 1's rows.
+            if (xi != 2) vqae::lds_barrier();
+            else stage_load(4, stg);
+            rows_read(xi, 0, rows_need(xi, 0));
+            rows_combine(xi, 0, rows_need(xi, 0));
+        } else {
+            __syncthreads();
+            if (PREF && xi < 3) tr_load(xi + 1, 0);                 // in flight under this pass's MFMAs (v is dead until then)
+            aq[0] = *reinterpret_cast<const f32x4*>(af);
+        }
 #pragma unroll
         for (int nu = 0; nu < 4; ++nu) {
             // One accumulator live at a time (register budget).  A lone dependent chain issues one 32x32x2 MFMA per
@@ -228,8 +323,12 @@ void wino_trunk_kernel(const WinoK p) {
 #pragma unroll
             for (int u = 0; u < KS; ++u) {
                 const int s = KS * nu + u;
-                if (s + 1 < STEPS)
+                if constexpr (ROWS) {
+                    if (s + 1 < STEPS) rows_read(xi, (s + 1) % KS, rows_need(xi, (s + 1) / KS));   // read under this step's MFMAs
+                    aq[s & 1] = rows_operand(nu, u);
+                } else if (s + 1 < STEPS) {
                     aq[(s + 1) & 1] = *reinterpret_cast<const f32x4*>(af + ((s + 1) / KS) * K::TILES * LDT + 8 * ((s + 1) % KS));
+                }
                 const f32x4 b = bq[s % BPF];
                 if (s + BPF < STEPS)
                     bq[s % BPF] = *reinterpret_cast<const f32x4*>(ux + WB(s + BPF));
@@ -243,6 +342,12 @@ void wino_trunk_kernel(const WinoK p) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
                     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(b[r], aq[s & 1][r], acc, 0, 0, 0);   // D[channel][tile]
+                if constexpr (ROWS) {
+                    if (s + 1 < STEPS && rows_need(xi, (s + 1) / KS) != 0) {
+                        __builtin_amdgcn_sched_barrier(0);            // the wait for the raw rows stays behind the MFMAs
+                        rows_combine(xi, (s + 1) % KS, rows_need(xi, (s + 1) / KS));
+                    }
+                }
                 __builtin_amdgcn_sched_barrier(0);                    // keep the prefetch distances as written (register budget)
             }
             // fold: Y[a][b] += A^T[a][xi] * A^T[b][nu] * acc,  A^T = [1 1 1 0; 0 1 -1 -1]
@@ -261,7 +366,7 @@ void wino_trunk_kernel(const WinoK p) {
         // (0.499 vs 0.478 ms per launch), as did a longer weight-fragment prefetch: more loads in flight per CU back
         // up the vector-memory queue and the in-order wave stalls at issue, MFMAs included.  The partner workgroup of
         // the CU covers this wait.
-        if (xi < 3) {
+        if (!ROWS && xi < 3) {
             if (!PREF) tr_load(xi + 1, 0);
             tr_combine(xi + 1, 0); tr_load(xi + 1, 1); tr_combine(xi + 1, 1);
         }
