@@ -205,20 +205,24 @@ SYMBOLS = {
     "vqae_prof_end": (c_int, [POINTER(c_double), POINTER(c_int), POINTER(c_double)]),
 }
 
-# The trainable convs of csrc/conv_train.hip: node -> (ABI stem, kernel size, stride, image).  image: the node is called with
-# (batch, h, w), a weight layout and a forward workspace; without it, with its rows M as given and a [Co, Ci] weight.
-CONV_TRAIN = {"conv1x1": ("vqae_conv1x1_train", 1, 1, False), "conv_down": ("vqae_conv_down_train", 2, 2, True),
-              "conv3x3": ("vqae_conv3x3_train", 3, 1, True)}
-for _stem, _, _, _image in CONV_TRAIN.values():
+# The trainable convs of csrc/conv_train.hip and csrc/conv_train_thin.hip: node -> (ABI stem, kernel size, stride, image, bias).
+# image: the node is called with (batch, h, w), a weight layout and a forward workspace; without it, with its rows M as given
+# and a [Co, Ci] weight.  bias: the forward takes a bias [Co] (or NULL) behind w, the backward writes g_bias behind g_b.
+CONV_TRAIN = {"conv1x1": ("vqae_conv1x1_train", 1, 1, False, False), "conv_down": ("vqae_conv_down_train", 2, 2, True, False),
+              "conv3x3": ("vqae_conv3x3_train", 3, 1, True, False), "conv3x3z": ("vqae_conv3x3z_train", 3, 1, True, True)}
+for _stem, _, _, _image, _bias in CONV_TRAIN.values():
     _geo, _lay = ([c_int64, c_int, c_int], [c_int]) if _image else ([c_int64], [])
+    _b = [c_void_p] if _bias else []
     SYMBOLS.update({
         _stem + "_supported": (c_int, [c_int, c_int]),
         _stem + "_wgrad_run": (c_int, []),
         _stem + "_workspace_bytes": (c_size_t, _geo + [c_int, c_int]),
-        # x a b pre w [w_layout] geometry cin cout y [ws] stream;  g x a b pre w [..] geometry cin cout g_x g_w g_a g_b ws stream
-        _stem + "_forward_f32": (c_int, [c_void_p] * 3 + [c_int, c_void_p] + _lay + _geo + [c_int, c_int]
+        # x a b pre w [bias] [w_layout] geometry cin cout y [ws] stream
+        # g x a b pre w [w_layout] geometry cin cout g_x g_w g_a g_b [g_bias] ws stream
+        _stem + "_forward_f32": (c_int, [c_void_p] * 3 + [c_int, c_void_p] + _b + _lay + _geo + [c_int, c_int]
                                  + [c_void_p] * (3 if _image else 2)),
-        _stem + "_backward_f32": (c_int, [c_void_p] * 4 + [c_int, c_void_p] + _lay + _geo + [c_int, c_int] + [c_void_p] * 6),
+        _stem + "_backward_f32": (c_int, [c_void_p] * 4 + [c_int, c_void_p] + _lay + _geo + [c_int, c_int] + [c_void_p] * 4 + _b
+                                  + [c_void_p] * 2),
     })
 
 _lib = None

@@ -817,6 +817,19 @@ inline int entry_backward(const float* g, const float* x, const float* a, const 
 
 }  // namespace
 
+// ---- kernels.h: the two final-sum launches, for conv_train_thin.hip ---------------------------------------------------------
+int vqae::conv_train_sum_final(const double* partials, int n_rows, float* o0, float* o1, hipStream_t stream) {
+    ct_sum_final<<<1, CT_THREADS, 0, stream>>>(partials, n_rows, o0, o1);
+    VQAE_LAUNCH_CHECK();
+    return VQAE_OK;
+}
+int vqae::conv_train_wgrad_final(const double* slots, int P, int n, int cin, int taps, int w_layout, float* g_w,
+                                 hipStream_t stream) {
+    ct_wgrad_final<<<blocks_for(n), CT_THREADS, 0, stream>>>(slots, P, n, cin, taps, w_layout, g_w);
+    VQAE_LAUNCH_CHECK();
+    return VQAE_OK;
+}
+
 // ---- the C ABI ---------------------------------------------------------------------------------------------------------------
 // the 1x1, stride-1 node
 extern "C" int vqae_conv1x1_train_supported(int cin, int cout) { return supported(cin, cout) ? 1 : 0; }

@@ -203,4 +203,13 @@ int vq_write_idx(const int* idx32, int64_t N, void* out, int idx_dtype, hipStrea
 // vqae_bicubic_up2_bias_f32, vqae_bicubic_up2_backward_f32 and their workspace size): C ABI only, include/vqae_hip.h.  The
 // grid and the number of fp64 partial rows are functions of the shape alone (ft_grid there).
 
+// ---- conv_train.hip ----------------------------------------------------------------------------
+// The trainable 1x1, 2x2 stride-2 and circular 3x3 convs: C ABI only, include/vqae_hip.h.  Its two final-sum launches serve
+// conv_train_thin.hip (the zero-padded 3x3 convs with a 3-channel side) as well:
+// partials [n_rows][2] doubles -> *o0, *o1 (each may be NULL): one workgroup, fixed order, one rounding
+int conv_train_sum_final(const double* partials, int n_rows, float* o0, float* o1, hipStream_t stream);
+// slots [P][n] doubles, an element order [cout][taps][cin] -> g_w [n] floats in the weight's layout (w_layout 1: that order,
+// 0: [cout][cin][taps]): the P slots added in index order in fp64, rounded once
+int conv_train_wgrad_final(const double* slots, int P, int n, int cin, int taps, int w_layout, float* g_w, hipStream_t stream);
+
 }  // namespace vqae

@@ -285,9 +285,9 @@ def bicubic_up2_backward(g, want_bias=True):
 @functools.lru_cache(maxsize=None)
 def _conv_train_node(node):
     """L.CONV_TRAIN[node] with its entries resolved, once."""
-    stem, k, stride, image = L.CONV_TRAIN[node]
+    stem, k, stride, image, bias = L.CONV_TRAIN[node]
     fns = {fn: getattr(L.lib(), f"{stem}_{fn}") for fn in ("workspace_bytes", "forward_f32", "backward_f32")}
-    return types.SimpleNamespace(kernel=(k, k), stride=stride, image=image, **fns)
+    return types.SimpleNamespace(kernel=(k, k), stride=stride, image=image, bias=bias, **fns)
 
 
 def _conv_train_args(nd, x, w, a, b):
@@ -313,19 +313,29 @@ def _conv_train_ws(nd, geo, cin, cout, dev):
     return torch.empty(nd.workspace_bytes(*geo[-3:], cin, cout), dtype=torch.uint8, device=dev)         # geo without the layout
 
 
-def _conv_train_forward(node, x, w, a, b):
+def _conv_train_forward(node, x, w, a, b, bias=None):
+    """bias [Co] or None: for a node with a bias seat (L.CONV_TRAIN) only."""
     _need_gpu(x, w)
     x = x.contiguous()
     nd = _conv_train_node(node)
+    assert bias is None or nd.bias, node
     wc, geo, cin, cout, y_shape, pre = _conv_train_args(nd, x, w, a, b)
     y = torch.empty(y_shape, dtype=torch.float32, device=x.device)
-    ws = _conv_train_ws(nd, geo, cin, cout, x.device) if nd.image and geo[0] == 0 else None           # layout 0 alone needs one
-    L.check(nd.forward_f32(_p(x), _p(_scalar(a)), _p(_scalar(b)), pre, _p(wc), *geo, cin, cout, _p(y),
-                           *([_p(ws)] if nd.image else []), _stream()))
+    # layout 0 alone needs one, and only where the node permutes the weight
+    ws = _conv_train_ws(nd, geo, cin, cout, x.device) if nd.image and not nd.bias and geo[0] == 0 else None
+    if bias is not None:
+        _need_gpu(bias)
+        bias = bias.detach().float().contiguous()
+        assert tuple(bias.shape) == (cout,), (bias.shape, w.shape)
+        if bias.data_ptr() % 16:                                   # a view into a flat buffer: the kernels read 16-byte groups
+            bias = bias.clone()
+    L.check(nd.forward_f32(_p(x), _p(_scalar(a)), _p(_scalar(b)), pre, _p(wc), *([_p(bias)] if nd.bias else []), *geo, cin, cout,
+                           _p(y), *([_p(ws)] if nd.image else []), _stream()))
     return y
 
 
-def _conv_train_backward(node, g, x, w, a, b, need_x, need_w):
+def _conv_train_backward(node, g, x, w, a, b, need_x, need_w, need_bias=False):
+    """-> (g_x, g_w, g_a, g_b), and g_bias [Co] | None behind them for a node with a bias seat."""
     _need_gpu(g, x, w)
     g, x = g.contiguous(), x.contiguous()
     nd = _conv_train_node(node)
@@ -340,10 +350,12 @@ def _conv_train_backward(node, g, x, w, a, b, need_x, need_w):
     g_w = (torch.empty_like(wc) if nd.image else torch.empty(w.shape, dtype=torch.float32, device=dev)) if need_w else None
     g_a = torch.empty(1, dtype=torch.float32, device=dev) if pre == 2 else None
     g_b = torch.empty(1, dtype=torch.float32, device=dev) if pre >= 1 else None
+    assert nd.bias or not need_bias, node
+    g_bias = torch.empty(cout, dtype=torch.float32, device=dev) if need_bias else None
     ws = _conv_train_ws(nd, geo, cin, cout, dev)
     L.check(nd.backward_f32(_p(g), _p(x), _p(_scalar(a)), _p(_scalar(b)), pre, _p(wc), *geo, cin, cout, _p(g_x), _p(g_w), _p(g_a),
-                            _p(g_b), _p(ws), _stream()))
-    return g_x, g_w, g_a, g_b
+                            _p(g_b), *([_p(g_bias)] if nd.bias else []), _p(ws), _stream()))
+    return (g_x, g_w, g_a, g_b, g_bias) if nd.bias else (g_x, g_w, g_a, g_b)
 
 
 def conv1x1_train_supported(cin, cout):
@@ -416,6 +428,32 @@ def conv3x3_train_backward(g, x, w, a=None, b=None, need_x=True, need_w=True):
     transposed weight), g_x = g_u * ELU'(x + a) (g_u without an activation), g_a = sum g_x, g_b = sum g_u, g_w = the weight
     gradient with u recomputed from x."""
     return _conv_train_backward("conv3x3", g, x, w, a, b, need_x, need_w)
+
+
+def conv3x3z_train_supported(cin, cout):
+    """Whether the trainable zero-padded 3x3 conv kernels take (cin, cout): exactly one side of 3 channels (cin = 3 with cout a
+    multiple of 8 up to 64, or cout = 3 with cin a multiple of 8 up to 256); any H, W >= 1.  Needs no GPU."""
+    return bool(L.lib().vqae_conv3x3z_train_supported(int(cin), int(cout)))
+
+
+def conv3x3z_train_wgrad_run():
+    """R: the longest fp32 accumulation run of the weight and bias gradients, in rows."""
+    return int(L.lib().vqae_conv3x3z_train_wgrad_run())
+
+
+def conv3x3z_train_forward(x, w, bias=None, c=None):
+    """y [B, H, W, Co] = bias + the 3x3, stride-1 conv with ZERO padding 1 of u [B, H, W, Ci] with w [Co, Ci, 3, 3] (contiguous
+    or channels_last, read in place); u = x (c None) or x + c, c a one-element device tensor.  The padding follows the pre-op:
+    F.conv2d(x + c, w, bias, padding=1).  u is not materialised."""
+    return _conv_train_forward("conv3x3z", x, w, None, c, bias)
+
+
+def conv3x3z_train_backward(g, x, w, c=None, need_x=True, need_w=True, need_bias=False):
+    """-> (g_x [B, H, W, Ci] | None, g_w (w's shape and memory format) | None, g_bias [Co] | None, g_c [1] | None) from
+    g [B, H, W, Co] and the forward's x, w, c: g_x the data gradient (gathered: the zero-padded 3x3 of g with the flipped,
+    transposed weight), g_c = sum g_x, g_w the weight gradient with u recomputed from x, g_bias = sum of g over the pixels."""
+    g_x, g_w, _, g_c, g_bias = _conv_train_backward("conv3x3z", g, x, w, None, c, need_x, need_w, need_bias)
+    return g_x, g_w, g_bias, g_c
 
 
 def vq_forward(z_flat, embed, commitment_cost=1.0, idx_dtype=torch.int64, want_q=True, want_margin=False, p=4):

@@ -25,8 +25,18 @@ keyword `conv3x3`:
                                  into the operand addressing, so neither the activation nor its halo is written or kept.  Channel
                                  counts outside the kernels' rule take the torch route, counted in stats["conv3x3_fallbacks"];
                                  stats["conv3x3_hip"] counts the nodes.
-With all three keywords at their defaults the graph is op for op the one described above.
-The zero-padded 3x3 skip_conv of an 'out' block, the stems and the quantiser's projections stay with torch.
+The zero-padded 3x3 convs with a 3-channel side -- encoder.in_stem (3 -> C0, bias), decoder.out_stem (C0 -> 3, bias) and the
+skip_conv of an 'out' block (C -> 3) -- have one behind the independent keyword `conv3x3z`:
+
+    conv3x3z="torch" (default)   F.conv2d(..., padding=1), behind fixup_add(x, bias1c) for the skip_conv, as always
+    conv3x3z="hip"               ONE node of csrc/conv_train_thin.hip, a direct conv on the vector ALU: the conv's bias and, for
+                                 the skip_conv, x + bias1c are folded in, and the zeros are padded behind the pre-op by select, so
+                                 no padded or re-laid-out copy of a full-resolution tensor exists.  Channel counts outside the
+                                 kernels' rule (one side 3, the other a multiple of 8) take the torch route, counted in
+                                 stats["conv3x3z_fallbacks"]; stats["conv3x3z_hip"] counts the nodes.
+With all four keywords at their defaults the graph is op for op the one described above.
+No conv then stays with torch except branch_conv3 8 -> 3 of an 'out' block, a counted conv1x1 fall-back (no shipped config
+instantiates an 'out' block), and the quantiser's 1x1 projections, which have their own fused backward (layers/vq.py).
 
     block_forward(block, x)      one block, NCHW in and out, any of the four modes, with or without a skip_conv
     forward_train(model, x)      VQAE.forward (vq_ae/model.py:41-48) over a vqae_amd.model.VQAE mirror -> (out, (vq_loss,))
@@ -34,6 +44,7 @@ The zero-padded 3x3 skip_conv of an 'out' block, the stems and the quantiser's p
     conv1x1(x, w, a, b)          the fused node on [B, H, W, Ci]
     conv_down(x, w, a, b)        the fused 2x2, stride-2 node: [B, H, W, Ci] -> [B, H/2, W/2, Co]
     conv3x3(x, w, a, b)          the fused circular 3x3 node: [B, H, W, Ci] -> [B, H, W, Co]
+    conv3x3z(x, w, bias, c)      the fused zero-padded 3x3 node with a 3-channel side: [B, H, W, Ci] -> [B, H, W, Co]
 
 The functional ops (fixup_act, fixup_add, fixup_out, bicubic_up2) take channel-last tensors [B, H, W, C], like every other
 op of the package.  The graph stays channel-last throughout (the reference trains in channels_last: model.py:124-126): a conv
@@ -44,9 +55,9 @@ The one-element parameters (bias1a .. bias4, scale, bias1c / bias1d) are read by
 gradients are written to device tensors by fixed-order fp64 sums: a step never synchronises the host for them, and two runs
 of any op here give the same bits -- under conv1x1="hip" the 1x1 convs and their weight gradients included, under
 conv_down="hip" the 2x2, stride-2 ones, under conv3x3="hip" the circular 3x3 ones: under conv1x1="hip", conv3x3="hip" no conv
-of a 'same' block is MIOpen's, and every gradient of the block repeats bit for bit.  (A whole step also runs MIOpen's gradients
-of the remaining convs -- the zero-padded 3x3 skip of 'out' blocks, the stems, the quantiser's projections -- for which no such
-claim is made.)
+of a 'same' block is MIOpen's, and every gradient of the block repeats bit for bit; under conv3x3z="hip" the stems and the
+'out' block's skip_conv too, so that with all four keywords "hip" no conv of a step on a shipped-style spec is MIOpen's and two
+runs of the step give the same gradients bit for bit.
 
 Each Function has a restatement in plain torch ops, taken when its tensors are on the CPU: the same forward, and the SAME
 hand-derived backward (the gather-fold of the halo, the bicubic adjoint, the fixed-order sums), which is what
@@ -64,9 +75,9 @@ from .layers.conv_block import PreActFixupResBlock
 from .layers.vq import ProjectedEMAVectorQuantizer2d
 
 stats = {"layout_checks": 0, "layout_copies": 0, "conv1x1_hip": 0, "conv1x1_fallbacks": 0, "conv_down_hip": 0,
-         "conv_down_fallbacks": 0, "conv3x3_hip": 0, "conv3x3_fallbacks": 0}
-ROUTES = ("torch", "hip")                                     # of each of the keywords conv1x1, conv_down, conv3x3
-CONV1X1_ROUTES = CONV_DOWN_ROUTES = CONV3X3_ROUTES = ROUTES
+         "conv_down_fallbacks": 0, "conv3x3_hip": 0, "conv3x3_fallbacks": 0, "conv3x3z_hip": 0, "conv3x3z_fallbacks": 0}
+ROUTES = ("torch", "hip")                                     # of each of the keywords conv1x1, conv_down, conv3x3, conv3x3z
+CONV1X1_ROUTES = CONV_DOWN_ROUTES = CONV3X3_ROUTES = CONV3X3Z_ROUTES = ROUTES
 
 _W75 = (-0.03515625, 0.26171875, 0.87890625, -0.10546875)     # even outputs: inputs m-2 .. m+1, m = o >> 1
 _W25 = (-0.10546875, 0.87890625, 0.26171875, -0.03515625)     # odd outputs:  inputs m-1 .. m+2
@@ -382,6 +393,56 @@ def conv3x3(x, w, a=None, b=None):
     return _Conv3x3Fn.apply(x, w, a, b)
 
 
+def _conv3x3z_backward_torch(g, x, w, c, need_x, need_w, need_bias):
+    """The hand-derived backward of F.conv2d(x + c, w, bias, padding=1) on [B, H, W, C] tensors -> (g_x, g_w, g_bias, g_c)."""
+    Co = g.shape[-1]
+    # the data gradient of the padded input [B, H + 2, W + 2, Ci], cropped: the rim's gradient belongs to the zeros
+    g_x = F.conv_transpose2d(to_nchw(g), w)[:, :, 1:-1, 1:-1].permute(0, 2, 3, 1)
+    g_w = None
+    if need_w:
+        u = x if c is None else x + c
+        patches = F.pad(u, (0, 0, 1, 1, 1, 1)).unfold(1, 3, 1).unfold(2, 3, 1)                    # [B, H, W, Ci, kh, kw]
+        g_w = (g.reshape(-1, Co).t() @ patches.reshape(-1, 9 * x.shape[-1])).reshape(w.shape)
+        if not w.is_contiguous() and w.is_contiguous(memory_format=torch.channels_last):
+            g_w = g_w.contiguous(memory_format=torch.channels_last)
+    return g_x, g_w, g.sum((0, 1, 2)) if need_bias else None, g_x.sum()
+
+
+class _Conv3x3zFn(torch.autograd.Function):
+    """y [B, H, W, Co] = bias + the 3x3, stride-1 conv with ZERO padding 1 of u = x + c (c None: x) with w [Co, Ci, 3, 3]: the
+    stems and the skip_conv of an 'out' block.  The zeros are padded after the pre-op.  Saves x, w and c, not u.  On the device
+    ops.conv3x3z_train_forward / _backward (csrc/conv_train_thin.hip); on CPU tensors the restatement above."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, c):
+        ctx.save_for_backward(x, w, *(() if c is None else (c,)))
+        ctx.bias = bias
+        if x.is_cuda:
+            return ops.conv3x3z_train_forward(x.float(), w, bias, c)
+        return to_nhwc(F.conv2d(to_nchw(x if c is None else x + c), w, bias, padding=1))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, w, *rest = ctx.saved_tensors
+        c = rest[0] if rest else None
+        need_x, need_w, need_bias = ctx.needs_input_grad[:3]
+        need_bias = need_bias and ctx.bias is not None
+        if g.is_cuda:
+            g_x, g_w, g_bias, g_c = ops.conv3x3z_train_backward(_dense(g.float()), x.float(), w, c, need_x, need_w, need_bias)
+        else:
+            g_x, g_w, g_bias, g_c = _conv3x3z_backward_torch(g, x, w, c, need_x, need_w, need_bias)
+        return (g_x if need_x else None, g_w.to(w.dtype) if need_w else None,
+                g_bias.to(ctx.bias.dtype) if need_bias else None, _like(g_c, c) if c is not None else None)
+
+
+def conv3x3z(x, w, bias=None, c=None):
+    """The 3x3, stride-1, zero-padding-1 conv on [B, H, W, Ci] -> [B, H, W, Co], w [Co, Ci, 3, 3], bias [Co] or None, of x + c
+    (c None: of x) as ONE node -- F.conv2d(x + c, w, bias, padding=1): csrc/conv_train_thin.hip on the device (one side of 3
+    channels: ops.conv3x3z_train_supported), a plain-torch restatement on CPU tensors."""
+    return _Conv3x3zFn.apply(x, w, bias, c)
+
+
 def fixup_act(x, a, b, halo=0):
     """ELU(x + a) + b on [B, H, W, C]; halo = 1: [B, H + 2, W + 2, C] with the circular wrap written."""
     return _ActFn.apply(x, a, b, int(halo))
@@ -405,9 +466,10 @@ def _conv(t, w, bias=None, stride=1, padding=0):
     return to_nhwc(F.conv2d(to_nchw(t), w, bias, stride=stride, padding=padding))
 
 
-def conv_routes(conv1x1="torch", conv_down="torch", conv3x3="torch"):
-    """The three route keywords, checked -> {node: whether its convs are the fused nodes of csrc/conv_train.hip}."""
-    routes = dict(conv1x1=conv1x1, conv_down=conv_down, conv3x3=conv3x3)
+def conv_routes(conv1x1="torch", conv_down="torch", conv3x3="torch", conv3x3z="torch"):
+    """The four route keywords, checked -> {node: whether its convs are the fused nodes of csrc/conv_train.hip and
+    csrc/conv_train_thin.hip}."""
+    routes = dict(conv1x1=conv1x1, conv_down=conv_down, conv3x3=conv3x3, conv3x3z=conv3x3z)
     for keyword, value in routes.items():
         if value not in ROUTES:
             raise ValueError(f"{keyword} must be one of {ROUTES}, not {value!r}")
@@ -420,32 +482,37 @@ def _pre_torch(x, a, b):
     return fixup_add(x, b) if a is None else fixup_act(x, a, b)
 
 
-# node -> (the fused node, the torch route).  conv3x3's: the activation writes the wrap, the conv pads nothing.
+# node -> (the fused node, the torch route).  conv3x3's: the activation writes the wrap, the conv pads nothing.  conv3x3z's: the
+# conv pads zeros behind x + b, and takes the conv's bias (its pre-op is never an activation: a is None).
 _NODES = {"conv1x1": (conv1x1, lambda x, a, b, w: _conv(_pre_torch(x, a, b), w)),
           "conv_down": (conv_down, lambda x, a, b, w: _conv(_pre_torch(x, a, b), w, stride=2)),
-          "conv3x3": (conv3x3, lambda x, a, b, w: _conv(fixup_act(x, a, b, halo=1), w))}
+          "conv3x3": (conv3x3, lambda x, a, b, w: _conv(fixup_act(x, a, b, halo=1), w)),
+          "conv3x3z": (lambda x, w, a, b, bias=None: conv3x3z(x, w, bias, b),
+                       lambda x, a, b, w, bias=None: _conv(_pre_torch(x, a, b), w, bias, padding=1))}
 
 
-def _pre_conv(node, hip, x, a, b, w):
+def _pre_conv(node, hip, x, a, b, w, bias=None):
     """The conv of a node of ops.L.CONV_TRAIN on ELU(x + a) + b (a None: x + b; both None: x).  hip[node]: one fused node where
     the kernels take the shape (the node's kernel size, H and W multiples of its stride, their channel rule); any other
-    shape takes the torch route and is counted."""
+    shape takes the torch route and is counted.  bias: the conv's own, for a node with a bias seat."""
     fused, torch_route = _NODES[node]
+    extra = () if bias is None else (bias,)
     if hip[node]:
-        _, k, stride, _ = ops.L.CONV_TRAIN[node]
+        _, k, stride, _, _ = ops.L.CONV_TRAIN[node]
         if (tuple(w.shape[2:]) == (k, k) and x.shape[1] % stride == 0 and x.shape[2] % stride == 0
                 and getattr(ops, node + "_train_supported")(w.shape[1], w.shape[0])):
             stats[node + "_hip"] += 1
-            return fused(x, w, a, b)
+            return fused(x, w, a, b, *extra)
         stats[node + "_fallbacks"] += 1
-    return torch_route(x, a, b, w)
+    return torch_route(x, a, b, w, *extra)
 
 
 def block_forward_nhwc(block, x, **routes):
     """conv_block.py:196-216 on [B, H, W, C] with a graph: the fused ops around F.conv2d.  routes: the keywords of conv_routes,
     each "torch" by default.  conv1x1 = "hip": every 1x1, stride-1 conv the kernels support is one node with the op in front
     of it (csrc/conv_train.hip); conv_down = "hip": so is each 2x2, stride-2 conv of a 'down' block; conv3x3 = "hip": so is
-    the circular 3x3 of a 'same' or 'out' block; "torch": F.conv2d."""
+    the circular 3x3 of a 'same' or 'out' block; conv3x3z = "hip": so is the zero-padded 3x3 skip_conv of an 'out' block
+    (csrc/conv_train_thin.hip); "torch": F.conv2d."""
     if not isinstance(block, PreActFixupResBlock):
         raise NotImplementedError(f"training is implemented for Fixup blocks only (no MBConv / BatchNorm training), not "
                                   f"{type(block).__name__}")
@@ -469,7 +536,7 @@ def block_forward_nhwc(block, x, **routes):
     elif mode == "same":
         skip = _pre_conv("conv1x1", hip, x, None, block.bias1c, w)
     else:                                               # out2d: 3x3, zero padding
-        skip = _conv(fixup_add(x, block.bias1c), w, padding=1)
+        skip = _pre_conv("conv3x3z", hip, x, None, block.bias1c, w)
     return fixup_out(t, skip, block.scale, block.bias4, block.bias1d)
 
 
@@ -480,7 +547,7 @@ def _compute_dtype(x):
 
 def block_forward(block, x, **routes):
     """One PreActFixupResBlock mirror on an NCHW-shaped tensor (channels_last preferred: no copy) -> NCHW-shaped, with a graph.
-    routes: conv1x1 / conv_down / conv3x3, as in block_forward_nhwc."""
+    routes: conv1x1 / conv_down / conv3x3 / conv3x3z, as in block_forward_nhwc."""
     return to_nchw(block_forward_nhwc(block, to_nhwc(_compute_dtype(x)), **routes))
 
 
@@ -539,13 +606,14 @@ def _quantize_torch(vq, inputs):
 
 def forward_train(model, x, return_indices=False, **routes):
     """VQAE.forward (vq_ae/model.py:41-48) over a vqae_amd.model.VQAE mirror, with a graph: -> (out, (vq_loss,)), out NCHW-shaped
-    (channels_last).  The stems are F.conv2d, the blocks block_forward, the quantiser its own trainable mirror (its EMA buffers
-    are updated in training mode, as in the reference).  routes: conv1x1 / conv_down / conv3x3 = "torch" (default) | "hip", the
-    routes of the blocks' 1x1, 2x2 stride-2 and circular 3x3 convs (block_forward_nhwc)."""
-    conv_routes(**routes)
+    (channels_last).  The stems are F.conv2d (conv3x3z = "hip": the fused zero-padded node, where the kernels take the stem's
+    width), the blocks block_forward, the quantiser its own trainable mirror (its EMA buffers are updated in training mode, as in
+    the reference).  routes: conv1x1 / conv_down / conv3x3 / conv3x3z = "torch" (default) | "hip", the routes of the blocks' 1x1,
+    2x2 stride-2, circular 3x3 and zero-padded 3x3 convs (block_forward_nhwc)."""
+    hip = conv_routes(**routes)
     enc, dec = model.encoder, model.decoder
     h = to_nhwc(_compute_dtype(x))
-    h = _conv(h, enc.in_stem.weight, enc.in_stem.bias, padding=1)
+    h = _pre_conv("conv3x3z", hip, h, None, None, enc.in_stem.weight, enc.in_stem.bias)
     for level in enc.down_layers[0].layers:
         for blk in level.layers:
             h = block_forward_nhwc(blk, h, **routes)
@@ -559,7 +627,7 @@ def forward_train(model, x, return_indices=False, **routes):
     for level in dec.up_layers[0].layers:
         for blk in level.layers:
             h = block_forward_nhwc(blk, h, **routes)
-    out = to_nchw(_conv(h, dec.out_stem.weight, dec.out_stem.bias, padding=1))
+    out = to_nchw(_pre_conv("conv3x3z", hip, h, None, None, dec.out_stem.weight, dec.out_stem.bias))
     if return_indices:
         return out, (vq_loss,), (idx,)
     return out, (vq_loss,)
@@ -567,6 +635,6 @@ def forward_train(model, x, return_indices=False, **routes):
 
 def step(model, batch, loss_f=F.huber_loss, **routes):
     """VQAE.step (vq_ae/model.py:114-122): -> (out, recon_loss, (vq_loss,)); the caller backpropagates recon_loss + sum(vq_loss).
-    routes: conv1x1 / conv_down / conv3x3, as in forward_train."""
+    routes: conv1x1 / conv_down / conv3x3 / conv3x3z, as in forward_train."""
     out, encoding_loss = forward_train(model, batch, **routes)
     return out, loss_f(input=out, target=batch), encoding_loss

@@ -891,6 +891,44 @@ int vqae_conv3x3_train_backward_f32(const float* g_dev, const float* x_dev, cons
                                     void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * 6f. Trainable zero-padded 3x3 convolutions with a 3-channel side: encoder.in_stem (model.py:198: 3 -> C0, bias),
+ *     decoder.out_stem (model.py:291: C0 -> 3, bias) and the skip_conv of a Fixup 'out' block (conv_block.py:211 with
+ *     conf/model/layers/conv_layer/out2d.yaml: kernel 3, stride 1, padding 1, padding_mode zeros, no bias), fp32, NHWC:
+ *         x [batch][h][w][cin];  y [batch][h][w][cout];  m = batch h w rows
+ *         y[b][i][j][co] = bias[co] + sum_{kh,kw,ci} uz[b][i + kh - 1][j + kw - 1][ci] w[co][ci][kh][kw]
+ *         pre = 0: u = x      pre = 1: u = x + *b;      uz = u inside the image and 0 OUTSIDE (the padding follows the pre-op,
+ *         as in F.conv2d(x + c, w, padding=1));  pre = 2 has no caller at this seat: VQAE_ERR_UNSUPPORTED
+ *         w_layout 0: w [cout][cin][3][3] (a contiguous torch weight)    1: w [cout][3][3][cin] (a channels_last one)
+ *     Both layouts are read as they lie (no copy on either side); gradients of w come back in the layout given.  Direct convs on
+ *     the vector ALU.  Grids depend on (batch, h, w, cin, cout) only, no floating-point atomics: bit-identical run to run.
+ *     Supported: exactly one side of 3 channels -- cin = 3 with cout a multiple of 8 in 8 .. 64, or cout = 3 with cin a
+ *     multiple of 8 in 8 .. 256 -- any batch, h, w >= 1 with m < 2^40; tensors 16-byte, the workspace 8-byte aligned.
+ *     Errors, before any HIP call, in this order: batch / h / w < 1, pre outside 0 .. 2, w_layout outside 0 .. 1, null pointers
+ *     -> VQAE_ERR_INVALID; any other cin / cout, pre = 2 -> VQAE_ERR_UNSUPPORTED; m >= 2^40, misaligned pointers ->
+ *     VQAE_ERR_INVALID.
+ * ------------------------------------------------------------------------------------------- */
+int vqae_conv3x3z_train_supported(int cin, int cout);
+/* R: the longest fp32 accumulation run of g_w and g_bias, in rows.  Longer row ranges are added run by run in fp64. */
+int vqae_conv3x3z_train_wgrad_run(void);
+/* Bytes of workspace of the backward (0 for an unsupported shape): P fp64 partials of g_w (27 C doubles each, C the wide side)
+ * and of g_bias (cout each) with P <= 1024 and P 27 C <= 2^21, 1024 rows of the scalar sum: below 16.6 MiB whatever m is. */
+size_t vqae_conv3x3z_train_workspace_bytes(int64_t batch, int h, int w, int cin, int cout);
+/* bias_dev [cout] or NULL.  a_dev is not read (pre < 2); workspace_dev is not used and may be NULL. */
+int vqae_conv3x3z_train_forward_f32(const float* x_dev, const float* a_dev, const float* b_dev, int pre, const float* w_dev,
+                                    const float* bias_dev, int w_layout, int64_t batch, int h, int w, int cin, int cout,
+                                    float* y_dev, void* workspace_dev, void* stream);
+/* From g [batch][h][w][cout] and the forward's x, b, w:
+ *   g_x[b][i][j][ci] = sum_{kh,kw,co} g[b][i - kh + 1][j - kw + 1][co] w[co][ci][kh][kw] over the positions inside the image,
+ *   GATHERED, every element written once by a plain store;   *g_b = sum g_x (pre = 1);   g_a is not written;
+ *   g_w (w's layout) = sum_m g[m][co] uz[b][i + kh - 1][j + kw - 1][ci], u recomputed from x;   g_bias[co] = sum_m g[m][co].
+ * g_x, g_w, g_b, g_bias may each be NULL: what is not asked for is not computed.  g_w, g_bias: fp32 accumulation over runs of at
+ * most R rows, the runs added in fp64 in index order, rounded to fp32 once; g_b in fp64 in a fixed order, rounded once. */
+int vqae_conv3x3z_train_backward_f32(const float* g_dev, const float* x_dev, const float* a_dev, const float* b_dev, int pre,
+                                     const float* w_dev, int w_layout, int64_t batch, int h, int w, int cin, int cout,
+                                     float* g_x_dev, float* g_w_dev, float* g_a_dev, float* g_b_dev, float* g_bias_dev,
+                                     void* workspace_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * 7. Counts of stored code grids -- produces what the reference commits as data under scripts/create_wsi_histograms/
  *    (embedding_idx_histogram_{K}_{split}.npy, histogram_{split}.npy; it ships no program for them) and reads its loss
  *    weights from (conf/model/optional_overrides/loss_f/bce_with_logits_loss_camelyon16_embeddings.yaml: "values taken

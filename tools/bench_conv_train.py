@@ -19,6 +19,15 @@ F.conv2d, which is what train.py ran before the keyword existed.  The method is 
               recorded for the same code ("fused" there)
 
     python tools/bench_conv_train.py --node conv3x3 [--rounds 9 --reps 10 --step-batch 16 --launches --out profiles/conv3x3_train.json]
+
+--node conv3x3z times the zero-padded 3x3 node with a 3-channel side of csrc/conv_train_thin.hip (the stems, the skip_conv of an
+'out' block) in the same way, with what differs stated in its record: the torch route is F.conv2d(x, w, bias, padding=1) on the
+NCHW-shaped view and aten.convolution_backward, the layout copy of its result included (train._conv); in_stem shapes time the
+backward without a data gradient (the batch needs none) on both sides; there is no block record (no shipped config has an 'out'
+block); the step is cfg B under all four keywords "hip", under the other three alone, and under all "torch", with peak memory
+and, with --launches, kernel launches per step.
+
+    python tools/bench_conv_train.py --node conv3x3z [--launches --out profiles/conv3x3z_train.json]
 """
 import argparse
 import csv
@@ -64,6 +73,11 @@ NODES = {
                     ops=[("B_trunk_128", 64, 32, 128, 128, 2), ("hires_same_16", 16, 256, 16, 16, 2), ("C_trunk_256", 64, 32, 256, 256, 2)],
                     blocks={"block": ("same", 64, 128, 128, 32)},
                     hip=KEYWORDS, block_key=lambda B, ci, co, H: {"batch_C_H": [B, ci, H], "mode": "same"}),
+    # ops: (name, batch, H = W, Ci, Co, whether the input needs a gradient); its own record (bench_ops_z, bench_step_z)
+    "conv3x3z": dict(k=3, stride=1, halo=0,
+                     ops=[("in_stem_3_16_256", 16, 256, 3, 16, False), ("out_stem_16_3_256", 16, 256, 16, 3, True),
+                          ("in_stem_3_8_512", 8, 512, 3, 8, False), ("out_stem_8_3_512", 8, 512, 8, 3, True)],
+                     blocks={}, hip=KEYWORDS + ("conv3x3z",), block_key=None),
 }
 
 
@@ -92,6 +106,115 @@ def node_counts(node, fn):
     train.stats.update({node + "_hip": 0, node + "_fallbacks": 0})
     fn()
     return {"hip_nodes": train.stats[node + "_hip"], "hip_fallbacks": train.stats[node + "_fallbacks"]}
+
+
+def bench_ops_z(reps, rounds):
+    out = {}
+    for (name, B, H, ci, co, need_x) in NODES["conv3x3z"]["ops"]:
+        gen = torch.Generator().manual_seed(ci + co)
+        x, g = torch.randn(B, H, H, ci, generator=gen).cuda(), torch.randn(B, H, H, co, generator=gen).cuda()
+        w = (torch.randn(co, ci, 3, 3, generator=gen) / (9 * ci) ** 0.5).cuda().contiguous(memory_format=torch.channels_last)
+        bias = torch.randn(co, generator=gen).cuda()
+        xn, gn = x.permute(0, 3, 1, 2), g.permute(0, 3, 1, 2)
+        m = B * H * H
+
+        def torch_fwd():
+            return train.to_nhwc(F.conv2d(xn, w, bias, padding=1))
+
+        def torch_bwd():
+            g_x, g_w, g_bias = torch.ops.aten.convolution_backward(gn, xn, w, [co], [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
+                                                                   [need_x, True, True])
+            return (train.to_nhwc(g_x) if need_x else None), g_w, g_bias
+
+        byts = {"fwd": 4 * (ci + co) * m, "bwd": 4 * (co + ci + (ci if need_x else 0)) * m}
+        fns = {"hip_fwd": lambda: ops.conv3x3z_train_forward(x, w, bias), "torch_fwd": torch_fwd,
+               "hip_bwd": lambda: ops.conv3x3z_train_backward(g, x, w, None, need_x, True, True), "torch_bwd": torch_bwd,
+               "hip_bwd_weight_only": lambda: ops.conv3x3z_train_backward(g, x, w, None, False, True, True)}
+        if need_x:
+            fns["hip_bwd_data_only"] = lambda: ops.conv3x3z_train_backward(g, x, w, None, True, False, False)
+        for d, n in byts.items():
+            src, dst = torch.empty(n // 8, device="cuda"), torch.empty(n // 8, device="cuda")
+            fns["copy_" + d] = (lambda src=src, dst=dst: dst.copy_(src))
+        us = alternate(fns, reps, rounds, 3)
+        res = {"batch": B, "H": H, "Ci": ci, "Co": co, "pre": 0, "bias": True, "data_gradient": bool(need_x), "rows": m, "w_layout": 1,
+               "us": us, "algorithmic_bytes": byts}
+        for d in ("fwd", "bwd"):
+            hip, tor, cp = (us[f"{side}_{d}"]["median"] for side in ("hip", "torch", "copy"))
+            res[d] = {"torch_over_hip": round(tor / hip, 3), "hip_over_copy": round(hip / cp, 3), "torch_over_copy": round(tor / cp, 3)}
+        out[name] = res
+        print(json.dumps({name: res}), flush=True)
+        del x, g, xn, gn, fns
+        torch.cuda.empty_cache()
+    return out
+
+
+def step_model_z(batch):
+    from oracle import vqae_oracle as O
+    from vqae_amd.model import VQAE
+    spec = O.SPECS["B"]
+    model = VQAE.from_spec(vqae_amd.SPECS["B"])
+    p = O.make_params(spec, 0)
+    vq = "encoder.vq_layers.0."
+    p.update({vq + "embed_avg": p[vq + "embed"].clone(), vq + "cluster_size": torch.ones(spec.num_embeddings),
+              vq + "first_pass": torch.as_tensor(0)})
+    model.load_state_dict(p)
+    model = model.cuda().train()
+    x = O.make_patches(batch, 256, 0).cuda().contiguous(memory_format=torch.channels_last)
+
+    def run(routes):
+        out, recon, (vq_loss,) = train.step(model, x, **routes)
+        (recon + vq_loss).backward()
+        for q in model.parameters():
+            q.grad = None
+
+    three = dict.fromkeys(KEYWORDS, "hip")
+    return {"all_hip": lambda: run({**three, "conv3x3z": "hip"}), "three_hip_conv3x3z_torch": lambda: run(three), "all_torch": lambda: run({})}
+
+
+def bench_step_z(batch, reps, rounds):
+    sides = step_model_z(batch)
+    res = {"spec": "B", "batch": batch, "patch": 256, "reps": reps, "rounds": rounds, "ms": alternate(sides, reps, rounds, 2, 1e-3),
+           "max_memory_allocated_GiB": {k: round(peak_of(fn, 2 ** 30, above_allocated=False), 2) for k, fn in sides.items()}}
+    res.update(node_counts("conv3x3z", sides["all_hip"]))
+    base = res["ms"]["all_torch"]["median"]
+    res["ratio_of_all_torch_over"] = {k: round(base / v["median"], 3) for k, v in res["ms"].items()}
+    return res
+
+
+def count_step_launches(side, batch, iters, workdir):
+    d = os.path.join(workdir, f"{side}_{iters}")
+    subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", sys.executable,
+                    os.path.abspath(__file__), "--node", "conv3x3z", "--child", side, "--child-iters", str(iters), "--step-batch",
+                    str(batch)], check=True, timeout=300, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    rows = 0
+    for path in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
+        with open(path) as f:
+            rows += sum(1 for _ in csv.reader(f)) - 1
+    return rows
+
+
+def main_z(args):
+    if args.child:
+        fn = step_model_z(args.step_batch)[args.child]
+        for _ in range(args.child_iters):
+            fn()
+        return torch.cuda.synchronize()
+    out = {"device": torch.cuda.get_device_name(0), "wgrad_run_rows": ops.conv3x3z_train_wgrad_run(), "ops": None, "step": None,
+           "launches_per_step_fwd_bwd": None}
+    out["ops"] = bench_ops_z(args.reps, args.rounds)
+    if not args.no_step:
+        out["step"] = bench_step_z(args.step_batch, args.step_reps, args.step_rounds)
+        print(json.dumps({"step": out["step"]}), flush=True)
+    if args.launches:
+        with tempfile.TemporaryDirectory() as wd:
+            out["launches_per_step_fwd_bwd"] = {
+                s: (count_step_launches(s, 2, 4, wd) - count_step_launches(s, 2, 2, wd)) / 2 for s in ("all_hip", "all_torch")}
+        print(json.dumps({"launches_per_step_fwd_bwd": out["launches_per_step_fwd_bwd"]}), flush=True)
+    path = args.out or os.path.join(ROOT, "profiles", "conv3x3z_train.json")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
 
 
 def bench_ops(node, reps, rounds):
@@ -254,9 +377,11 @@ def main():
     ap.add_argument("--child-iters", type=int, default=5)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    assert torch.cuda.is_available(), "bench_conv_train needs a GPU: there is no CPU timing"
+    if args.node == "conv3x3z":
+        return main_z(args)
     node, blocks = args.node, NODES[args.node]["blocks"]
     first = next(iter(blocks))
-    assert torch.cuda.is_available(), "bench_conv_train needs a GPU: there is no CPU timing"
     if args.child:
         return child(node, args.child, args.child_shape or first, args.child_iters)
     many = list(blocks) != ["block"]

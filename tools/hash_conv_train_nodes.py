@@ -3,7 +3,9 @@
 inputs, at the op shapes of profiles/conv_train_refactor.json and profiles/conv3x3_train.json and at three edge shapes of each
 node's GPU test (M = 33, 129 and the shape of two accumulation runs, Ci, Co = 24, 40): the order of every sum in those nodes is
 part of their recorded results, so a change to the shared kernels or to the host code in front of them must leave these digests
-as they were.  Raw ctypes on the library file given, so the same script runs on another build of it:
+as they were.  Where the library has it, the conv3x3z node of csrc/conv_train_thin.hip follows (y, g_x, g_w, g_b = g_c, g_bias at
+the op shapes of profiles/conv3x3z_train.json and the same edge shapes, Ci, Co = 3, 16 and 16, 3); a build without the node
+gives the first three nodes' list alone.  Raw ctypes on the library file given, so the same script runs on another build of it:
 
     python tools/hash_conv_train_nodes.py LIBVQAE_HIP.so OUT.json
 """
@@ -67,5 +69,39 @@ for node, (_, _, image) in NODES.items():
     for (tag, B, OH, OW) in EDGES:
         for layout in ((0, 1) if image else (0,)):
             run(node, tag, B, OH, OW, 24, 40, 2, layout)
+
+
+def run_z(tag, B, H, W, ci, co, pre, layout):
+    """one forward and backward of the zero-padded 3x3 node with a 3-channel side (bias behind w, g_bias behind g_b)"""
+    gen = torch.Generator().manual_seed(ci + co)
+    x, g = torch.randn(B, H, W, ci, generator=gen).cuda(), torch.randn(B, H, W, co, generator=gen).cuda()
+    w, bias = (torch.randn(co, ci, 3, 3, generator=gen) / (9 * ci) ** 0.5).cuda(), torch.randn(co, generator=gen).cuda()
+    if layout:
+        w = w.contiguous(memory_format=torch.channels_last)
+    y, gx, gw, gbias = torch.empty_like(g), torch.empty_like(x), torch.empty_like(w), torch.empty_like(bias)
+    gb = torch.zeros(1, device="cuda")
+    ws = torch.empty(lib.vqae_conv3x3z_train_workspace_bytes(B, H, W, ci, co), dtype=torch.uint8, device="cuda")
+    assert lib.vqae_conv3x3z_train_forward_f32(p(x), None, p(b), pre, p(w), p(bias), layout, B, H, W, ci, co, p(y), None, None) == 0
+    assert lib.vqae_conv3x3z_train_backward_f32(p(g), p(x), None, p(b), pre, p(w), layout, B, H, W, ci, co, p(gx), p(gw), None, p(gb),
+                                                p(gbias), p(ws), None) == 0
+    torch.cuda.synchronize()
+    out.append({"node": "conv3x3z", "shape": tag, "BOHOW": [B, H, W], "Ci": ci, "Co": co, "pre": pre, "w_layout": layout, "y": sha(y),
+                "g_x": sha(gx), "g_w": sha(gw.as_strided((gw.numel(),), (1,))), "g_b": sha(gb), "g_bias": sha(gbias)})
+
+
+if hasattr(lib, "vqae_conv3x3z_train_forward_f32"):
+    geo = [c_int64, c_int, c_int]
+    lib.vqae_conv3x3z_train_workspace_bytes.restype = c_size_t
+    lib.vqae_conv3x3z_train_workspace_bytes.argtypes = geo + [c_int, c_int]
+    lib.vqae_conv3x3z_train_forward_f32.argtypes = [V, V, V, c_int, V, V, c_int] + geo + [c_int, c_int, V, V, V]
+    lib.vqae_conv3x3z_train_backward_f32.argtypes = [V, V, V, V, c_int, V, c_int] + geo + [c_int, c_int] + [V] * 7
+    for (name, B, H, ci, co, pre) in [("in_stem_16", 16, 256, 3, 16, 0), ("out_stem_16", 16, 256, 16, 3, 0), ("in_stem_8", 8, 512, 3, 8, 0),
+                                      ("out_stem_8", 8, 512, 8, 3, 0)]:
+        for layout in (0, 1):
+            run_z(name, B, H, H, ci, co, pre, layout)
+    for (tag, B, H, W) in EDGES:
+        for layout in (0, 1):
+            for ci, co in ((3, 16), (16, 3)):
+                run_z(tag, B, H, W, ci, co, 1, layout)
 json.dump(out, open(sys.argv[2], "w"), indent=1)
 print("hashed", len(out), "cases with", sys.argv[1])
