@@ -105,7 +105,7 @@ struct Block : vqae::FixupScalars {
     void *wU43s = nullptr, *w1s = nullptr, *w3s = nullptr;   // the same and conv1 / conv3 as three bf16 planes (split form, C = 128)
     float* wU = nullptr;                  // Winograd-domain conv2 weights [16][C][C] (fp32 trunk blocks, C = 64 / 128, conv_wino.hip)
     float *w1f = nullptr, *w3f = nullptr; // conv1 / conv3 weights in MFMA fragment order for the fused tails (both trunk kernels)
-    float *w2f = nullptr, *wskf = nullptr;// 'down' blocks: conv2 / skip_conv in fragment order too (down_fused.hip)
+    float *w2f = nullptr, *wskf = nullptr;// 'down' blocks: conv2 / skip_conv in fragment order too (down_fused.hip); fp32 'up': w1f, w2f, wskf (up_fused.hip)
     // 16-bit modes: the convs as 16-bit MFMA fragments for the one kernel family that the block's mode and width select (load_block):
     // 'same' C >= 16: trunk16.hip / same16_16; 'same' C = 8: w2h / w3h for same8_16.hip; 'down': down16.hip; 'up': head16 (w1h) + up16.hip
     void *w1h = nullptr, *w2h = nullptr, *w3h = nullptr, *wskh = nullptr;
@@ -149,6 +149,7 @@ struct vqae_handle {
     bool fuse_down16 = true;               // ... on the 16-bit MFMA in the autocast modes (down16.hip)
     bool fuse_up16 = true;                 // 'up' blocks in the autocast modes: head16 + one launch (up16.hip)
     bool fuse_up_tail = true;              // fp32 up blocks at the stem-side levels: resize + ELU + conv3 + skip in one launch
+    bool fuse_up_head = true;              // fp32 up blocks, convs before the resize: skip_conv + conv1 + conv2 in one launch (up_fused.hip)
     bool use_wino = true;                  // fp32 trunk blocks (C = 128 on a 32-wide grid, C = 64 on a 64-wide one): Winograd F(2x2,3x3) conv2
     bool w43_split = true;                 // F(4x4,3x3) trunk at C = 128: GEMMs on the bf16 MFMA with 3-way split operands (conv_wino43.hip)
     void* idx_scratch = nullptr;           // indices nobody asked for (vqae_forward with idx == NULL)
@@ -261,6 +262,7 @@ int load_block(vqae_handle* h, const TensorMap& tm, const std::string& pre, int 
     const bool down = mode == MODE_DOWN && cout == 2 * cin && h->fuse_down && vqae::down_block_channels(cin);   // any dtype
     const bool down16 = mode == MODE_DOWN && cout == 2 * cin && !f32 && h->fuse_down16 && vqae::down16_channels(cin);
     const bool up16 = mode == MODE_UP && cin == 2 * cout && !f32 && h->fuse_up16 && vqae::up16_channels(cin);
+    const bool up_head = mode == MODE_UP && cin == 2 * cout && b->br == cin && f32 && h->up_conv_first && h->fuse_up_head && vqae::up_head_channels(cin);
 
     const int k2 = mode == MODE_SAME ? 3 : (mode == MODE_DOWN ? 2 : 1);
     const float* p;
@@ -307,6 +309,8 @@ int load_block(vqae_handle* h, const TensorMap& tm, const std::string& pre, int 
     if (same8 && ((rc = pack_r16(b->w2, 8, 72, &b->w2h)) || (rc = pack_r16(b->w3, 8, 8, &b->w3h)))) return rc;
     if (down && ((rc = frag_rect(b->w1, cin, &b->w1f)) || (rc = frag_rect(b->w2, 4 * cout, &b->w2f)) ||
                  (rc = frag_rect(b->w3, cout, &b->w3f)) || (rc = frag_rect(b->wskip, 4 * cin, &b->wskf)))) return rc;
+    if (up_head && ((rc = frag(b->w1, cin, cin, 8, &b->w1f)) || (rc = frag(b->w2, cin, cin, 8, &b->w2f)) ||
+                    (rc = frag(b->wskip, std::max(cout, 32), cin, 8, &b->wskf)))) return rc;   // packed rows past cout are zero
     if (down16 && ((rc = pack_r16(b->w1, cout, cin, &b->w1h)) || (rc = pack_r16(b->w2, cout, 4 * cout, &b->w2h)) ||
                    (rc = pack_r16(b->w3, cout, cout, &b->w3h)) || (rc = pack_r16(b->wskip, cout, 4 * cin, &b->wskh)))) return rc;
     if (up16 && ((rc = pack_t16(b->w1, 1, &b->w1h)) || (rc = pack_r16(b->w2, cin, cin, &b->w2h)) ||
@@ -484,8 +488,9 @@ enum Route {
     R_FIXUP_FUSED,                  // high-resolution levels: the whole block in one launch (fixup_fused.hip)
     R_SAME,                         // three generic conv launches
     R_DOWN16, R_DOWN_FUSED, R_DOWN, // 'down': one launch on the 16-bit MFMA (down16.hip) / on the fp32 engine (down_fused.hip) / four generic
-    R_UP_CONV_FIRST_TAIL,           // fp32 'up', 1x1 convs before the resize; stem-side levels: resizes + ELU + conv3 in one launch
-    R_UP_CONV_FIRST,
+    R_UP_CONV_FIRST_TAIL,           // fp32 'up', 1x1 convs before the resize: skip_conv + conv1 + conv2 in one launch (up_head, C = 32 / 64 / 128;
+                                    // three generic launches otherwise), then at the stem-side levels resizes + ELU + conv3 in one launch (up_tail)
+    R_UP_CONV_FIRST,                // ... at the other levels two resize launches and a generic conv3
     R_UP16,                         // 16-bit 'up': head16 + one launch (up16.hip)
     R_UP                            // generic 'up': resize first
 };
@@ -617,23 +622,25 @@ int run_block(vqae_handle* h, const Block& b, const Block* next, int B, int& H, 
     // <= 1e-5 MSE).  fp32 only: under autocast the 16-bit rounding points would move.
     case R_UP_CONV_FIRST_TAIL:
     case R_UP_CONV_FIRST: {
-        const ConvCall sk = ConvCall(h, B, H, W, b.cin, b.cout, 1, 1, 0, VQAE_PAD_NONE).pre(VQAE_PRE_BIAS, b.b1c, 0.f).bias(b.b1d);
-        const ConvCall c2(h, B, H, W, b.br, b.br, 1, 1, 0, VQAE_PAD_NONE);                // conv2 at low resolution
-        if ((rc = conv(sk, X, b.wskip, nullptr, Q, st))) return rc;                        // skip_conv(inp + b1c) + b1d
-        if (r == R_UP_CONV_FIRST_TAIL) {
-            // stem-side levels: both resizes, the ELU and conv3 in one launch (misc_kernels.hip up_tail_kernel); output in buf[0]
+        // the three convs at the low resolution: skip_conv(inp + b1c) + b1d -> Q, conv2(t1) -> R; one launch (up_fused.hip up_head_kernel)
+        // where the block has the fragment-order weights, bit-identical to the three generic launches
+        if (b.w1f && b.w2f && b.wskf) {
+            if ((rc = vqae::up_head(X, b.w1f, b.w2f, b.wskf, (int64_t)B * H * W, b.cin, b, Q, R, st))) return rc;
+        } else {
+            const ConvCall sk = ConvCall(h, B, H, W, b.cin, b.cout, 1, 1, 0, VQAE_PAD_NONE).pre(VQAE_PRE_BIAS, b.b1c, 0.f).bias(b.b1d);
+            if ((rc = conv(sk, X, b.wskip, nullptr, Q, st))) return rc;
             if ((rc = run_conv1(h, b, B, H, W, X, P, st))) return rc;
-            if ((rc = conv(c2, P, b.w2, nullptr, R, st))) return rc;
+            if ((rc = conv(ConvCall(h, B, H, W, b.br, b.br, 1, 1, 0, VQAE_PAD_NONE), P, b.w2, nullptr, R, st))) return rc;
+        }
+        if (r == R_UP_CONV_FIRST_TAIL) {
+            // stem-side levels: both resizes, the ELU and conv3 in one launch (up_fused.hip up_tail_kernel); output in buf[0]
             if ((rc = vqae::up_tail(R, Q, b.w3, B, H, W, b.br, b.cout, b.b3a, b.b3b, b.scale, b.b4, X, st))) return rc;
             break;
         }
-        if ((rc = vqae_bicubic_up2_f32(Q, B, H, W, b.cout, 0.f, R, st))) return rc;
-        if ((rc = run_conv1(h, b, B, H, W, X, P, st))) return rc;
-        if ((rc = conv(c2, P, b.w2, nullptr, Q, st))) return rc;
-        if ((rc = vqae_bicubic_up2_f32(Q, B, H, W, b.br, 0.f, P, st))) return rc;
+        if ((rc = vqae_bicubic_up2_f32(Q, B, H, W, b.cout, 0.f, X, st))) return rc;        // the input is dead: resized skip -> X
+        if ((rc = vqae_bicubic_up2_f32(R, B, H, W, b.br, 0.f, P, st))) return rc;
         if ((rc = conv(ConvCall(h, B, 2 * H, 2 * W, b.br, b.cout, 1, 1, 0, VQAE_PAD_NONE).pre(VQAE_PRE_BIAS_ELU_BIAS, b.b3a, b.b3b).scale_bias(b.scale, b.b4),
-                       P, b.w3, R, R, st))) return rc;
-        out = R;
+                       P, b.w3, X, X, st))) return rc;                                     // + resized skip, in place; output in buf[0]
         break;
     }
     case R_UP16:
@@ -835,6 +842,7 @@ extern "C" int vqae_create(const vqae_config* cfg, const vqae_tensor* tensors, i
     h->use_wino = vqae::env_int("VQAE_NO_WINOGRAD", 0) == 0;
     h->w43_split = vqae::env_int("VQAE_W43_SPLIT", 1) != 0;
     h->fuse_up_tail = vqae::env_int("VQAE_NO_UP_TAIL_FUSION", 0) == 0;
+    h->fuse_up_head = vqae::env_int("VQAE_NO_UP_HEAD_FUSION", 0) == 0;
     h->fuse_down = vqae::env_int("VQAE_NO_DOWN_FUSION", 0) == 0;
     h->fuse_down16 = vqae::env_int("VQAE_NO_DOWN16", 0) == 0;
     h->fuse_up16 = vqae::env_int("VQAE_NO_UP16", 0) == 0;

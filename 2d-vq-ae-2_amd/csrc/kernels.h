@@ -145,11 +145,20 @@ int istem16(const void* x, int x_kind, const float* mean255, const float* inv_st
 int ostem16(const float* x, const void* wf, const float* bias, int B, int H, int W, int c, float* y, int y_nchw, int dtype,
             hipStream_t stream);
 
-// ---- misc_kernels.hip --------------------------------------------------------------------------
-// Fused tail of an fp32 'up' block: (branch channels, out channels) in {(64, 32), (32, 16), (16, 8)}
+// ---- up_fused.hip (fp32 'up' blocks, convs before the resize) -----------------------------------
+// Head: Q = skip_conv(x + b1c) + b1d and R = conv2(ELU(conv1(ELU(x + b1a) + b1b) + b2a) + b2b) in one launch, bit-identical to the
+// three generic launches; x [M][c] -> q [M][c / 2], r [M][c]; c in {32, 64, 128}, any M; weights in fragment order (frag_weight,
+// k-slice 8): w1f, w2f [c][c], wskf [max(c / 2, 32)][c] with zero rows past c / 2
+bool up_head_channels(int c);
+int up_head(const float* x, const float* w1f, const float* w2f, const float* wskf, int64_t M, int c, const FixupScalars& s,
+            float* q, float* r, hipStream_t stream);
+// Fused tail: both resizes, the ELU and conv3; (branch channels, out channels) in {(64, 32), (32, 16), (16, 8)}, any H, W >= 1
+// q [B][H][W][cb], s [B][H][W][co] -> y [B][2H][2W][co]
 bool up_tail_supported(int cb, int co);
 int up_tail(const float* q, const float* s, const float* w3_packed, int B, int H, int W, int cb, int co, float b3a, float b3b,
             float scale, float b4, float* y, hipStream_t stream);
+
+// ---- misc_kernels.hip --------------------------------------------------------------------------
 // 1x1 / stride 1 or 2x2 / stride 2, no padding, cin == 8, cout % 4 == 0 (VALU kernel at the HBM rate)
 bool conv_small_k_supported(const vqae_conv_args* a);
 int conv_small_k(const vqae_conv_args* a, const float* x, const float* w, const float* bias_vec, const float* residual,

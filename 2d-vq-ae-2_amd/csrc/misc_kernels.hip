@@ -170,150 +170,6 @@ void bicubic_up2_kernel(const float4* __restrict__ x, int B, int H, int W, int C
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// Tail of an 'up' Fixup block at the stem-side levels, fused (fp32, conv-before-resize order of handle.hip):
-//   out = conv3(ELU(bicubic_x2(q) + b3a) + b3b) * scale + b4 + bicubic_x2(s)
-// q [B][H][W][CB] = branch_conv2 output at the low resolution, s [B][H][W][CO] = skip_conv output, out [B][2H][2W][CO].
-// Unfused this is two resize launches that write 4x-larger tensors and a 1x1 conv that reads them back (8 GB per call
-// at 256x256x32 for a batch of 256).  A workgroup owns 2 x 16 resize blocks = 4 x 32 output pixels:
-//   phase 1  one (block, channel group) item per thread and step: the shared 4x4 input window of the block's 2x2 outputs
-//            (as bicubic_up2_kernel) -> resized values, ELU'd for the branch -> LDS
-//   phase 2  thread = (pixel, half of the output channels): the CB x CO conv3 from LDS (weights: wave-uniform broadcast
-//            reads), + scale / bias4 / resized skip, 128-bit stores.
-// Few registers and 31 KB of LDS per workgroup keep 5 workgroups per CU in flight, which hides the load latency that
-// bound the one-thread-per-block form (1.87 ms).
-// ------------------------------------------------------------------------------------------------
-template <int CB, int CO>
-__global__ __launch_bounds__(256)
-void up_tail_kernel(const float4* __restrict__ q, const float4* __restrict__ sk, const float* __restrict__ w3, int B, int H,
-                    int W, int tiles_x, int tiles_y, float b3a, float b3b, float scale, float b4, float* __restrict__ y) {
-    constexpr int LB = CB + 4, LS = CO + 4, GB = CB / 4, GS = CO / 4, NG = GB + GS;
-    constexpr int NTL = (CO + 15) / 16;                                             // 16-channel output tiles (CO = 8: half a tile)
-    static_assert(CB % 16 == 0 && CO % 4 == 0, "conv3 runs on 16x16x4 MFMA tiles");
-    const float w75[4] = {-0.03515625f, 0.26171875f, 0.87890625f, -0.10546875f};   // even outputs (offset .75)
-    const float w25[4] = {-0.10546875f, 0.87890625f, 0.26171875f, -0.03515625f};   // odd outputs  (offset .25)
-    __shared__ __attribute__((aligned(16))) float Tb[128 * LB];                     // ELU'd resized branch [pixel][ci]
-    __shared__ __attribute__((aligned(16))) float Ts[128 * LS];                     // resized skip [pixel][co]
-    const int tid = threadIdx.x;
-    // conv3 weights as the MFMA row operand, kept in registers for the whole (persistent) launch: lane (li, q) of n-tile nt, k-slice s
-    // holds w3[co = 16 nt + li][ci = 16 s + 4 q .. + 3] (packed rows are [co][ci])
-    float4 w3r[NTL][CB / 16];
-#pragma unroll
-    for (int nt = 0; nt < NTL; ++nt)
-#pragma unroll
-        for (int s_ = 0; s_ < CB / 16; ++s_) {
-            const int co = 16 * nt + (tid & 15);
-            w3r[nt][s_] = co < CO ? *reinterpret_cast<const float4*>(w3 + co * CB + 16 * s_ + 4 * ((tid & 63) >> 4)) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    const int OW = 2 * W, OH = 2 * H;
-    const int n_tiles = B * tiles_x * tiles_y;
-    for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int txi = tile % tiles_x;
-        const int tyi = (tile / tiles_x) % tiles_y;
-        const int64_t b = tile / (tiles_x * tiles_y);
-        const int bi0 = 2 * tyi - 1, bj0 = 16 * txi - 1;                            // first resize block of the tile
-        __syncthreads();                                                           // previous tile's phase 2 is done
-        // ---- phase 1 ------------------------------------------------------------------------------------------------
-        for (int it = tid; it < 32 * NG; it += 256) {
-            const int g = it % NG, blk = it / NG;
-            const int bi = bi0 + (blk >> 4), bj = bj0 + (blk & 15);
-            const bool branch = g < GB;
-            const float4* src = branch ? q : sk;
-            const int C4 = branch ? GB : GS, gg = branch ? g : g - GB;
-            int xs[4], ys[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                int v = bj - 1 + j; xs[j] = v < 0 ? 0 : (v > W - 1 ? W - 1 : v);
-                int u = bi - 1 + j; ys[j] = u < 0 ? 0 : (u > H - 1 ? H - 1 : u);
-            }
-            float4 ho[4], he[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float4* row = src + ((b * H + ys[r]) * W) * C4 + gg;
-                float4 v[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = row[(int64_t)xs[j] * C4];
-                // accumulation steps as fmas (round 3): the resize is this kernel's vector-issue bound (PMC: 401 M vector instructions per
-                // launch against 9.6 M MFMAs) and a * b + c written as two instructions was a third of them; <= 1 fp32 ulp per tap from
-                // the unfused form (the fp32 handle's conv-before-resize order is not bit-comparable with the reference's anyway)
-                ho[r].x = v[0].x * w25[0]; ho[r].y = v[0].y * w25[0]; ho[r].z = v[0].z * w25[0]; ho[r].w = v[0].w * w25[0];
-                he[r].x = v[0].x * w75[0]; he[r].y = v[0].y * w75[0]; he[r].z = v[0].z * w75[0]; he[r].w = v[0].w * w75[0];
-#pragma unroll
-                for (int j = 1; j < 4; ++j) {
-                    ho[r].x = __builtin_fmaf(v[j].x, w25[j], ho[r].x); ho[r].y = __builtin_fmaf(v[j].y, w25[j], ho[r].y);
-                    ho[r].z = __builtin_fmaf(v[j].z, w25[j], ho[r].z); ho[r].w = __builtin_fmaf(v[j].w, w25[j], ho[r].w);
-                    he[r].x = __builtin_fmaf(v[j].x, w75[j], he[r].x); he[r].y = __builtin_fmaf(v[j].y, w75[j], he[r].y);
-                    he[r].z = __builtin_fmaf(v[j].z, w75[j], he[r].z); he[r].w = __builtin_fmaf(v[j].w, w75[j], he[r].w);
-                }
-            }
-#pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                const float* wy = a == 0 ? w25 : w75;
-#pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    const float4* in = c == 0 ? ho : he;
-                    float4 o;
-                    o.x = in[0].x * wy[0]; o.y = in[0].y * wy[0]; o.z = in[0].z * wy[0]; o.w = in[0].w * wy[0];
-#pragma unroll
-                    for (int r = 1; r < 4; ++r) {
-                        o.x = __builtin_fmaf(in[r].x, wy[r], o.x); o.y = __builtin_fmaf(in[r].y, wy[r], o.y);
-                        o.z = __builtin_fmaf(in[r].z, wy[r], o.z); o.w = __builtin_fmaf(in[r].w, wy[r], o.w);
-                    }
-                    const int px = (2 * (blk >> 4) + a) * 32 + 2 * (blk & 15) + c;   // pixel of the 4 x 32 tile
-                    if (branch) {
-                        o.x = vqae::elu_act(o.x + b3a) + b3b; o.y = vqae::elu_act(o.y + b3a) + b3b;
-                        o.z = vqae::elu_act(o.z + b3a) + b3b; o.w = vqae::elu_act(o.w + b3a) + b3b;
-                        *reinterpret_cast<float4*>(Tb + px * LB + 4 * gg) = o;
-                    } else {
-                        *reinterpret_cast<float4*>(Ts + px * LS + 4 * gg) = o;
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        // ---- phase 2: conv3 on the fp32 MFMA (round 3; it was CB x CO / 2 broadcast FMAs per thread) ------------------------------------
-        // v_mfma_f32_16x16x4_f32 with the weights as the row operand: lane (li, q) feeds Tb[pixel li][16 s + 4 q ..] and receives
-        // D[4 q + r][li] = 4 consecutive output channels of its pixel -> 16-byte skip read and store.  A wave owns 2 groups of 16 pixels.
-        {
-            const int lane = tid & 63, wv = tid >> 6;
-            const int li = lane & 15, q = lane >> 4;
-#pragma unroll
-            for (int gg = 0; gg < 2; ++gg) {
-                const int px = 32 * wv + 16 * gg + li;
-                const int oy = 2 * bi0 + 1 + (px >> 5), ox = 2 * bj0 + 1 + (px & 31);
-                float4 tb[CB / 16];
-#pragma unroll
-                for (int s_ = 0; s_ < CB / 16; ++s_) tb[s_] = *reinterpret_cast<const float4*>(Tb + px * LB + 16 * s_ + 4 * q);
-#pragma unroll
-                for (int nt = 0; nt < NTL; ++nt) {
-                    typedef float f32x4_t __attribute__((ext_vector_type(4)));
-                    f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int s_ = 0; s_ < CB / 16; ++s_) {
-                        const float4 wv4 = w3r[nt][s_];
-                        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wv4.x, tb[s_].x, acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wv4.y, tb[s_].y, acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wv4.z, tb[s_].z, acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wv4.w, tb[s_].w, acc, 0, 0, 0);
-                    }
-                    if (oy >= 0 && oy < OH && ox >= 0 && ox < OW && 16 * nt + 4 * q < CO) {
-                        const float4 sp = *reinterpret_cast<const float4*>(Ts + px * LS + 16 * nt + 4 * q);
-                        float o[4];
-                        const float sv[4] = {sp.x, sp.y, sp.z, sp.w};
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            float tv = acc[e] * scale;
-                            tv = tv + b4;
-                            o[e] = tv + sv[e];
-                        }
-                        *reinterpret_cast<float4*>(y + ((b * OH + oy) * OW + ox) * CO + 16 * nt + 4 * q) = make_float4(o[0], o[1], o[2], o[3]);
-                    }
-                }
-            }
-        }
-    }
-}
-
 // Batched 2-D transpose: in [B][R][S] -> out [B][S][R]  (NCHW <-> NHWC with R/S = C / H*W).
 __global__ __launch_bounds__(256)
 void transpose_kernel(const float* __restrict__ in, int R, int S, float* __restrict__ out) {
@@ -546,25 +402,6 @@ void conv_small_k_kernel(const SmallK p) {
 }  // namespace
 
 namespace vqae {
-// Fused tail of an 'up' block (up_tail_kernel)
-bool up_tail_supported(int cb, int co) { return (cb == 64 && co == 32) || (cb == 32 && co == 16) || (cb == 16 && co == 8); }
-
-int up_tail(const float* q, const float* s, const float* w3_packed, int B, int H, int W, int cb, int co, float b3a, float b3b,
-            float scale, float b4, float* y, hipStream_t stream) {
-    VQAE_REQUIRE(q && s && w3_packed && y, VQAE_ERR_INVALID, "up_tail: null pointer");
-    VQAE_REQUIRE(up_tail_supported(cb, co), VQAE_ERR_UNSUPPORTED, "up_tail: channels %d -> %d", cb, co);
-    if ((int64_t)B * H * W == 0) return VQAE_OK;
-    const int tiles_x = (int)ceil_div(W + 1, 16), tiles_y = (int)ceil_div(H + 1, 2);      // 2 x 16 resize blocks per tile
-    const int64_t n_tiles = (int64_t)B * tiles_x * tiles_y;
-    VQAE_REQUIRE(n_tiles < (1ll << 31), VQAE_ERR_UNSUPPORTED, "up_tail: too many tiles");
-    const unsigned grid = (unsigned)std::min<int64_t>(n_tiles, 256 * 40);
-    if (cb == 64) up_tail_kernel<64, 32><<<grid, 256, 0, stream>>>((const float4*)q, (const float4*)s, w3_packed, B, H, W, tiles_x, tiles_y, b3a, b3b, scale, b4, y);
-    else if (cb == 32) up_tail_kernel<32, 16><<<grid, 256, 0, stream>>>((const float4*)q, (const float4*)s, w3_packed, B, H, W, tiles_x, tiles_y, b3a, b3b, scale, b4, y);
-    else up_tail_kernel<16, 8><<<grid, 256, 0, stream>>>((const float4*)q, (const float4*)s, w3_packed, B, H, W, tiles_x, tiles_y, b3a, b3b, scale, b4, y);
-    VQAE_LAUNCH_CHECK();
-    return VQAE_OK;
-}
-
 // see conv_small_k_kernel
 bool conv_small_k_supported(const vqae_conv_args* a) {
     return a->cin == 8 && a->pad == 0 && a->ksize == a->stride && (a->ksize == 1 || a->ksize == 2) && a->cout % 4 == 0 &&
