@@ -150,6 +150,7 @@ SYMBOLS = {
     "vqae_block_count": (c_int, [c_void_p, c_int]),
     "vqae_run_blocks": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, POINTER(c_int),
                                 POINTER(c_int), c_void_p]),
+    "vqae_block_route": (c_char_p, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int]),
     "vqae_recon_metrics_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "vqae_recon_metrics_f32": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_float), POINTER(c_float), c_int, c_int, c_int,
                                        c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),

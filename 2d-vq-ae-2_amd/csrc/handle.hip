@@ -495,6 +495,11 @@ enum Route {
     R_UP                            // generic 'up': resize first
 };
 
+// the enum's names, lower-case and without R_, in its order (vqae_block_route)
+const char* const kRouteNames[] = {"same16_16", "trunk16", "wino43_split", "wino43", "wino", "tail", "same8_16", "fixup_fused", "same",
+                                   "down16", "down_fused", "down", "up_conv_first_tail", "up_conv_first", "up16", "up"};
+static_assert(sizeof(kRouteNames) / sizeof(kRouteNames[0]) == R_UP + 1, "one name per Route");
+
 // is `next` another 'same' block of b's width (whose conv1 the trunk tail of b can run)?
 bool same_width_next(const Block& b, const Block* next) {
     return next && next->mode == MODE_SAME && next->cin == b.cin && next->cout == b.cin;
@@ -1074,6 +1079,18 @@ extern "C" int vqae_decode_indices_u8_levels(vqae_handle* h, const void* idx, in
 extern "C" int vqae_block_count(const vqae_handle* h, int side) {
     if (!h) return 0;
     return (int)(side == 0 ? h->enc.size() : h->dec.size());
+}
+
+extern "C" const char* vqae_block_route(const vqae_handle* h, int side, int index, int chained, int batch, int in_h, int in_w) {
+    auto bad = [](const char* what) -> const char* { vqae::fail(VQAE_ERR_INVALID, "vqae_block_route: %s", what); return nullptr; };
+    if (!h) return bad("null handle");
+    if (side != 0 && side != 1) return bad("side");
+    const std::vector<Block>& v = side == 0 ? h->enc : h->dec;
+    if (index < 0 || (size_t)index >= v.size()) return bad("block index");
+    if (batch < 1 || in_h < 1 || in_w < 1) return bad("shape");
+    if (v[index].kind == VQAE_BLOCK_MBCONV) return "mbconv";                       // run_block takes these before any route
+    const Block* next = chained && (size_t)index + 1 < v.size() ? &v[index + 1] : nullptr;
+    return kRouteNames[select_route(h, v[index], next, batch, in_h, in_w)];
 }
 
 extern "C" int vqae_run_blocks(vqae_handle* h, int side, int first, int count, const float* x, int B, int in_h, int in_w,

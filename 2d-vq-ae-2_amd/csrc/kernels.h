@@ -126,7 +126,7 @@ int down16_block(const float* x, const void* w1h, const void* w2h, const void* w
 
 // ---- up16.hip (16-bit modes) -------------------------------------------------------------------
 bool up16_channels(int c);              // the block's input channels: 16, 32, 64, 128
-// ... low-resolution width a multiple of 16
+// ... low-resolution width a multiple of 16, output height a multiple of the tile's rows (4; 2 at c = 128): exactly what up16_block runs
 bool up16_supported(int c, int h, int w, int dtype);
 // x, t1 (trunk16_head, out32): [B][H][W][c] fp32 -> y [B][2H][2W][c / 2] fp32; weights: pack16_weight([c][c]), ([c / 2][c]), ([c / 2][c])
 int up16_block(const float* x, const float* t1, const void* w2h, const void* w3h, const void* wskh, int B, int H, int W, int c,

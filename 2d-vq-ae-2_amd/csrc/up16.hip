@@ -227,7 +227,7 @@ bool up16_channels(int c) { return c == 16 || c == 32 || c == 64 || c == 128; }
 
 bool up16_supported(int c, int h, int w, int dtype) {
     if (dtype != VQAE_DT_BF16 && dtype != VQAE_DT_F16) return false;
-    return up16_channels(c) && h >= 1 && w % 16 == 0;
+    return up16_channels(c) && h >= 1 && w % 16 == 0 && 2 * h % up16_rows(c) == 0;   // whole ROWS x 32 output tiles
 }
 
 int up16_block(const float* x, const float* t1, const void* w2h, const void* w3h, const void* wskh, int B, int H, int W, int c,

@@ -217,6 +217,15 @@ class NativeVQAE:
     def block_count(self, side):
         return int(L.lib().vqae_block_count(self._h, 0 if side in (0, "encoder") else 1))
 
+    def block_route(self, side, index, B, H, W, chained=False):
+        """The name of the kernel route block `index` of the encoder / decoder block list takes on a [B,H,W] input
+        (vqae_block_route: 'trunk16', 'same16_16', 'down16', 'up16', 'up', ...).  chained: the next block of the list
+        runs in the same run_blocks call.  Nothing is launched."""
+        name = L.lib().vqae_block_route(self._h, 0 if side in (0, "encoder") else 1, index, int(bool(chained)), B, H, W)
+        if name is None:
+            raise AssertionError(L.lib().vqae_last_error().decode(errors="replace"))
+        return name.decode()
+
     def run_blocks(self, side, first, count, x_nhwc):
         """Blocks [first, first + count) of the encoder ('encoder' / 0) or decoder ('decoder' / 1) block list on
         x [B,H,W,cin] (NHWC) through the handle's own kernel dispatch -> y [B,H',W',cout] (NHWC).  The block

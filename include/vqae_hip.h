@@ -435,6 +435,13 @@ int vqae_forward(vqae_handle* h, const float* x_dev, int batch, int in_h, int in
 int vqae_block_count(const vqae_handle* h, int side);
 int vqae_run_blocks(vqae_handle* h, int side, int first, int count, const float* x_dev, int batch, int in_h, int in_w,
                     float* y_dev, int* out_h, int* out_w, void* stream);
+/* Which kernel family vqae_run_blocks (and every handle-level call) runs block `index` of that list on, for a
+ * [batch][in_h][in_w] input of the block: the name of the dispatch's route -- "same16_16", "trunk16", "wino43_split",
+ * "wino43", "wino", "tail", "same8_16", "fixup_fused", "same", "down16", "down_fused", "down", "up_conv_first_tail",
+ * "up_conv_first", "up16", "up" ("mbconv" for an MBConv handle) -- as a static string.  chained != 0: the next block of
+ * the list runs in the same call (only then can a route depend on it).  Read-only: launches and allocates nothing.
+ * NULL handle, side not 0 / 1, index outside the list, batch / in_h / in_w < 1 -> NULL, vqae_last_error() says which. */
+const char* vqae_block_route(const vqae_handle* h, int side, int index, int chained, int batch, int in_h, int in_w);
 
 /* Introspection for benchmarks: algorithmic FLOPs (2*MACs) of the conv stacks per patch. */
 double vqae_flops_per_patch(const vqae_handle* h, int in_h, int in_w, int encoder, int decoder);

@@ -55,6 +55,13 @@ def test_error_convention_without_gpu(amd):
         L.check(lib.vqae_vq_code_stats_f32(None, None, 0, 4, 3, 8, one, one, None))
 
 
+def test_block_route_without_a_handle(amd):
+    """vqae_block_route answers a bad argument with NULL and a message, like every other call, before it reads anything."""
+    lib = amd._lib.lib()
+    assert lib.vqae_block_route(None, 0, 0, 0, 1, 8, 8) is None
+    assert b"vqae_block_route" in lib.vqae_last_error()
+
+
 def test_ops_refuse_cpu_tensors(amd):
     import torch
     with pytest.raises(amd._lib.VqaeHipError):

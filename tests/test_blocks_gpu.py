@@ -30,91 +30,10 @@ import numpy as np
 import pytest
 import torch
 
+from block_cases import ULP, autocast_ctx, block_lists, compare, distance_to_exact, exact_block, native_handle, nhwc, oracle_taps
 from conftest import load_golden, record_parity, tap_sample
 
 pytestmark = pytest.mark.gpu
-TDT = {"f32": None, "bf16": torch.bfloat16, "f16": torch.float16}
-ULP = {"bf16": 2.0 ** -8, "f16": 2.0 ** -11}
-_cache = {}
-
-
-def oracle_taps(oracle, name, tag):
-    """Full per-block tensors of the oracle on this machine's CPU, verified against the reference's fixture."""
-    key = (name, tag)
-    if key in _cache:
-        return _cache[key]
-    g = load_golden(f"taps_{name}_{tag}")
-    spec = oracle.SPECS[name]
-    p = oracle.make_params(spec, 0)
-    p["encoder.vq_layers.0.embed"] = torch.from_numpy(g["embed"])
-    x = oracle.make_patches(int(g["batch"]), int(g["size"]), 0)
-    # encoder taps from x; decoder taps from the REFERENCE's indices (q = codebook lookup [+ proj_out]): on another CPU
-    # the 16-bit encoder flips a few near-tie indices, which would change q wholesale and make the decoder taps
-    # incomparable with the fixture.  (embed[idx] differs from the reference's x + (q - x) by <= 1 fp32 ulp.)
-    import contextlib
-    taps = {}
-    with (torch.autocast("cpu", dtype=TDT[tag]) if TDT[tag] is not None else contextlib.nullcontext()):
-        oracle.encoder_forward(x, p, spec, taps)
-        vq = "encoder.vq_layers.0."
-        q = p[vq + "embed"][torch.from_numpy(g["idx"].astype(np.int64))].permute(0, 3, 1, 2).contiguous()
-        if spec.projection_dim > 0:
-            q = torch.nn.functional.conv2d(q, p[vq + "proj_out.weight"], p[vq + "proj_out.bias"])
-        taps["q"] = q
-        taps["out"] = oracle.decoder_forward((q,), p, spec, taps)
-    # the GPU box's CPU may take other oneDNN kernels than the container the fixture was recorded in: allow
-    # summation-order noise (fp32) / isolated 16-bit rounding flips here; bit-exactness is the CPU suite's job
-    for k in g.files:
-        if not k.startswith("tap:"):
-            continue
-        got, ref = tap_sample(taps[k[4:]].float()).numpy(), g[k]
-        scale = max(1.0, float(np.abs(ref).max()))
-        err = np.abs(got - ref)
-        if tag == "f32":
-            assert err.max() <= 1e-5 * scale, (k, err.max())
-        else:                # the taps are cumulative (each block runs on the chain's own previous output): flips add up
-            rms = float(np.sqrt((err.astype(np.float64) ** 2).mean() / (ref.astype(np.float64) ** 2).mean()))
-            assert rms <= 4 * ULP[tag], (k, rms)
-    _cache[key] = (spec, p, x, {k: v.float() for k, v in taps.items() if torch.is_tensor(v)})
-    return _cache[key]
-
-
-def nhwc(t):
-    return t.permute(0, 2, 3, 1).contiguous()
-
-
-def compare(got_nhwc, ref_nchw, tag, n_blocks):
-    got = got_nhwc.permute(0, 3, 1, 2).cpu()
-    err = (got - ref_nchw).abs()
-    scale = max(1.0, float(ref_nchw.abs().max()))
-    mx = float(err.max())
-    frac = float((err > 1e-5 * scale).float().mean())
-    if tag == "f32":
-        ok = mx <= 2e-5 * scale * n_blocks
-    else:
-        ok = frac <= 0.08 * n_blocks and mx <= 3 * ULP[tag] * scale * n_blocks
-    return ok, mx / scale, frac
-
-
-_p64 = {}
-
-
-def exact_block(oracle, p, name, x_nchw, prefix, mode, spec):
-    """The block in fp64 with no rounding points: what the 16-bit evaluations (reference autocast and HIP) approximate."""
-    if name not in _p64:
-        _p64.clear()                                   # one model's fp64 weights at a time
-        _p64[name] = {k: v.double() for k, v in p.items() if torch.is_tensor(v) and v.is_floating_point()}
-    return oracle.conv_block(x_nchw.double(), _p64[name], prefix, mode, spec)
-
-
-def distance_to_exact(got_nhwc, ref_nchw, exact_nchw):
-    """(rms_hip, rms_ref, max_hip, max_ref) of |. - exact| in fp64."""
-    got = got_nhwc.permute(0, 3, 1, 2).cpu().double()
-    eh, er = (got - exact_nchw).abs(), (ref_nchw.double() - exact_nchw).abs()
-    return float((eh ** 2).mean().sqrt()), float((er ** 2).mean().sqrt()), float(eh.max()), float(er.max())
-
-
-def block_lists(oracle, spec):
-    return (("encoder", oracle.encoder_blocks(spec), "stem"), ("decoder", oracle.decoder_blocks(spec), "q"))
 
 
 @pytest.mark.parametrize("tag", ["f32", "bf16", "f16"])
@@ -122,7 +41,7 @@ def block_lists(oracle, spec):
 def test_production_blocks_match_oracle_per_block(amd, oracle, name, tag):
     """Every block alone (count = 1): conv1 launch + fused tail without the next-block conv1, 'down' / 'up' blocks."""
     spec, p, x, taps = oracle_taps(oracle, name, tag)
-    nat = amd.NativeVQAE(amd.SPECS[name], p, compute_dtype=None if tag == "f32" else tag)
+    nat = native_handle(amd, oracle, name, tag)
     worst = (0.0, 0.0, "")
     bad, far = [], []
     worst_ratio = (0.0, 0.0, "")                        # (rms ratio, max ratio, block) of |hip - exact| / |ref16 - exact|
@@ -153,11 +72,6 @@ def test_production_blocks_match_oracle_per_block(amd, oracle, name, tag):
     assert not far, far                                # the HIP block is as close to the exact value as the reference's 16-bit one
 
 
-def autocast_ctx(tag):
-    import contextlib
-    return torch.autocast("cpu", dtype=TDT[tag]) if TDT[tag] is not None else contextlib.nullcontext()
-
-
 @pytest.mark.parametrize("tag", ["f32", "bf16", "f16"])
 @pytest.mark.parametrize("name", ["mid", "mid16", "midA", "midC", "midW"])
 def test_fused_next_conv1_on_identical_inputs(amd, oracle, name, tag):
@@ -166,7 +80,7 @@ def test_fused_next_conv1_on_identical_inputs(amd, oracle, name, tag):
     y2 = blocks[i, i+1] in one run (block i+1 then takes its t1 from block i's fused tail); the oracle evaluates block
     i+1 on the GPU's own y1, so y2 is compared with a reference that saw bit-identical input.  Per-block bars."""
     spec, p, x, taps = oracle_taps(oracle, name, tag)
-    nat = amd.NativeVQAE(amd.SPECS[name], p, compute_dtype=None if tag == "f32" else tag)
+    nat = native_handle(amd, oracle, name, tag)
     bad, worst, n = [], (0.0, 0.0, ""), 0
     for side, blocks, first_in in block_lists(oracle, spec):
         ins = [taps[first_in]] + [taps[b[0]] for b in blocks[:-1]]
@@ -198,7 +112,7 @@ def test_production_block_chains_match_oracle(amd, oracle, name, tag):
     4 ulp16 * sqrt(blocks) * scale, mean |err| <= ulp16 * scale / 2 (a wrong weight / lane gives errors of the order
     of the branch itself, 10-100x more)."""
     spec, p, x, taps = oracle_taps(oracle, name, tag)
-    nat = amd.NativeVQAE(amd.SPECS[name], p, compute_dtype=None if tag == "f32" else tag)
+    nat = native_handle(amd, oracle, name, tag)
     bad, worst, n_runs = [], (0.0, 0.0, ""), 0
     for side, blocks, first_in in block_lists(oracle, spec):
         ins = [taps[first_in]] + [taps[b[0]] for b in blocks[:-1]]
@@ -233,7 +147,7 @@ def test_mid_models_end_to_end_vs_reference(amd, oracle, name, tag):
     """Whole forward of the mid-size models against the reference's recorded indices / output samples."""
     g = load_golden(f"taps_{name}_{tag}")
     spec, p, x, taps = oracle_taps(oracle, name, tag)
-    nat = amd.NativeVQAE(amd.SPECS[name], p, compute_dtype=None if tag == "f32" else tag)
+    nat = native_handle(amd, oracle, name, tag)
     out, idx, loss = nat.forward(x.cuda())
     ref_idx = g["idx"].astype(np.int64)
     agree = float((idx.cpu().numpy() == ref_idx).mean())
