@@ -12,10 +12,13 @@ label grids, no DataLoader), classifier.py (the downstream slide
 classifier on stored code grids: heatmaps and scores), classifier_train.py + optim.py (its training: the fused backward, the
 LAMB / SAM mirrors and the device-resident optimiser step; FusedAdam / FusedAdamW / FusedLamb: the fused multi-tensor step for
 any parameter list), train.py + layers/fixup_train.py (training through the Fixup mirrors: fused HIP forward / backward of
-every non-conv op of a block around torch's conv2d; block_forward, forward_train, step), code_stats.py (exact code / label histograms of stored code grids and
+every non-conv op of a block around torch's conv2d; block_forward, forward_train, step), train_mbconv.py +
+layers/mbconv_train.py (the same for the MBConv mirrors: fused batch-statistic BatchNorm, depthwise conv and SE product),
+code_stats.py (exact code / label histograms of stored code grids and
 the loss weights read off them), dist.py (one-process-per-GPU sharding over RCCL).
 """
-from . import _lib, classifier, classifier_train, code_stats, ingest, ops, optim, reconstruct, spec, train  # noqa: F401
+from . import (_lib, classifier, classifier_train, code_stats, ingest, ops, optim, reconstruct, spec, train,  # noqa: F401
+               train_mbconv)
 from .classifier import CNNClassifier, classify_hdf5, classify_slide  # noqa: F401
 from .classifier_train import (ce_loss_and_grads, collate_random_crop, embeddings_split, loss_and_grads,  # noqa: F401
                                smooth_targets, train_hdf5)

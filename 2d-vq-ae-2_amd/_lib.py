@@ -19,6 +19,7 @@ PAD_NONE, PAD_CIRCULAR, PAD_ZEROS = 0, 1, 2
 PRE_NONE, PRE_BIAS, PRE_BIAS_ELU_BIAS, PRE_CHANNEL_GATE = 0, 1, 2, 3
 ACT_NONE, ACT_ELU, ACT_SILU = 0, 1, 2
 DW_SAME, DW_DOWN, DW_UP = 0, 1, 2
+MBT_ROWS, MBT_FIN_LANES = 256, 64       # VQAE_MBT_ROWS, VQAE_MBT_FIN_LANES: the reduction geometry of csrc/mbconv_train.hip
 BLOCK_FIXUP, BLOCK_MBCONV = 0, 1
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 MAX_PIXEL_LEVEL = 6                     # VQAE_MAX_PIXEL_LEVEL: overview levels 0 .. 6 (vqae_pixels_u8_level)
@@ -198,6 +199,20 @@ SYMBOLS = {
                                             c_void_p, c_void_p]),
     "vqae_bicubic_up2_bias_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "vqae_bicubic_up2_backward_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vqae_bn_act_train_supported": (c_int, [c_int]),
+    "vqae_bn_act_train_workspace_bytes": (c_size_t, [c_int, c_int64, c_int]),
+    # x gamma beta running_mean running_var training momentum eps act batch hw c y mean invstd pool ws stream
+    "vqae_bn_act_train_forward_f32": (c_int, [c_void_p] * 5 + [c_int, c_double, c_double, c_int, c_int, c_int64, c_int]
+                                      + [c_void_p] * 6),
+    # g x mean invstd gamma beta g_pool training act batch hw c g_x g_beta_gamma ws stream
+    "vqae_bn_act_train_backward_f32": (c_int, [c_void_p] * 7 + [c_int, c_int, c_int, c_int64, c_int] + [c_void_p] * 4),
+    "vqae_dwconv_train_supported": (c_int, [c_int, c_int, c_int, c_int]),
+    "vqae_dwconv_train_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "vqae_dwconv_train_forward_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "vqae_dwconv_train_backward_f32": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 4),
+    "vqae_se_scale_workspace_bytes": (c_size_t, [c_int, c_int64, c_int]),
+    "vqae_se_scale_forward_f32": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p]),
+    "vqae_se_scale_backward_f32": (c_int, [c_void_p] * 3 + [c_int, c_int64, c_int] + [c_void_p] * 4),
     "vqae_code_histogram_workspace_bytes": (c_size_t, [c_int, c_int64, c_int, c_int]),
     "vqae_code_histogram": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                     c_void_p, c_void_p]),

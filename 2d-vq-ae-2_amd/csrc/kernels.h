@@ -212,6 +212,11 @@ int vq_write_idx(const int* idx32, int64_t N, void* out, int idx_dtype, hipStrea
 // vqae_bicubic_up2_bias_f32, vqae_bicubic_up2_backward_f32 and their workspace size): C ABI only, include/vqae_hip.h.  The
 // grid and the number of fp64 partial rows are functions of the shape alone (ft_grid there).
 
+// ---- mbconv_train.hip --------------------------------------------------------------------------
+// The training forms of an MBConv block's non-dense ops (vqae_bn_act_train_*, vqae_dwconv_train_*, vqae_se_scale_*): C ABI
+// only, include/vqae_hip.h.  One workgroup reduces VQAE_MBT_ROWS rows; the grid and the number of fp64 partial rows are
+// functions of the shape alone.
+
 // ---- conv_train.hip ----------------------------------------------------------------------------
 // The trainable 1x1, 2x2 stride-2 and circular 3x3 convs: C ABI only, include/vqae_hip.h.  Its two final-sum launches serve
 // conv_train_thin.hip (the zero-padded 3x3 convs with a 3-channel side) as well:

@@ -282,6 +282,119 @@ def bicubic_up2_backward(g, want_bias=True):
     return g_x, g_pb
 
 
+def _ws(n_bytes, dev):
+    return torch.empty(max(int(n_bytes), 8), dtype=torch.uint8, device=dev)
+
+
+def _vec(p):
+    """A [C] parameter or buffer as the kernels read it: dense fp32 in HBM (no copy for an fp32 Parameter)."""
+    _need_gpu(p)
+    return p.detach().float().contiguous()
+
+
+def bn_act_train_supported(c):
+    """Whether csrc/mbconv_train.hip takes c channels (a multiple of 4 up to 1024): one rule for its three nodes."""
+    return bool(L.lib().vqae_bn_act_train_supported(int(c)))
+
+
+def bn_act_train_forward(x, gamma, beta, running_mean, running_var, training, momentum, eps, silu=False, want_pool=False):
+    """BatchNorm2d (+ SiLU) on x [B, H, W, C] -> (y, mean [C], invstd [C] (fp64), pool [B, C] | None).  training: batch statistics, and
+    running_mean / running_var (fp32 device tensors, or None) are updated IN PLACE by the launch that finishes the sums; else
+    the running statistics normalise and nothing is written.  pool[b, c] = sum_hw y.  One row in training mode: ValueError."""
+    _need_gpu(x, gamma, beta)
+    x = x.contiguous()
+    B, H, W, C = x.shape
+    dev = x.device
+    for t in (running_mean, running_var):
+        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()), "running statistics: dense fp32 in HBM"
+    y = torch.empty_like(x)
+    stat = torch.empty((2, C), dtype=torch.float64, device=dev)        # mean, invstd: kept in fp64 for the backward
+    pool = torch.empty((B, C), dtype=torch.float32, device=dev) if want_pool else None
+    ws = _ws(L.lib().vqae_bn_act_train_workspace_bytes(B, H * W, C), dev)
+    L.check(L.lib().vqae_bn_act_train_forward_f32(_p(x), _p(_vec(gamma)), _p(_vec(beta)), _p(running_mean), _p(running_var),
+                                                  int(training), float(momentum), float(eps), int(silu), B, H * W, C, _p(y),
+                                                  _p(stat[0]), _p(stat[1]), _p(pool), _p(ws), _stream()))
+    return y, stat[0], stat[1], pool
+
+
+def bn_act_train_backward(g, x, mean, invstd, gamma, beta, training, silu=False, g_pool=None):
+    """-> (g_x, g_gamma [C], g_beta [C]) from the gradient of y, the forward's x, mean, invstd and (when the pooled output was
+    used) the gradient of pool [B, C]."""
+    _need_gpu(g, x, mean, invstd, gamma, beta, g_pool)
+    g, x = g.contiguous(), x.contiguous()
+    B, H, W, C = x.shape
+    assert g.shape == x.shape, (g.shape, x.shape)
+    dev = x.device
+    g_x = torch.empty_like(x)
+    sums = torch.empty((2, C), dtype=torch.float32, device=dev)
+    ws = _ws(L.lib().vqae_bn_act_train_workspace_bytes(B, H * W, C), dev)
+    gp = None if g_pool is None else g_pool.float().contiguous()
+    L.check(L.lib().vqae_bn_act_train_backward_f32(_p(g), _p(x), _p(mean.contiguous()), _p(invstd.contiguous()), _p(_vec(gamma)),
+                                                   _p(_vec(beta)), _p(gp), int(training), int(silu), B, H * W, C, _p(g_x),
+                                                   _p(sums), _p(ws), _stream()))
+    return g_x, sums[1], sums[0]
+
+
+def dwconv_train_supported(c, h, w, mode):
+    return bool(L.lib().vqae_dwconv_train_supported(int(c), int(h), int(w), int(mode)))
+
+
+def _dw_out_shape(mode, H, W):
+    return {L.DW_SAME: (H, W), L.DW_DOWN: (H // 2, W // 2), L.DW_UP: (2 * H, 2 * W)}[mode]
+
+
+def dwconv_train_forward(x, w, mode):
+    """The depthwise conv of branch[3] on x [B, H, W, C] with the module's own weight [C, 1, k, k], read in place."""
+    _need_gpu(x, w)
+    x = x.contiguous()
+    B, H, W, C = x.shape
+    k = 3 if mode == L.DW_SAME else 2
+    assert tuple(w.shape) == (C, 1, k, k), (w.shape, C, mode)
+    Ho, Wo = _dw_out_shape(mode, H, W)
+    y = torch.empty((B, Ho, Wo, C), dtype=torch.float32, device=x.device)
+    L.check(L.lib().vqae_dwconv_train_forward_f32(_p(x), _p(_vec(w)), mode, B, H, W, C, _p(y), _stream()))
+    return y
+
+
+def dwconv_train_backward(g, x, w, mode, need_x=True, need_w=True):
+    """-> (g_x | None, g_w in w's shape | None); g_x gathered, g_w a fixed-order fp64 sum."""
+    _need_gpu(g, x, w)
+    g, x = g.contiguous(), x.contiguous()
+    B, H, W, C = x.shape
+    assert tuple(g.shape) == (B, *_dw_out_shape(mode, H, W), C), (g.shape, x.shape, mode)
+    dev = x.device
+    g_x = torch.empty_like(x) if need_x else None
+    g_w = torch.empty(tuple(w.shape), dtype=torch.float32, device=dev) if need_w else None
+    ws = _ws(L.lib().vqae_dwconv_train_workspace_bytes(B, H, W, C, mode), dev) if need_w else None
+    L.check(L.lib().vqae_dwconv_train_backward_f32(_p(g), _p(x), _p(_vec(w)), mode, B, H, W, C, _p(g_x), _p(g_w), _p(ws),
+                                                   _stream()))
+    return g_x, g_w
+
+
+def se_scale_forward(x, gate):
+    """x [B, H, W, C] * gate [B, C]."""
+    _need_gpu(x, gate)
+    x, gate = x.contiguous(), gate.float().contiguous()
+    B, H, W, C = x.shape
+    assert tuple(gate.shape) == (B, C), (gate.shape, x.shape)
+    y = torch.empty_like(x)
+    L.check(L.lib().vqae_se_scale_forward_f32(_p(x), _p(gate), B, H * W, C, _p(y), _stream()))
+    return y
+
+
+def se_scale_backward(g, x, gate):
+    """-> (g_x = g * gate, g_gate [B, C] = sum_hw g * x)."""
+    _need_gpu(g, x, gate)
+    g, x, gate = g.contiguous(), x.contiguous(), gate.float().contiguous()
+    B, H, W, C = x.shape
+    assert g.shape == x.shape, (g.shape, x.shape)
+    g_x = torch.empty_like(x)
+    g_gate = torch.empty((B, C), dtype=torch.float32, device=x.device)
+    ws = _ws(L.lib().vqae_se_scale_workspace_bytes(B, H * W, C), x.device)
+    L.check(L.lib().vqae_se_scale_backward_f32(_p(g), _p(x), _p(gate), B, H * W, C, _p(g_x), _p(g_gate), _p(ws), _stream()))
+    return g_x, g_gate
+
+
 @functools.lru_cache(maxsize=None)
 def _conv_train_node(node):
     """L.CONV_TRAIN[node] with its entries resolved, once."""

@@ -936,6 +936,64 @@ int vqae_conv3x3z_train_backward_f32(const float* g_dev, const float* x_dev, con
                                      void* workspace_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * 6g. Training forms of the non-dense ops of an MBConv block (conv_block.py:240-321, misc.py:7-30; mbconv.yaml): the three
+ *     BatchNorms with batch statistics (+ SiLU), the depthwise conv of branch[3] and the SE product, forward and backward,
+ *     fp32, NHWC.  The dense 1x1 and skip convs stay with the caller.  One float4 of channels per lane: c a multiple of 4 in
+ *     4 .. 1024 (other c: VQAE_ERR_UNSUPPORTED), batch <= 65535, tensors 16-byte and workspaces 8-byte aligned.
+ *     Sums: every workgroup reduces VQAE_MBT_ROWS rows in fp64 in a fixed order and writes one fp64 partial row to the
+ *     workspace; a second launch adds the rows of one column with VQAE_MBT_FIN_LANES lanes (lane l: rows l, l + 64, ... in
+ *     order, then the lanes by shuffle) and rounds to fp32 once.  Grids depend on the shape only, no floating-point atomics:
+ *     bit-identical run to run.  No call synchronises.
+ *     Errors, before any HIP call: a dimension < 1, null pointers, a bad act / mode, misaligned pointers -> VQAE_ERR_INVALID;
+ *     c outside the rule, batch > 65535, batch hw c >= 2^40 -> VQAE_ERR_UNSUPPORTED; one row in training mode ->
+ *     VQAE_ERR_VALUE (torch's ValueError).
+ * ------------------------------------------------------------------------------------------- */
+#define VQAE_MBT_ROWS 256
+#define VQAE_MBT_FIN_LANES 64
+int vqae_bn_act_train_supported(int c);
+/* Bytes of workspace of the forward and of the backward (0 for a bad shape). */
+size_t vqae_bn_act_train_workspace_bytes(int batch, int64_t hw, int c);
+/* x, y [batch][hw][c]; gamma, beta, running_mean, running_var [c] floats; mean, invstd [c] DOUBLES (at a handful of rows the
+ * backward is a difference of nearly equal numbers, and a statistic rounded to fp32 would dominate it); M = batch hw rows.
+ * training != 0: mean and the BIASED variance of the M rows (fp64 sums of x - x[0] and its square, so that a constant channel
+ *   has variance exactly 0), invstd = 1 / sqrt(var + eps); in the launch that finishes the sums
+ *   running_mean = (1 - momentum) running_mean + momentum mean and running_var likewise with the UNBIASED variance
+ *   var M / (M - 1) (either may be NULL: not tracked).  M == 1 -> VQAE_ERR_VALUE.
+ * training == 0: mean = running_mean, invstd = 1 / sqrt(running_var + eps); no buffer is written.
+ * y = act((x - mean) invstd gamma + beta), act 0: identity, 1: SiLU.  mean and invstd are outputs: the backward's inputs.
+ * pool [batch][c] or NULL: pool[b][c] = sum over the image's hw rows of y (the squeeze of the SE layer before its division). */
+int vqae_bn_act_train_forward_f32(const float* x_dev, const float* gamma_dev, const float* beta_dev, float* running_mean_dev,
+                                  float* running_var_dev, int training, double momentum, double eps, int act, int batch,
+                                  int64_t hw, int c, float* y_dev, double* mean_dev, double* invstd_dev, float* pool_dev,
+                                  void* workspace_dev, void* stream);
+/* From g (the gradient of y), the forward's x, mean, invstd, gamma, beta and g_pool [batch][c] (the gradient of pool, or NULL):
+ *   xhat = (x - mean) invstd,  z = xhat gamma + beta (recomputed, never stored),  d = (g + g_pool[b]) act'(z) (pool is a sum);
+ *   g_beta_gamma [2][c]: row 0 = g_beta = sum d, row 1 = g_gamma = sum d xhat;
+ *   g_x = gamma invstd (d - g_beta / M - xhat g_gamma / M) for training != 0, gamma invstd d otherwise: xhat, the unrounded
+ *   sums and this combination in fp64, rounded to fp32 once. */
+int vqae_bn_act_train_backward_f32(const float* g_dev, const float* x_dev, const double* mean_dev, const double* invstd_dev,
+                                   const float* gamma_dev, const float* beta_dev, const float* g_pool_dev, int training, int act,
+                                   int batch, int64_t hw, int c, float* g_x_dev, float* g_beta_gamma_dev, void* workspace_dev,
+                                   void* stream);
+/* Depthwise conv of x [batch][h][w][c] with the module's own weight [c][1][k][k], read in place; no bias, no activation.
+ * mode: VQAE_DW_SAME (3x3, circular, any h, w >= 1: the wrap is in the addressing), VQAE_DW_DOWN (2x2 stride 2, h and w even),
+ * VQAE_DW_UP (ConvTranspose2d 2x2 stride 2, weight [c][1][2][2]).  Supported: c as above, h, w and the output's at most 16384. */
+int vqae_dwconv_train_supported(int c, int h, int w, int mode);
+size_t vqae_dwconv_train_workspace_bytes(int batch, int h, int w, int c, int mode);
+int vqae_dwconv_train_forward_f32(const float* x_dev, const float* w_dev, int mode, int batch, int h, int w, int c, float* y_dev,
+                                  void* stream);
+/* h, w: of the forward's x.  g_x (x's shape) is GATHERED, every element written once by a plain store: the same 3x3 over g
+ * with flipped taps, the stride-2 modes by each other's kernel.  g_w (w's shape) = sum over batch and pixels of g x at each
+ * tap, in fp64 as above.  g_x or g_w may be NULL (x and the workspace are read for g_w only, w for g_x only). */
+int vqae_dwconv_train_backward_f32(const float* g_dev, const float* x_dev, const float* w_dev, int mode, int batch, int h, int w,
+                                   int c, float* g_x_dev, float* g_w_dev, void* workspace_dev, void* stream);
+/* The SE product (misc.py:30): y[b][p][c] = x[b][p][c] gate[b][c];  g_x = g gate,  g_gate[b][c] = sum_p g x. */
+size_t vqae_se_scale_workspace_bytes(int batch, int64_t hw, int c);
+int vqae_se_scale_forward_f32(const float* x_dev, const float* gate_dev, int batch, int64_t hw, int c, float* y_dev, void* stream);
+int vqae_se_scale_backward_f32(const float* g_dev, const float* x_dev, const float* gate_dev, int batch, int64_t hw, int c,
+                               float* g_x_dev, float* g_gate_dev, void* workspace_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * 7. Counts of stored code grids -- produces what the reference commits as data under scripts/create_wsi_histograms/
  *    (embedding_idx_histogram_{K}_{split}.npy, histogram_{split}.npy; it ships no program for them) and reads its loss
  *    weights from (conf/model/optional_overrides/loss_f/bce_with_logits_loss_camelyon16_embeddings.yaml: "values taken
