@@ -1,5 +1,5 @@
-"""Shared by tests/test_blocks_gpu.py and tests/test_edges16_gpu.py: the oracle's per-block activations of the mid-size
-models, the handles that run them, and the block-parity bars.
+"""Shared by tests/test_blocks_gpu.py, tests/test_edges16_gpu.py and tests/test_edges32_*.py: the oracle's per-block activations
+of the mid-size models, the handles that run them, the block-parity bars, and the inputs of the edge cases.
 
 Oracle link: tests/golden/taps_<model>_<dtype>.npz hold, for every block of the mid-size models, a strided sample and the
 fp64 checksums of the REFERENCE's output (fp32 and under torch.autocast bf16 / f16); `oracle_taps` recomputes the full
@@ -115,3 +115,50 @@ def distance_to_exact(got_nhwc, ref_nchw, exact_nchw):
 def block_lists(oracle, spec):
     """(side, [(prefix, mode, cin, cout)], name of the tap in front of the side's first block)."""
     return (("encoder", oracle.encoder_blocks(spec), "stem"), ("decoder", oracle.decoder_blocks(spec), "q"))
+
+
+def find_block(oracle, spec, mode, cin, pair=False):
+    """(side, index, blocks, name of the tap in front of it) of the first block of that mode and input width -- with
+    pair, the first that is followed by another 'same' block of its width."""
+    for side, blocks, first_in in block_lists(oracle, spec):
+        if (side == "decoder") != (mode == "up") and not pair:
+            continue
+        for i, (prefix, m, ci, co) in enumerate(blocks):
+            if m != mode or ci != cin or (pair and not (i + 1 < len(blocks) and blocks[i + 1][1:] == ("same", cin, cin))):
+                continue
+            return side, i, blocks, (first_in if i == 0 else blocks[i - 1][0])
+    raise AssertionError((mode, cin, pair))
+
+
+def mirror_index(n, size):
+    """0 .. n - 1 of a signal of `size` samples continued by its mirror image: 0 1 .. size-1 size-1 .. 1 0 0 1 .."""
+    i = torch.arange(n) % (2 * size)
+    return torch.where(i < size, i, 2 * size - 1 - i)
+
+
+def edge_input(tap_nchw, B, H, W):
+    """The case's input [B, C, H, W] from the activation tap in front of the block cropped from the top-left
+    corner, continued by its mirror image where the case is wider or taller than the tap; the tap's first B images, further ones
+    the tap's images rolled by (1, 3) pixels."""
+    nb = tap_nchw.shape[0]
+    imgs = [torch.roll(tap_nchw[j % nb], shifts=(j // nb, 3 * (j // nb)), dims=(1, 2)) for j in range(B)]
+    x = torch.stack(imgs)
+    return x[:, :, mirror_index(H, x.shape[2])][:, :, :, mirror_index(W, x.shape[3])].contiguous()
+
+
+def roll_nhwc(t, dy, dx):
+    return torch.roll(t, shifts=(dy % t.shape[1], dx % t.shape[2]), dims=(1, 2))
+
+
+def f44_block(oracle, p, x_nchw, prefix):
+    """The 'same' block in x's dtype with conv2 evaluated as Winograd F(4x4, 3x3) (oracle/winograd_sim.py, test infrastructure
+    the product never imports): the CPU yardstick of the routes whose conv2 is F(4x4, 3x3), whose transforms cost accuracy
+    that no kernel of that form can avoid.  H and W multiples of 4."""
+    import importlib
+    sim = importlib.import_module("oracle.winograd_sim")
+    direct = oracle.conv_circular3x3
+    oracle.conv_circular3x3 = lambda t, w: sim.winograd_conv3x3_circular(t, w, 4)
+    try:
+        return oracle.fixup_block(x_nchw, p, prefix, "same")
+    finally:
+        oracle.conv_circular3x3 = direct

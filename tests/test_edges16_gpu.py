@@ -31,7 +31,8 @@ Per case:
 import pytest
 import torch
 
-from block_cases import autocast_ctx, block_lists, compare, distance_to_exact, exact_block, native_handle, nhwc, oracle_taps
+from block_cases import (autocast_ctx, compare, distance_to_exact, edge_input, exact_block, find_block, native_handle, nhwc, oracle_taps,
+                         roll_nhwc)
 from conftest import record_parity
 
 pytestmark = pytest.mark.gpu
@@ -83,39 +84,8 @@ ROLLS = {"same": (((1, 0), (1, 0)), ((0, 1), (0, 1)), ((0, 31), (0, 31)), ((1, 3
          "down": (((2, 0), (1, 0)), ((0, 2), (0, 1)), ((0, 66), (0, 33)))}
 
 
-def find_block(oracle, spec, mode, cin, pair=False):
-    """(side, index, blocks, name of the tap in front of it) of the first block of that mode and input width -- with
-    pair, the first that is followed by another 'same' block of its width."""
-    for side, blocks, first_in in block_lists(oracle, spec):
-        if (side == "decoder") != (mode == "up") and not pair:
-            continue
-        for i, (prefix, m, ci, co) in enumerate(blocks):
-            if m != mode or ci != cin or (pair and not (i + 1 < len(blocks) and blocks[i + 1][1:] == ("same", cin, cin))):
-                continue
-            return side, i, blocks, (first_in if i == 0 else blocks[i - 1][0])
-    raise AssertionError((mode, cin, pair))
-
-
-def mirror_index(n, size):
-    """0 .. n - 1 of a signal of `size` samples continued by its mirror image: 0 1 .. size-1 size-1 .. 1 0 0 1 .."""
-    i = torch.arange(n) % (2 * size)
-    return torch.where(i < size, i, 2 * size - 1 - i)
-
-
-def edge_input(tap_nchw, B, H, W):
-    """The case's input [B, C, H, W] from the activation tap in front of the block (module docstring)."""
-    nb = tap_nchw.shape[0]
-    imgs = [torch.roll(tap_nchw[j % nb], shifts=(j // nb, 3 * (j // nb)), dims=(1, 2)) for j in range(B)]
-    x = torch.stack(imgs)
-    return x[:, :, mirror_index(H, x.shape[2])][:, :, :, mirror_index(W, x.shape[3])].contiguous()
-
-
 def run1(nat, side, i, x_nchw, count=1):
     return nat.run_blocks(side, i, count, nhwc(x_nchw).cuda())
-
-
-def roll_nhwc(t, dy, dx):
-    return torch.roll(t, shifts=(dy % t.shape[1], dx % t.shape[2]), dims=(1, 2))
 
 
 @pytest.mark.parametrize("tag", ["bf16", "f16"])
