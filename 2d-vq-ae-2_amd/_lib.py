@@ -199,6 +199,18 @@ SYMBOLS = {
                                             c_void_p, c_void_p]),
     "vqae_bicubic_up2_bias_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "vqae_bicubic_up2_backward_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vqae_up_train_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    # t_low a b batch h w c y stream
+    "vqae_up2_act_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    # g t_low a batch h w c g_t_low g_a g_b ws stream
+    "vqae_up2_act_backward_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p]),
+    # t s_low scale bias4 bias1d batch h w c y stream
+    "vqae_fixup_out_up_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                      c_void_p]),
+    # g t scale batch h w c g_t g_s_low g_scale g_bias4 g_bias1d ws stream
+    "vqae_fixup_out_up_backward_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vqae_bn_act_train_supported": (c_int, [c_int]),
     "vqae_bn_act_train_workspace_bytes": (c_size_t, [c_int, c_int64, c_int]),
     # x gamma beta running_mean running_var training momentum eps act batch hw c y mean invstd pool ws stream

@@ -282,6 +282,67 @@ def bicubic_up2_backward(g, want_bias=True):
     return g_x, g_pb
 
 
+def _up_train_ws(B, H, W, C, dev):
+    return torch.empty(L.lib().vqae_up_train_workspace_bytes(B, H, W, C), dtype=torch.uint8, device=dev)
+
+
+def up2_act(t_low, a, b):
+    """y [B, 2H, 2W, C] = ELU(bicubic_up2(t_low) + a) + b on t_low [B, H, W, C], one launch: bit for bit
+    fixup_act(bicubic_up2_bias(t_low), a, b), without the upsampled tensor in between (csrc/up_train.hip)."""
+    _need_gpu(t_low)
+    t_low = t_low.contiguous()
+    B, H, W, C = t_low.shape
+    y = torch.empty((B, 2 * H, 2 * W, C), dtype=torch.float32, device=t_low.device)
+    L.check(L.lib().vqae_up2_act_f32(_p(t_low), _p(_scalar(a)), _p(_scalar(b)), B, H, W, C, _p(y), _stream()))
+    return y
+
+
+def up2_act_backward(g, t_low, a):
+    """-> (g_t_low [B, H, W, C], g_a [1], g_b [1]) from g [B, 2H, 2W, C] and the forward's t_low and a: the bits of
+    bicubic_up2_backward(fixup_act_backward(g, bicubic_up2_bias(t_low), a)[0]) with up2(t_low) recomputed in LDS."""
+    _need_gpu(g, t_low)
+    g, t_low = g.contiguous(), t_low.contiguous()
+    B, H, W, C = t_low.shape
+    assert tuple(g.shape) == (B, 2 * H, 2 * W, C), (g.shape, t_low.shape)
+    dev = g.device
+    g_t_low = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
+    g_a, g_b = (torch.empty(1, dtype=torch.float32, device=dev) for _ in range(2))
+    ws = _up_train_ws(B, H, W, C, dev)
+    L.check(L.lib().vqae_up2_act_backward_f32(_p(g), _p(t_low), _p(_scalar(a)), B, H, W, C, _p(g_t_low), _p(g_a), _p(g_b),
+                                              _p(ws), _stream()))
+    return g_t_low, g_a, g_b
+
+
+def fixup_out_up(t, s_low, scale, bias4, bias1d):
+    """y = (t * scale + bias4) + (bicubic_up2(s_low) + bias1d), t [B, 2H, 2W, C], s_low [B, H, W, C], one launch: bit for bit
+    fixup_out(t, bicubic_up2_bias(s_low), scale, bias4, bias1d), without the upsampled skip (csrc/up_train.hip)."""
+    _need_gpu(t, s_low)
+    t, s_low = t.contiguous(), s_low.contiguous()
+    B, H, W, C = s_low.shape
+    assert tuple(t.shape) == (B, 2 * H, 2 * W, C), (t.shape, s_low.shape)
+    y = torch.empty_like(t)
+    L.check(L.lib().vqae_fixup_out_up_f32(_p(t), _p(s_low), _p(_scalar(scale)), _p(_scalar(bias4)), _p(_scalar(bias1d)), B, H, W,
+                                          C, _p(y), _stream()))
+    return y
+
+
+def fixup_out_up_backward(g, t, scale):
+    """-> (g_t = g * scale, g_s_low [B, H, W, C] = the bicubic adjoint of g, g_scale [1] = sum g t, g_bias [1] = sum g), one
+    pass over g [B, 2H, 2W, C]."""
+    _need_gpu(g, t)
+    g, t = g.contiguous(), t.contiguous()
+    assert t.shape == g.shape and g.shape[1] % 2 == 0 and g.shape[2] % 2 == 0, (t.shape, g.shape)
+    B, H, W, C = g.shape[0], g.shape[1] // 2, g.shape[2] // 2, g.shape[3]
+    dev = g.device
+    g_t = torch.empty_like(g)
+    g_s_low = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
+    g_scale, g_bias = (torch.empty(1, dtype=torch.float32, device=dev) for _ in range(2))
+    ws = _up_train_ws(B, H, W, C, dev)
+    L.check(L.lib().vqae_fixup_out_up_backward_f32(_p(g), _p(t), _p(_scalar(scale)), B, H, W, C, _p(g_t), _p(g_s_low),
+                                                   _p(g_scale), _p(g_bias), None, _p(ws), _stream()))
+    return g_t, g_s_low, g_scale, g_bias
+
+
 def _ws(n_bytes, dev):
     return torch.empty(max(int(n_bytes), 8), dtype=torch.uint8, device=dev)
 

@@ -34,7 +34,19 @@ skip_conv of an 'out' block (C -> 3) -- have one behind the independent keyword 
                                  no padded or re-laid-out copy of a full-resolution tensor exists.  Channel counts outside the
                                  kernels' rule (one side 3, the other a multiple of 8) take the torch route, counted in
                                  stats["conv3x3z_fallbacks"]; stats["conv3x3z_hip"] counts the nodes.
-With all four keywords at their defaults the graph is op for op the one described above.
+The 'up' blocks have a fifth, independent keyword, `conv_up`, which selects the ORDER of the block and two fused nodes, not a
+conv kernel (the 1x1 convs stay routed by `conv1x1`):
+
+    conv_up="torch" (default)    conv2 and the skip_conv run at FULL resolution, behind bicubic_up2, as always
+    conv_up="hip"                a 1x1 conv and the bicubic x2 commute (the conv mixes channels per pixel, the resize pixels per
+                                 channel, and its clamped taps sum to 1, so the pre-bias commutes too): conv2 and the skip_conv run
+                                 at LOW resolution, a quarter of the FLOPs and of the weight gradients' rows, and the resize moves
+                                 into the two element-wise ops behind them, each ONE node of csrc/up_train.hip:
+                                 up2_act = ELU(up2(t_low) + bias3a) + bias3b in front of conv3, and fixup_out_up = (t * scale +
+                                 bias4) + (up2(s_low) + bias1d).  No upsampled tensor is written in either direction.  Any shape;
+                                 stats["conv_up_hip"] counts the nodes (two per block); stats["conv_up_fallbacks"] counts the
+                                 'up' blocks without a skip_conv, which no constructor builds and which raise as the torch route.
+With all five keywords at their defaults the graph is op for op the one described above.
 No conv then stays with torch except branch_conv3 8 -> 3 of an 'out' block, a counted conv1x1 fall-back (no shipped config
 instantiates an 'out' block), and the quantiser's 1x1 projections, which have their own fused backward (layers/vq.py).
 
@@ -45,6 +57,8 @@ instantiates an 'out' block), and the quantiser's 1x1 projections, which have th
     conv_down(x, w, a, b)        the fused 2x2, stride-2 node: [B, H, W, Ci] -> [B, H/2, W/2, Co]
     conv3x3(x, w, a, b)          the fused circular 3x3 node: [B, H, W, Ci] -> [B, H, W, Co]
     conv3x3z(x, w, bias, c)      the fused zero-padded 3x3 node with a 3-channel side: [B, H, W, Ci] -> [B, H, W, Co]
+    up2_act(t_low, a, b)         ELU(bicubic_up2(t_low) + a) + b as one node: [B, H, W, C] -> [B, 2H, 2W, C]
+    fixup_out_up(t, s_low, scale, bias4, bias1d)   (t * scale + bias4) + (bicubic_up2(s_low) + bias1d) as one node
 
 The functional ops (fixup_act, fixup_add, fixup_out, bicubic_up2) take channel-last tensors [B, H, W, C], like every other
 op of the package.  The graph stays channel-last throughout (the reference trains in channels_last: model.py:124-126): a conv
@@ -75,9 +89,10 @@ from .layers.conv_block import PreActFixupResBlock
 from .layers.vq import ProjectedEMAVectorQuantizer2d
 
 stats = {"layout_checks": 0, "layout_copies": 0, "conv1x1_hip": 0, "conv1x1_fallbacks": 0, "conv_down_hip": 0,
-         "conv_down_fallbacks": 0, "conv3x3_hip": 0, "conv3x3_fallbacks": 0, "conv3x3z_hip": 0, "conv3x3z_fallbacks": 0}
-ROUTES = ("torch", "hip")                                     # of each of the keywords conv1x1, conv_down, conv3x3, conv3x3z
-CONV1X1_ROUTES = CONV_DOWN_ROUTES = CONV3X3_ROUTES = CONV3X3Z_ROUTES = ROUTES
+         "conv_down_fallbacks": 0, "conv3x3_hip": 0, "conv3x3_fallbacks": 0, "conv3x3z_hip": 0, "conv3x3z_fallbacks": 0,
+         "conv_up_hip": 0, "conv_up_fallbacks": 0}
+ROUTES = ("torch", "hip")                           # of each of the keywords conv1x1, conv_down, conv3x3, conv3x3z, conv_up
+CONV1X1_ROUTES = CONV_DOWN_ROUTES = CONV3X3_ROUTES = CONV3X3Z_ROUTES = CONV_UP_ROUTES = ROUTES
 
 _W75 = (-0.03515625, 0.26171875, 0.87890625, -0.10546875)     # even outputs: inputs m-2 .. m+1, m = o >> 1
 _W25 = (-0.10546875, 0.87890625, 0.26171875, -0.03515625)     # odd outputs:  inputs m-1 .. m+2
@@ -252,6 +267,56 @@ class _BicubicFn(torch.autograd.Function):
             g_x = _bicubic_up2_adjoint_torch(g)
             g_pb = g_x.sum()
         return g_x, _like(g_pb, ctx.pb) if ctx.pb is not None else None
+
+
+class _Up2ActFn(torch.autograd.Function):
+    """y = ELU(up2(t_low) + a) + b, up2 the bicubic x2 of _BicubicFn.  Saves t_low only: the backward recomputes up2(t_low) for
+    ELU' (csrc/up_train.hip: in LDS), so no full-resolution tensor is kept or written."""
+
+    @staticmethod
+    def forward(ctx, t_low, a, b):
+        if t_low.is_cuda:
+            y = ops.up2_act(t_low.float(), a, b)
+        else:
+            y = F.elu(_bicubic_up2_torch(t_low, None) + a) + b
+        ctx.save_for_backward(t_low, a)
+        ctx.b = b
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        t_low, a = ctx.saved_tensors
+        if g.is_cuda:
+            g_t_low, g_a, g_b = ops.up2_act_backward(_dense(g.float()), t_low.float(), a)
+        else:
+            g_v = g * elu_grad(_bicubic_up2_torch(t_low, None) + a)
+            g_t_low, g_a, g_b = _bicubic_up2_adjoint_torch(g_v), g_v.sum(), g.sum()
+        return g_t_low, _like(g_a, a), _like(g_b, ctx.b)
+
+
+class _OutUpFn(torch.autograd.Function):
+    """y = (t * scale + bias4) + (up2(s_low) + bias1d): the output op of an 'up' block whose skip_conv ran at low resolution."""
+
+    @staticmethod
+    def forward(ctx, t, s_low, scale, bias4, bias1d):
+        if t.is_cuda:
+            y = ops.fixup_out_up(t.float(), _dense(s_low.float()), scale, bias4, bias1d)
+        else:
+            y = (t * scale + bias4) + (_bicubic_up2_torch(s_low, None) + bias1d)
+        ctx.save_for_backward(t, scale)
+        ctx.b4, ctx.b1d = bias4, bias1d
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        t, scale = ctx.saved_tensors
+        if g.is_cuda:
+            g_t, g_s_low, g_scale, g_bias = ops.fixup_out_up_backward(_dense(g.float()), t.float(), scale)
+        else:
+            g_t, g_s_low, g_scale, g_bias = g * scale, _bicubic_up2_adjoint_torch(g), (g * t).sum(), g.sum()
+        return g_t, g_s_low, _like(g_scale, scale), _like(g_bias, ctx.b4), _like(g_bias, ctx.b1d)
 
 
 def _pre_op_torch(x, a, b):
@@ -460,16 +525,29 @@ def bicubic_up2(x, pre_bias=None):
     return _BicubicFn.apply(x, pre_bias)
 
 
+def up2_act(t_low, a, b):
+    """ELU(bicubic_up2(t_low) + a) + b on [B, H, W, C] -> [B, 2H, 2W, C] as ONE node: csrc/up_train.hip on the device, a
+    plain-torch restatement on CPU tensors."""
+    return _Up2ActFn.apply(t_low, a, b)
+
+
+def fixup_out_up(t, s_low, scale, bias4, bias1d):
+    """(t * scale + bias4) + (bicubic_up2(s_low) + bias1d), t [B, 2H, 2W, C], s_low [B, H, W, C], as ONE node: csrc/up_train.hip
+    on the device, a plain-torch restatement on CPU tensors."""
+    assert tuple(t.shape) == (s_low.shape[0], 2 * s_low.shape[1], 2 * s_low.shape[2], s_low.shape[3]), (t.shape, s_low.shape)
+    return _OutUpFn.apply(t, s_low, scale, bias4, bias1d)
+
+
 # ---- blocks and the model ------------------------------------------------------------------------------------------------
 def _conv(t, w, bias=None, stride=1, padding=0):
     """F.conv2d on a channel-last tensor, channel-last result."""
     return to_nhwc(F.conv2d(to_nchw(t), w, bias, stride=stride, padding=padding))
 
 
-def conv_routes(conv1x1="torch", conv_down="torch", conv3x3="torch", conv3x3z="torch"):
-    """The four route keywords, checked -> {node: whether its convs are the fused nodes of csrc/conv_train.hip and
-    csrc/conv_train_thin.hip}."""
-    routes = dict(conv1x1=conv1x1, conv_down=conv_down, conv3x3=conv3x3, conv3x3z=conv3x3z)
+def conv_routes(conv1x1="torch", conv_down="torch", conv3x3="torch", conv3x3z="torch", conv_up="torch"):
+    """The five route keywords, checked -> {node: whether its convs are the fused nodes of csrc/conv_train.hip and
+    csrc/conv_train_thin.hip; "conv_up": whether an 'up' block runs its convs at low resolution around csrc/up_train.hip}."""
+    routes = dict(conv1x1=conv1x1, conv_down=conv_down, conv3x3=conv3x3, conv3x3z=conv3x3z, conv_up=conv_up)
     for keyword, value in routes.items():
         if value not in ROUTES:
             raise ValueError(f"{keyword} must be one of {ROUTES}, not {value!r}")
@@ -507,17 +585,38 @@ def _pre_conv(node, hip, x, a, b, w, bias=None):
     return torch_route(x, a, b, w, *extra)
 
 
+def _up_block_low(block, x, hip):
+    """An 'up' block in the commuted order (conv_up = "hip"): conv2 and the skip_conv at LOW resolution, the bicubic x2 inside
+    the two ops behind them.  up2(conv(u)) = conv(up2(u)) for a 1x1 conv, and up2(s) + c = up2(s + c), so this is the block's
+    function; the sums are the same products in another order."""
+    t = _pre_conv("conv1x1", hip, x, block.bias1a, block.bias1b, block.branch_conv1.weight)
+    t_low = _pre_conv("conv1x1", hip, t, block.bias2a, block.bias2b, block.branch_conv2.weight)
+    stats["conv_up_hip"] += 1
+    u = up2_act(t_low, block.bias3a, block.bias3b)
+    t = _pre_conv("conv1x1", hip, u, None, None, block.branch_conv3.weight)
+    s_low = _pre_conv("conv1x1", hip, x, None, block.bias1c, block.skip_conv.weight)
+    stats["conv_up_hip"] += 1
+    return fixup_out_up(t, s_low, block.scale, block.bias4, block.bias1d)
+
+
 def block_forward_nhwc(block, x, **routes):
     """conv_block.py:196-216 on [B, H, W, C] with a graph: the fused ops around F.conv2d.  routes: the keywords of conv_routes,
     each "torch" by default.  conv1x1 = "hip": every 1x1, stride-1 conv the kernels support is one node with the op in front
     of it (csrc/conv_train.hip); conv_down = "hip": so is each 2x2, stride-2 conv of a 'down' block; conv3x3 = "hip": so is
     the circular 3x3 of a 'same' or 'out' block; conv3x3z = "hip": so is the zero-padded 3x3 skip_conv of an 'out' block
-    (csrc/conv_train_thin.hip); "torch": F.conv2d."""
+    (csrc/conv_train_thin.hip); "torch": F.conv2d.  conv_up = "hip": an 'up' block runs conv2 and its skip_conv at low
+    resolution, with the bicubic x2 inside up2_act and fixup_out_up (csrc/up_train.hip); "torch": behind bicubic_up2."""
     if not isinstance(block, PreActFixupResBlock):
         raise NotImplementedError(f"training is implemented for Fixup blocks only (no MBConv / BatchNorm training), not "
                                   f"{type(block).__name__}")
     hip = conv_routes(**routes)
     mode = block.mode
+    if mode == "up" and hip["conv_up"]:
+        if block.skip_conv is not None:
+            return _up_block_low(block, x, hip)
+        # No constructor builds an 'up' block without a skip_conv, and fixup_out_up has no such form (t and x differ in shape):
+        # counted, and the order below raises on those shapes as it always has.
+        stats["conv_up_fallbacks"] += 1
     t = _pre_conv("conv1x1", hip, x, block.bias1a, block.bias1b, block.branch_conv1.weight)
     if mode in ("same", "out"):                         # 3x3 circular
         t = _pre_conv("conv3x3", hip, t, block.bias2a, block.bias2b, block.branch_conv2.weight)
@@ -547,7 +646,7 @@ def _compute_dtype(x):
 
 def block_forward(block, x, **routes):
     """One PreActFixupResBlock mirror on an NCHW-shaped tensor (channels_last preferred: no copy) -> NCHW-shaped, with a graph.
-    routes: conv1x1 / conv_down / conv3x3 / conv3x3z, as in block_forward_nhwc."""
+    routes: conv1x1 / conv_down / conv3x3 / conv3x3z / conv_up, as in block_forward_nhwc."""
     return to_nchw(block_forward_nhwc(block, to_nhwc(_compute_dtype(x)), **routes))
 
 
@@ -608,8 +707,8 @@ def forward_train(model, x, return_indices=False, **routes):
     """VQAE.forward (vq_ae/model.py:41-48) over a vqae_amd.model.VQAE mirror, with a graph: -> (out, (vq_loss,)), out NCHW-shaped
     (channels_last).  The stems are F.conv2d (conv3x3z = "hip": the fused zero-padded node, where the kernels take the stem's
     width), the blocks block_forward, the quantiser its own trainable mirror (its EMA buffers are updated in training mode, as in
-    the reference).  routes: conv1x1 / conv_down / conv3x3 / conv3x3z = "torch" (default) | "hip", the routes of the blocks' 1x1,
-    2x2 stride-2, circular 3x3 and zero-padded 3x3 convs (block_forward_nhwc)."""
+    the reference).  routes: conv1x1 / conv_down / conv3x3 / conv3x3z / conv_up = "torch" (default) | "hip", the routes of the
+    blocks' 1x1, 2x2 stride-2, circular 3x3 and zero-padded 3x3 convs and the order of the 'up' blocks (block_forward_nhwc)."""
     hip = conv_routes(**routes)
     enc, dec = model.encoder, model.decoder
     h = to_nhwc(_compute_dtype(x))
@@ -635,6 +734,6 @@ def forward_train(model, x, return_indices=False, **routes):
 
 def step(model, batch, loss_f=F.huber_loss, **routes):
     """VQAE.step (vq_ae/model.py:114-122): -> (out, recon_loss, (vq_loss,)); the caller backpropagates recon_loss + sum(vq_loss).
-    routes: conv1x1 / conv_down / conv3x3 / conv3x3z, as in forward_train."""
+    routes: conv1x1 / conv_down / conv3x3 / conv3x3z / conv_up, as in forward_train."""
     out, encoding_loss = forward_train(model, batch, **routes)
     return out, loss_f(input=out, target=batch), encoding_loss

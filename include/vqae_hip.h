@@ -792,6 +792,33 @@ int vqae_bicubic_up2_backward_f32(const float* g_dev, int batch, int h, int w, i
                                   void* workspace_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * 6b'. The two full-resolution ops of an 'up' block whose 1x1 convs run BEFORE the bicubic x2 (conv_block.py:196-216,
+ *     conv.py:4-11: a 1x1 conv and the resize commute, the clamped taps summing to 1), fp32, NHWC, any c >= 1 and h, w >= 1.
+ *     up2 is the bicubic of vqae_bicubic_up2_bias_f32 and up2^T the gather of vqae_bicubic_up2_backward_f32: the same sums in
+ *     the same order, so each entry is bit for bit the composition of the 6b entries it fuses; what it removes is memory.
+ *     One-element parameters, sums, determinism and errors as in 6b.  workspace_dev: vqae_up_train_workspace_bytes(batch, h,
+ *     w, c) bytes, 8-byte aligned; h, w are the LOW-resolution extents everywhere.
+ * ------------------------------------------------------------------------------------------- */
+size_t vqae_up_train_workspace_bytes(int batch, int h, int w, int c);
+/* conv_block.py:196-216, conv.py:4-11.  y [B][2H][2W][C] = ELU(v + *a) + *b, v = up2(t_low), t_low [B][H][W][C]; v is not
+ * written. */
+int vqae_up2_act_f32(const float* t_low_dev, const float* a_dev, const float* b_dev, int batch, int h, int w, int c,
+                     float* y_dev, void* stream);
+/* conv_block.py:196-216, conv.py:4-11.  g [B][2H][2W][C]; g_v = g * ELU'(v + *a) with v recomputed from t_low (never
+ * written);  g_t_low [B][H][W][C] = up2^T g_v;  *g_a = sum g_v;  *g_b = sum g (each may be NULL). */
+int vqae_up2_act_backward_f32(const float* g_dev, const float* t_low_dev, const float* a_dev, int batch, int h, int w, int c,
+                              float* g_t_low_dev, float* g_a_dev, float* g_b_dev, void* workspace_dev, void* stream);
+/* conv_block.py:196-216, conv.py:4-11.  y = (t * *scale + *bias4) + (up2(s_low) + *bias1d); t, y [B][2H][2W][C], s_low
+ * [B][H][W][C]; the upsampled skip is not written. */
+int vqae_fixup_out_up_f32(const float* t_dev, const float* s_low_dev, const float* scale_dev, const float* bias4_dev,
+                          const float* bias1d_dev, int batch, int h, int w, int c, float* y_dev, void* stream);
+/* conv_block.py:196-216, conv.py:4-11.  One pass over g [B][2H][2W][C]: g_t = g * *scale;  g_s_low [B][H][W][C] = up2^T g;
+ * *g_scale = sum g * t;  *g_bias4 = *g_bias1d = sum g (each may be NULL). */
+int vqae_fixup_out_up_backward_f32(const float* g_dev, const float* t_dev, const float* scale_dev, int batch, int h, int w,
+                                   int c, float* g_t_dev, float* g_s_low_dev, float* g_scale_dev, float* g_bias4_dev,
+                                   float* g_bias1d_dev, void* workspace_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * 6c. Trainable 1x1, stride-1 convolutions of a Fixup block (conv_block.py:196-216: branch_conv1, branch_conv3, the 1x1 after
  *     the bicubic of 'up' blocks, skip_conv of 'same' blocks; conf/model/layers/conv_layer/proj2d.yaml: kernel 1, no bias), fp32,
  *     NHWC, with the element-wise op in front of the conv folded into the operand load:
