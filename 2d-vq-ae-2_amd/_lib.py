@@ -197,6 +197,18 @@ SYMBOLS = {
     "vqae_fixup_out_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "vqae_fixup_out_backward_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_void_p, c_void_p]),
+    # x x_dt a b act halo batch h w c y y_dt stream
+    "vqae_fixup_act_io": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
+                                  c_void_p]),
+    # g g_dt x x_dt a act halo batch h w c g_x g_a g_b ws stream
+    "vqae_fixup_act_backward_io": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # t t_dt skip skip_dt scale bias4 bias1d n y y_dt stream
+    "vqae_fixup_out_io": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int,
+                                  c_void_p]),
+    # g t t_dt scale n g_t g_skip skip_dt g_scale g_bias4 g_bias1d ws stream
+    "vqae_fixup_out_backward_io": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p]),
     "vqae_bicubic_up2_bias_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "vqae_bicubic_up2_backward_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vqae_up_train_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),

@@ -28,6 +28,10 @@
 // wave by shuffle, the 4 waves in index order, one fp64 row per workgroup in the workspace; ft_final adds the rows in a
 // fixed order and rounds to fp32 once.  The grid is a function of the shape alone and there are no floating-point atomics:
 // every result is bit-identical run to run.
+//
+// Everything here is fp32.  The forms of act / plain / out with 16-bit I/O, for training under autocast, are the sibling file
+// fixup_train_io.hip (vqae_fixup_*_io): the same arithmetic in the same element order on up-cast values, one rounding on
+// store; with every tensor fp32 they forward to the entry points below.
 #include "fixup_train_impl.h"
 
 namespace {

@@ -200,6 +200,22 @@ def _train_ws(n, dev):
     return torch.empty(L.lib().vqae_fixup_train_workspace_bytes(int(n)), dtype=torch.uint8, device=dev)
 
 
+_IO_DTYPES = {torch.float32: L.DT_F32, torch.bfloat16: L.DT_BF16, torch.float16: L.DT_F16}
+
+
+def _need_f32(who, **tensors):
+    """The fp32 entry points read 4 bytes per element: a tensor of another dtype never reaches them (before any device call)."""
+    for name, t in tensors.items():
+        assert t is None or t.dtype == torch.float32, f"{who}: {name} is {t.dtype}; the fp32 op takes fp32 tensors (see {who}_io)"
+
+
+def _io_code(who, name, dtype):
+    try:
+        return _IO_DTYPES[dtype]
+    except KeyError:
+        raise AssertionError(f"{who}: {name} is {dtype}; fp32, bf16 and f16 are taken")
+
+
 def fixup_act(x, a, b, halo=0):
     """y = ELU(x + a) + b on x [B, H, W, C]; a, b one-element device tensors; a None: the plain mode y = x + b.
     halo = 1: y [B, H + 2, W + 2, C] with the circular wrap written (= F.pad(y, (1, 1, 1, 1), 'circular') in NCHW terms)."""
@@ -215,6 +231,7 @@ def fixup_act(x, a, b, halo=0):
 def fixup_act_backward(g, x, a, halo=0, act=True):
     """-> (g_x [B, H, W, C], g_a [1], g_b [1]) from g (with the halo when halo = 1) and the forward's x and a.  Plain mode
     (act False; x, a unused): (g, None, g_b) -- the input gradient is the incoming tensor itself."""
+    _need_f32("fixup_act_backward", g=g, x=x if act else None)
     _need_gpu(g)
     g = g.contiguous()
     B, H, W, C = g.shape[0], g.shape[1] - 2 * halo, g.shape[2] - 2 * halo, g.shape[3]
@@ -246,6 +263,7 @@ def fixup_out(t, skip, scale, bias4, bias1d=None):
 
 def fixup_out_backward(g, t, scale):
     """-> (g_t = g * scale, g_scale [1] = sum g t, g_bias [1] = sum g); the skip gradient is g itself."""
+    _need_f32("fixup_out_backward", g=g, t=t)
     _need_gpu(g, t)
     g, t = g.contiguous(), t.contiguous()
     assert t.shape == g.shape, (t.shape, g.shape)
@@ -256,6 +274,79 @@ def fixup_out_backward(g, t, scale):
     L.check(L.lib().vqae_fixup_out_backward_f32(_p(g), _p(t), _p(_scalar(scale)), g.numel(), _p(g_t), _p(g_scale), _p(g_bias),
                                                 None, _p(ws), _stream()))
     return g_t, g_scale, g_bias
+
+
+def fixup_act_io(x, a, b, halo=0, out_dtype=torch.float32):
+    """fixup_act with 16-bit I/O (csrc/fixup_train_io.hip): x fp32, bf16 or f16 -> y of `out_dtype` (fp32 or the same 16-bit
+    type), bit for bit fixup_act(x.float(), a, b, halo).to(out_dtype) without the two casts."""
+    dx, dy = _io_code("fixup_act_io", "x", x.dtype), _io_code("fixup_act_io", "out_dtype", out_dtype)
+    _need_gpu(x)
+    x = x.contiguous()
+    B, H, W, C = x.shape
+    y = torch.empty((B, H + 2 * halo, W + 2 * halo, C), dtype=out_dtype, device=x.device)
+    L.check(L.lib().vqae_fixup_act_io(_p(x), dx, _p(_scalar(a)), _p(_scalar(b)), int(a is not None), int(halo), B, H, W, C,
+                                      _p(y), dy, _stream()))
+    return y
+
+
+def fixup_act_backward_io(g, x, a, halo=0, act=True, x_dtype=None):
+    """fixup_act_backward with 16-bit I/O: g in the forward's output dtype (with the halo when halo = 1), x as the forward
+    read it -> (g_x in x's dtype, g_a [1], g_b [1]), g_a / g_b fp32 sums of the unrounded terms.  Plain mode (act False; x, a
+    unused, x_dtype = the forward's input dtype): g_x is g itself where the dtypes agree, else g cast to x_dtype, written by
+    the launch that sums it."""
+    x_dtype = x.dtype if act else (g.dtype if x_dtype is None else x_dtype)
+    dg, dx = _io_code("fixup_act_backward_io", "g", g.dtype), _io_code("fixup_act_backward_io", "x", x_dtype)
+    _need_gpu(g, x if act else None)
+    g = g.contiguous()
+    B, H, W, C = g.shape[0], g.shape[1] - 2 * halo, g.shape[2] - 2 * halo, g.shape[3]
+    dev = g.device
+    g_b = torch.empty(1, dtype=torch.float32, device=dev)
+    ws = _train_ws(g.numel(), dev)
+    if not act:
+        g_x = g if x_dtype == g.dtype else torch.empty(g.shape, dtype=x_dtype, device=dev)
+        L.check(L.lib().vqae_fixup_act_backward_io(_p(g), dg, None, dx, None, 0, 0, B, H, W, C, None if g_x is g else _p(g_x),
+                                                   None, _p(g_b), _p(ws), _stream()))
+        return g_x, None, g_b
+    x = x.contiguous()
+    assert tuple(x.shape) == (B, H, W, C), (x.shape, g.shape)
+    g_x = torch.empty((B, H, W, C), dtype=x_dtype, device=dev)
+    g_a = torch.empty(1, dtype=torch.float32, device=dev)
+    L.check(L.lib().vqae_fixup_act_backward_io(_p(g), dg, _p(x), dx, _p(_scalar(a)), 1, int(halo), B, H, W, C, _p(g_x), _p(g_a),
+                                               _p(g_b), _p(ws), _stream()))
+    return g_x, g_a, g_b
+
+
+def fixup_out_io(t, skip, scale, bias4, bias1d=None, out_dtype=torch.float32):
+    """fixup_out with 16-bit inputs: t and skip each fp32 or 16-bit -> y, the fp32 residual stream (any other out_dtype is
+    refused by the library): bit for bit fixup_out(t.float(), skip.float(), ...)."""
+    dt, ds = _io_code("fixup_out_io", "t", t.dtype), _io_code("fixup_out_io", "skip", skip.dtype)
+    dy = _io_code("fixup_out_io", "out_dtype", out_dtype)
+    _need_gpu(t, skip)
+    t, skip = t.contiguous(), skip.contiguous()
+    assert t.shape == skip.shape, (t.shape, skip.shape)
+    y = torch.empty(t.shape, dtype=out_dtype, device=t.device)
+    L.check(L.lib().vqae_fixup_out_io(_p(t), dt, _p(skip), ds, _p(_scalar(scale)), _p(_scalar(bias4)), _p(_scalar(bias1d)),
+                                      t.numel(), _p(y), dy, _stream()))
+    return y
+
+
+def fixup_out_backward_io(g, t, scale, skip_dtype=torch.float32):
+    """fixup_out_backward with 16-bit I/O: g fp32, t as the forward read it -> (g_t in t's dtype, g_skip, g_scale [1],
+    g_bias [1]).  g_skip is g itself for an fp32 skip and g cast to a 16-bit skip_dtype, written in the same pass."""
+    _need_f32("fixup_out_backward_io", g=g)
+    dt, ds = _io_code("fixup_out_backward_io", "t", t.dtype), _io_code("fixup_out_backward_io", "skip_dtype", skip_dtype)
+    _need_gpu(g, t)
+    g, t = g.contiguous(), t.contiguous()
+    assert t.shape == g.shape, (t.shape, g.shape)
+    dev = g.device
+    g_t = torch.empty_like(t)
+    g_skip = g if skip_dtype == torch.float32 else torch.empty(g.shape, dtype=skip_dtype, device=dev)
+    g_scale, g_bias = (torch.empty(1, dtype=torch.float32, device=dev) for _ in range(2))
+    ws = _train_ws(g.numel(), dev)
+    L.check(L.lib().vqae_fixup_out_backward_io(_p(g), _p(t), dt, _p(_scalar(scale)), g.numel(), _p(g_t),
+                                               None if g_skip is g else _p(g_skip), ds, _p(g_scale), _p(g_bias), None, _p(ws),
+                                               _stream()))
+    return g_t, g_skip, g_scale, g_bias
 
 
 def bicubic_up2_bias(x, pre_bias=None):

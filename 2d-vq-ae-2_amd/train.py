@@ -75,8 +75,28 @@ runs of the step give the same gradients bit for bit.
 
 Each Function has a restatement in plain torch ops, taken when its tensors are on the CPU: the same forward, and the SAME
 hand-derived backward (the gather-fold of the halo, the bicubic adjoint, the fixed-order sums), which is what
-torch.autograd.gradcheck checks in tests/test_fixup_train_cpu.py.  fp32 only on the device; the Functions are
-once-differentiable.
+torch.autograd.gradcheck checks in tests/test_fixup_train_cpu.py.  The Functions are once-differentiable.
+
+16-bit autocast (`torch.autocast("cuda", dtype=torch.bfloat16 | torch.float16)` around the step; no keyword -- autocast is the
+switch; f16 with torch.amp.GradScaler, inf / NaN pass through the nodes as through torch's ops).  The reference's rounding
+points under autocast: a conv output is 16-bit; `conv_out + bias` promotes to fp32 (the biases are fp32 [1] Parameters), so
+ELU and the second bias are fp32; the next conv rounds its input to 16 bits; `out * scale + bias4 + x` is fp32, so the
+residual stream stays fp32; the gradient of a 16-bit tensor is 16-bit, of an fp32 tensor fp32.  The three element-wise nodes
+fixup_act, fixup_add and fixup_out follow them with 16-bit I/O (csrc/fixup_train_io.hip, ops.*_io):
+
+    reads     a 16-bit tensor (a conv output) as it is -- no `.float()` copy -- and saves it as it is: half the activation
+              memory of these nodes
+    writes    the autocast dtype where the consumer is an F.conv2d on the torch route with nothing in between (feeds_conv:
+              the bits the conv's own cast of the fp32 result would read, the cast kernel gone), fp32 anywhere else: an act in
+              front of bicubic_up2 stays fp32, and fixup_out always writes fp32
+    backward  g in the output's dtype, g_x in the input's; the scalar gradients are fp32, fp64 sums of the unrounded terms
+
+The arithmetic is the fp32 kernels' on the up-cast values with one rounding on store, so a node is bit for bit its fp32 form
+between the casts torch would have made.  With every tensor fp32 the Functions call what they always called.
+stats["io16_hip"] counts the nodes that ran a 16-bit form; stats["io16_fallbacks"] counts, under autocast, the nodes that have
+none and run their fp32 kernels on explicitly cast operands, correct but not 16-bit-native: the resize nodes (bicubic_up2,
+up2_act, fixup_out_up) and the fused conv nodes of the "hip" routes, which get fp32 operands.  The quantiser runs fp32, as in
+the reference (cdist is an fp32 op under autocast); MBConv training (train_mbconv.py) is fp32.
 """
 import functools
 
@@ -90,7 +110,7 @@ from .layers.vq import ProjectedEMAVectorQuantizer2d
 
 stats = {"layout_checks": 0, "layout_copies": 0, "conv1x1_hip": 0, "conv1x1_fallbacks": 0, "conv_down_hip": 0,
          "conv_down_fallbacks": 0, "conv3x3_hip": 0, "conv3x3_fallbacks": 0, "conv3x3z_hip": 0, "conv3x3z_fallbacks": 0,
-         "conv_up_hip": 0, "conv_up_fallbacks": 0}
+         "conv_up_hip": 0, "conv_up_fallbacks": 0, "io16_hip": 0, "io16_fallbacks": 0}
 ROUTES = ("torch", "hip")                           # of each of the keywords conv1x1, conv_down, conv3x3, conv3x3z, conv_up
 CONV1X1_ROUTES = CONV_DOWN_ROUTES = CONV3X3_ROUTES = CONV3X3Z_ROUTES = CONV_UP_ROUTES = ROUTES
 
@@ -171,17 +191,49 @@ def _like(g, p):
     return g.reshape(p.shape).to(p.dtype)
 
 
+# ---- dtypes under autocast -----------------------------------------------------------------------------------------------------
+_IO16 = (torch.bfloat16, torch.float16)
+
+
+def autocast16(t):
+    """The 16-bit dtype an F.conv2d rounds its input to under the autocast that is on for t's device; None without one."""
+    kind = t.device.type
+    if not torch.is_autocast_enabled(kind):
+        return None
+    dtype = torch.get_autocast_dtype(kind)
+    return dtype if dtype in _IO16 else None
+
+
+def _one16(*dtypes):
+    """Whether the dtypes hold one 16-bit type at most (the kernels' rule)."""
+    return len({d for d in dtypes if d in _IO16}) <= 1
+
+
+def _up(t):
+    """A 16-bit tensor up-cast (exact); any other as it is."""
+    return t.float() if t.dtype in _IO16 else t
+
+
 # ---- autograd Functions --------------------------------------------------------------------------------------------------
 class _ActFn(torch.autograd.Function):
     """y = ELU(x + a) + b (+ circular halo).  Saves x: ELU' from the output, (y - b) + 1, has no correct bits where the ELU
-    saturates, and Adam steps dead channels by the sign of that noise (DESIGN section 16 has both measured distances)."""
+    saturates, and Adam steps dead channels by the sign of that noise (DESIGN section 16 has both measured distances).
+    out_dtype: None (fp32 on the device, the promoted dtype on the CPU) or the 16-bit dtype of the conv that reads y.  A 16-bit
+    x (a conv output under autocast) is read and saved as it is; g_x has x's dtype."""
 
     @staticmethod
-    def forward(ctx, x, a, b, halo):
-        if x.is_cuda:
+    def forward(ctx, x, a, b, halo, out_dtype):
+        if x.is_cuda and (x.dtype in _IO16 or out_dtype in _IO16):
+            if not _one16(x.dtype, out_dtype):
+                x = x.float()
+            stats["io16_hip"] += 1
+            y = ops.fixup_act_io(x, a, b, halo, out_dtype or torch.float32)
+        elif x.is_cuda:
             y = ops.fixup_act(x.float(), a, b, halo)
         else:
-            y = F.elu(x + a) + b
+            y = F.elu(x + a) + b                        # a, b are [1] fp32 tensors: a 16-bit x promotes to fp32
+            if out_dtype is not None:
+                y = y.to(out_dtype)
             if halo:
                 y = pad_circular_nhwc(y)
         ctx.save_for_backward(x, a)
@@ -192,40 +244,61 @@ class _ActFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g):
         x, a = ctx.saved_tensors
-        if g.is_cuda:
-            g_x, g_a, g_b = ops.fixup_act_backward(_dense(g.float()), x, a, ctx.halo)
+        if g.is_cuda and (g.dtype in _IO16 or x.dtype in _IO16):
+            g_x, g_a, g_b = ops.fixup_act_backward_io(_dense(g), x, a, ctx.halo)
+        elif g.is_cuda:
+            g_x, g_a, g_b = ops.fixup_act_backward(_dense(g.float()), x.float(), a, ctx.halo)
         else:
+            g = _up(g)
             if ctx.halo:
                 g = fold_circular_nhwc(g)
             g_x = g * elu_grad(x + a)
-            g_a, g_b = g_x.sum(), g.sum()
-        return g_x, _like(g_a, a), _like(g_b, ctx.b), None
+            g_a, g_b = g_x.sum(), g.sum()               # of the unrounded terms
+            g_x = g_x.to(x.dtype)
+        return g_x, _like(g_a, a), _like(g_b, ctx.b), None, None
 
 
 class _AddFn(torch.autograd.Function):
-    """y = x + c, c a one-element parameter.  g_x is the incoming gradient itself; g_c = sum g."""
+    """y = x + c, c a one-element parameter.  g_c = sum g; g_x is the incoming gradient itself, or, where y and x differ in
+    dtype (a 16-bit y of an fp32 x, an fp32 y of a 16-bit x), its cast, written by the launch that sums it."""
 
     @staticmethod
-    def forward(ctx, x, c):
-        ctx.c = c
-        return ops.fixup_act(x.float(), None, c) if x.is_cuda else x + c
+    def forward(ctx, x, c, out_dtype):
+        ctx.c, ctx.x_dtype = c, x.dtype
+        if x.is_cuda and (x.dtype in _IO16 or out_dtype in _IO16):
+            if not _one16(x.dtype, out_dtype):
+                x = x.float()
+            stats["io16_hip"] += 1
+            return ops.fixup_act_io(x, None, c, 0, out_dtype or torch.float32)
+        if x.is_cuda:
+            return ops.fixup_act(x.float(), None, c)
+        y = x + c
+        return y if out_dtype is None else y.to(out_dtype)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        if g.is_cuda:
+        if g.is_cuda and (g.dtype in _IO16 or ctx.x_dtype in _IO16) and _one16(g.dtype, ctx.x_dtype):
+            g, _, g_c = ops.fixup_act_backward_io(_dense(g), None, None, act=False, x_dtype=ctx.x_dtype)
+        elif g.is_cuda:
             g, _, g_c = ops.fixup_act_backward(_dense(g.float()), None, None, act=False)
         else:
-            g_c = g.sum()
-        return g, _like(g_c, ctx.c)
+            g_c = _up(g).sum()
+            g = g.to(ctx.x_dtype)
+        return g, _like(g_c, ctx.c), None
 
 
 class _OutFn(torch.autograd.Function):
-    """y = (t * scale + bias4) + (skip [+ bias1d])."""
+    """y = (t * scale + bias4) + (skip [+ bias1d]), the fp32 residual stream.  t and skip may each be 16-bit (conv outputs under
+    autocast): they are read, and t is saved, as they are; g_t has t's dtype and a 16-bit skip gets its own copy of g."""
 
     @staticmethod
     def forward(ctx, t, skip, scale, bias4, bias1d):
-        if t.is_cuda:
+        ctx.skip_dtype = skip.dtype
+        if t.is_cuda and (t.dtype in _IO16 or skip.dtype in _IO16):
+            stats["io16_hip"] += 1
+            y = ops.fixup_out_io(t, _dense(skip), scale, bias4, bias1d)
+        elif t.is_cuda:
             y = ops.fixup_out(t.float(), _dense(skip.float()), scale, bias4, bias1d)
         else:
             y = (t * scale + bias4) + (skip if bias1d is None else skip + bias1d)
@@ -237,12 +310,15 @@ class _OutFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g):
         t, scale = ctx.saved_tensors
-        if g.is_cuda:
-            g = _dense(g.float())
-            g_t, g_scale, g_bias = ops.fixup_out_backward(g, t, scale)
+        if g.is_cuda and (t.dtype in _IO16 or ctx.skip_dtype in _IO16):
+            g_t, g_skip, g_scale, g_bias = ops.fixup_out_backward_io(_dense(g.float()), t, scale, ctx.skip_dtype)
+        elif g.is_cuda:
+            g_skip = _dense(g.float())
+            g_t, g_scale, g_bias = ops.fixup_out_backward(g_skip, t.float(), scale)
         else:
-            g_t, g_scale, g_bias = g * scale, (g * t).sum(), g.sum()
-        return (g_t, g, _like(g_scale, scale), _like(g_bias, ctx.b4),
+            g = _up(g)
+            g_t, g_skip, g_scale, g_bias = (g * scale).to(t.dtype), g.to(ctx.skip_dtype), (g * t).sum(), g.sum()
+        return (g_t, g_skip, _like(g_scale, scale), _like(g_bias, ctx.b4),
                 _like(g_bias, ctx.b1d) if ctx.b1d is not None else None)
 
 
@@ -253,7 +329,8 @@ class _BicubicFn(torch.autograd.Function):
     def forward(ctx, x, pre_bias):
         ctx.pb = pre_bias
         if not x.is_cuda:
-            return _bicubic_up2_torch(x, pre_bias)
+            with torch.autocast("cpu", enabled=False):
+                return _bicubic_up2_torch(_up(x), pre_bias)
         if pre_bias is None and x.shape[3] % 4 == 0:
             return ops.bicubic_up2(x.float())                  # the inference kernel: the same sums in the same order
         return ops.bicubic_up2_bias(x.float(), pre_bias)
@@ -264,7 +341,7 @@ class _BicubicFn(torch.autograd.Function):
         if g.is_cuda:
             g_x, g_pb = ops.bicubic_up2_backward(_dense(g.float()), want_bias=ctx.pb is not None)
         else:
-            g_x = _bicubic_up2_adjoint_torch(g)
+            g_x = _bicubic_up2_adjoint_torch(_up(g))
             g_pb = g_x.sum()
         return g_x, _like(g_pb, ctx.pb) if ctx.pb is not None else None
 
@@ -278,7 +355,8 @@ class _Up2ActFn(torch.autograd.Function):
         if t_low.is_cuda:
             y = ops.up2_act(t_low.float(), a, b)
         else:
-            y = F.elu(_bicubic_up2_torch(t_low, None) + a) + b
+            with torch.autocast("cpu", enabled=False):
+                y = F.elu(_bicubic_up2_torch(_up(t_low), None) + a) + b
         ctx.save_for_backward(t_low, a)
         ctx.b = b
         return y
@@ -290,7 +368,7 @@ class _Up2ActFn(torch.autograd.Function):
         if g.is_cuda:
             g_t_low, g_a, g_b = ops.up2_act_backward(_dense(g.float()), t_low.float(), a)
         else:
-            g_v = g * elu_grad(_bicubic_up2_torch(t_low, None) + a)
+            g_v = _up(g) * elu_grad(_bicubic_up2_torch(_up(t_low), None) + a)
             g_t_low, g_a, g_b = _bicubic_up2_adjoint_torch(g_v), g_v.sum(), g.sum()
         return g_t_low, _like(g_a, a), _like(g_b, ctx.b)
 
@@ -303,7 +381,8 @@ class _OutUpFn(torch.autograd.Function):
         if t.is_cuda:
             y = ops.fixup_out_up(t.float(), _dense(s_low.float()), scale, bias4, bias1d)
         else:
-            y = (t * scale + bias4) + (_bicubic_up2_torch(s_low, None) + bias1d)
+            with torch.autocast("cpu", enabled=False):
+                y = (t * scale + bias4) + (_bicubic_up2_torch(_up(s_low), None) + bias1d)
         ctx.save_for_backward(t, scale)
         ctx.b4, ctx.b1d = bias4, bias1d
         return y
@@ -315,6 +394,7 @@ class _OutUpFn(torch.autograd.Function):
         if g.is_cuda:
             g_t, g_s_low, g_scale, g_bias = ops.fixup_out_up_backward(_dense(g.float()), t.float(), scale)
         else:
+            g = _up(g)
             g_t, g_s_low, g_scale, g_bias = g * scale, _bicubic_up2_adjoint_torch(g), (g * t).sum(), g.sum()
         return g_t, g_s_low, _like(g_scale, scale), _like(g_bias, ctx.b4), _like(g_bias, ctx.b1d)
 
@@ -337,7 +417,8 @@ class _PreConvFn(torch.autograd.Function):
         ctx.has = (a is not None, b is not None)
         if x.is_cuda:
             return getattr(ops, cls.NODE + "_train_forward")(x.float(), w, a, b)
-        return cls._forward(x, w, a, b)
+        with torch.autocast("cpu", enabled=False):
+            return cls._forward(_up(x), w, a, b)
 
     @classmethod
     @once_differentiable
@@ -349,7 +430,7 @@ class _PreConvFn(torch.autograd.Function):
         if g.is_cuda:
             g, x, backward = _dense(g.float()), x.float(), getattr(ops, cls.NODE + "_train_backward")
         else:
-            backward = cls._backward
+            g, x, backward = _up(g), _up(x), cls._backward
         g_x, g_w, g_a, g_b = backward(g, x, w, a, b, need_x, need_w)
         return (g_x if need_x else None, g_w.to(w.dtype) if need_w else None, _like(g_a, a) if a is not None else None,
                 _like(g_b, b) if b is not None else None)
@@ -484,7 +565,9 @@ class _Conv3x3zFn(torch.autograd.Function):
         ctx.bias = bias
         if x.is_cuda:
             return ops.conv3x3z_train_forward(x.float(), w, bias, c)
-        return to_nhwc(F.conv2d(to_nchw(x if c is None else x + c), w, bias, padding=1))
+        with torch.autocast("cpu", enabled=False):
+            x = _up(x)
+            return to_nhwc(F.conv2d(to_nchw(x if c is None else x + c), w, bias, padding=1))
 
     @staticmethod
     @once_differentiable
@@ -496,7 +579,7 @@ class _Conv3x3zFn(torch.autograd.Function):
         if g.is_cuda:
             g_x, g_w, g_bias, g_c = ops.conv3x3z_train_backward(_dense(g.float()), x.float(), w, c, need_x, need_w, need_bias)
         else:
-            g_x, g_w, g_bias, g_c = _conv3x3z_backward_torch(g, x, w, c, need_x, need_w, need_bias)
+            g_x, g_w, g_bias, g_c = _conv3x3z_backward_torch(_up(g), _up(x), w, c, need_x, need_w, need_bias)
         return (g_x if need_x else None, g_w.to(w.dtype) if need_w else None,
                 g_bias.to(ctx.bias.dtype) if need_bias else None, _like(g_c, c) if c is not None else None)
 
@@ -508,26 +591,38 @@ def conv3x3z(x, w, bias=None, c=None):
     return _Conv3x3zFn.apply(x, w, bias, c)
 
 
-def fixup_act(x, a, b, halo=0):
-    """ELU(x + a) + b on [B, H, W, C]; halo = 1: [B, H + 2, W + 2, C] with the circular wrap written."""
-    return _ActFn.apply(x, a, b, int(halo))
+def fixup_act(x, a, b, halo=0, feeds_conv=False):
+    """ELU(x + a) + b on [B, H, W, C]; halo = 1: [B, H + 2, W + 2, C] with the circular wrap written.  feeds_conv: an F.conv2d
+    reads the result directly, so under 16-bit autocast the result is written in the autocast dtype -- the bits the conv's own
+    cast of the fp32 result would read; anywhere else, and without autocast, the result is fp32."""
+    return _ActFn.apply(x, a, b, int(halo), autocast16(x) if feeds_conv else None)
 
 
-def fixup_add(x, c):
-    return _AddFn.apply(x, c)
+def fixup_add(x, c, feeds_conv=False):
+    """x + c; feeds_conv as in fixup_act."""
+    return _AddFn.apply(x, c, autocast16(x) if feeds_conv else None)
 
 
 def fixup_out(t, skip, scale, bias4, bias1d=None):
     return _OutFn.apply(t, skip, scale, bias4, bias1d)
 
 
+def _fp32_node(x):
+    """A node without a 16-bit form (the resize nodes, the fused conv nodes): under 16-bit autocast it runs its fp32 kernels
+    on explicitly cast operands, correct but not 16-bit-native, and is counted."""
+    if autocast16(x) is not None:
+        stats["io16_fallbacks"] += 1
+
+
 def bicubic_up2(x, pre_bias=None):
+    _fp32_node(x)
     return _BicubicFn.apply(x, pre_bias)
 
 
 def up2_act(t_low, a, b):
     """ELU(bicubic_up2(t_low) + a) + b on [B, H, W, C] -> [B, 2H, 2W, C] as ONE node: csrc/up_train.hip on the device, a
     plain-torch restatement on CPU tensors."""
+    _fp32_node(t_low)
     return _Up2ActFn.apply(t_low, a, b)
 
 
@@ -535,6 +630,7 @@ def fixup_out_up(t, s_low, scale, bias4, bias1d):
     """(t * scale + bias4) + (bicubic_up2(s_low) + bias1d), t [B, 2H, 2W, C], s_low [B, H, W, C], as ONE node: csrc/up_train.hip
     on the device, a plain-torch restatement on CPU tensors."""
     assert tuple(t.shape) == (s_low.shape[0], 2 * s_low.shape[1], 2 * s_low.shape[2], s_low.shape[3]), (t.shape, s_low.shape)
+    _fp32_node(t)
     return _OutUpFn.apply(t, s_low, scale, bias4, bias1d)
 
 
@@ -555,16 +651,17 @@ def conv_routes(conv1x1="torch", conv_down="torch", conv3x3="torch", conv3x3z="t
 
 
 def _pre_torch(x, a, b):
+    """The op in front of an F.conv2d on the torch route: nothing sits between them, so under autocast it writes 16 bits."""
     if b is None:
         return x
-    return fixup_add(x, b) if a is None else fixup_act(x, a, b)
+    return fixup_add(x, b, feeds_conv=True) if a is None else fixup_act(x, a, b, feeds_conv=True)
 
 
 # node -> (the fused node, the torch route).  conv3x3's: the activation writes the wrap, the conv pads nothing.  conv3x3z's: the
 # conv pads zeros behind x + b, and takes the conv's bias (its pre-op is never an activation: a is None).
 _NODES = {"conv1x1": (conv1x1, lambda x, a, b, w: _conv(_pre_torch(x, a, b), w)),
           "conv_down": (conv_down, lambda x, a, b, w: _conv(_pre_torch(x, a, b), w, stride=2)),
-          "conv3x3": (conv3x3, lambda x, a, b, w: _conv(fixup_act(x, a, b, halo=1), w)),
+          "conv3x3": (conv3x3, lambda x, a, b, w: _conv(fixup_act(x, a, b, halo=1, feeds_conv=True), w)),
           "conv3x3z": (lambda x, w, a, b, bias=None: conv3x3z(x, w, bias, b),
                        lambda x, a, b, w, bias=None: _conv(_pre_torch(x, a, b), w, bias, padding=1))}
 
@@ -580,6 +677,7 @@ def _pre_conv(node, hip, x, a, b, w, bias=None):
         if (tuple(w.shape[2:]) == (k, k) and x.shape[1] % stride == 0 and x.shape[2] % stride == 0
                 and getattr(ops, node + "_train_supported")(w.shape[1], w.shape[0])):
             stats[node + "_hip"] += 1
+            _fp32_node(x)
             return fused(x, w, a, b, *extra)
         stats[node + "_fallbacks"] += 1
     return torch_route(x, a, b, w, *extra)

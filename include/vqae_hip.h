@@ -782,6 +782,33 @@ int vqae_fixup_out_f32(const float* t_dev, const float* skip_dev, const float* s
 int vqae_fixup_out_backward_f32(const float* g_dev, const float* t_dev, const float* scale_dev, int64_t n, float* g_t_dev,
                                 float* g_scale_dev, float* g_bias4_dev, float* g_bias1d_dev, void* workspace_dev,
                                 void* stream);
+/* Mixed-precision forms of the four entries above, for training under 16-bit autocast (csrc/fixup_train_io.hip): each
+ * tensor is fp32 or a 16-bit type, stated by a VQAE_DT_* code; the one-element parameters, the scalar gradients and the
+ * workspace (vqae_fixup_train_workspace_bytes) stay as above.  The arithmetic is the fp32 entry's on the up-cast values,
+ * and a 16-bit result is rounded once (RNE, torch's cast): every output tensor is bit for bit the _f32 entry on the
+ * up-cast inputs followed by the cast.  The scalar gradients are fp64 sums of the UNROUNDED fp32 terms, in the fp32
+ * entries' element order: bit for bit theirs where every tensor is aligned to its 4-element access (16 bytes fp32, 8 bytes
+ * 16-bit); any other alignment is taken, on the scalar path.  inf / NaN pass through.  All tensors fp32: the _f32 entry.
+ * Errors as above, and: a dtype code outside VQAE_DT_* -> VQAE_ERR_INVALID; two different 16-bit types in one call, a y
+ * of vqae_fixup_out_io other than fp32 -> VQAE_ERR_UNSUPPORTED.
+ *
+ * vqae_fixup_act_io: x (x_dtype) -> y (y_dtype), shapes as vqae_fixup_act_f32. */
+int vqae_fixup_act_io(const void* x_dev, int x_dtype, const float* a_dev, const float* b_dev, int act, int halo, int batch,
+                      int h, int w, int c, void* y_dev, int y_dtype, void* stream);
+/* g has the forward's y dtype (g_dtype), x its own (x_dtype); g_x is written in x_dtype.  Plain mode: x_dev is unused
+ * (NULL); where g_dtype == x_dtype g_x is the incoming tensor itself and is not written (pass NULL), otherwise g_x = g
+ * cast to x_dtype is written in the pass that sums it. */
+int vqae_fixup_act_backward_io(const void* g_dev, int g_dtype, const void* x_dev, int x_dtype, const float* a_dev, int act,
+                               int halo, int batch, int h, int w, int c, void* g_x_dev, float* g_a_dev, float* g_b_dev,
+                               void* workspace_dev, void* stream);
+/* t (t_dtype), skip (skip_dtype) -> y, which is the residual stream: y_dtype must be VQAE_DT_F32. */
+int vqae_fixup_out_io(const void* t_dev, int t_dtype, const void* skip_dev, int skip_dtype, const float* scale_dev,
+                      const float* bias4_dev, const float* bias1d_dev, int64_t n, void* y_dev, int y_dtype, void* stream);
+/* g fp32; g_t = g * *scale is written in t_dtype.  A 16-bit skip_dtype: g_skip_dev gets g cast to it in the same pass;
+ * fp32: the skip gradient is g itself and g_skip_dev is not written (pass NULL). */
+int vqae_fixup_out_backward_io(const float* g_dev, const void* t_dev, int t_dtype, const float* scale_dev, int64_t n,
+                               void* g_t_dev, void* g_skip_dev, int skip_dtype, float* g_scale_dev, float* g_bias4_dev,
+                               float* g_bias1d_dev, void* workspace_dev, void* stream);
 /* vqae_bicubic_up2_f32 with pre_bias read from the device (NULL: none) and any channel count; per output the same sums
  * in the same order. */
 int vqae_bicubic_up2_bias_f32(const float* x_dev, int batch, int h, int w, int c, const float* pre_bias_dev, float* y_dev,
