@@ -237,6 +237,15 @@ SYMBOLS = {
     "vqae_se_scale_workspace_bytes": (c_size_t, [c_int, c_int64, c_int]),
     "vqae_se_scale_forward_f32": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p]),
     "vqae_se_scale_backward_f32": (c_int, [c_void_p] * 3 + [c_int, c_int64, c_int] + [c_void_p] * 4),
+    # the _f32 argument lists with the dtype code(s) in front of the stream (csrc/mbconv_train_io.hip)
+    "vqae_bn_act_train_forward_io": (c_int, [c_void_p] * 5 + [c_int, c_double, c_double, c_int, c_int, c_int64, c_int]
+                                     + [c_void_p] * 5 + [c_int, c_void_p]),
+    "vqae_bn_act_train_backward_io": (c_int, [c_void_p] * 7 + [c_int, c_int, c_int, c_int64, c_int] + [c_void_p] * 3
+                                      + [c_int, c_void_p]),
+    "vqae_dwconv_train_forward_io": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "vqae_dwconv_train_backward_io": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 3 + [c_int, c_void_p]),
+    "vqae_se_scale_forward_io": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "vqae_se_scale_backward_io": (c_int, [c_void_p] * 3 + [c_int, c_int64, c_int] + [c_void_p] * 3 + [c_int, c_int, c_void_p]),
     "vqae_code_histogram_workspace_bytes": (c_size_t, [c_int, c_int64, c_int, c_int]),
     "vqae_code_histogram": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                     c_void_p, c_void_p]),

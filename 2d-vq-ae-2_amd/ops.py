@@ -453,6 +453,7 @@ def bn_act_train_forward(x, gamma, beta, running_mean, running_var, training, mo
     """BatchNorm2d (+ SiLU) on x [B, H, W, C] -> (y, mean [C], invstd [C] (fp64), pool [B, C] | None).  training: batch statistics, and
     running_mean / running_var (fp32 device tensors, or None) are updated IN PLACE by the launch that finishes the sums; else
     the running statistics normalise and nothing is written.  pool[b, c] = sum_hw y.  One row in training mode: ValueError."""
+    _need_f32("bn_act_train_forward", x=x)
     _need_gpu(x, gamma, beta)
     x = x.contiguous()
     B, H, W, C = x.shape
@@ -472,6 +473,7 @@ def bn_act_train_forward(x, gamma, beta, running_mean, running_var, training, mo
 def bn_act_train_backward(g, x, mean, invstd, gamma, beta, training, silu=False, g_pool=None):
     """-> (g_x, g_gamma [C], g_beta [C]) from the gradient of y, the forward's x, mean, invstd and (when the pooled output was
     used) the gradient of pool [B, C]."""
+    _need_f32("bn_act_train_backward", g=g, x=x)
     _need_gpu(g, x, mean, invstd, gamma, beta, g_pool)
     g, x = g.contiguous(), x.contiguous()
     B, H, W, C = x.shape
@@ -497,6 +499,7 @@ def _dw_out_shape(mode, H, W):
 
 def dwconv_train_forward(x, w, mode):
     """The depthwise conv of branch[3] on x [B, H, W, C] with the module's own weight [C, 1, k, k], read in place."""
+    _need_f32("dwconv_train_forward", x=x)
     _need_gpu(x, w)
     x = x.contiguous()
     B, H, W, C = x.shape
@@ -510,6 +513,7 @@ def dwconv_train_forward(x, w, mode):
 
 def dwconv_train_backward(g, x, w, mode, need_x=True, need_w=True):
     """-> (g_x | None, g_w in w's shape | None); g_x gathered, g_w a fixed-order fp64 sum."""
+    _need_f32("dwconv_train_backward", g=g, x=x)
     _need_gpu(g, x, w)
     g, x = g.contiguous(), x.contiguous()
     B, H, W, C = x.shape
@@ -525,6 +529,7 @@ def dwconv_train_backward(g, x, w, mode, need_x=True, need_w=True):
 
 def se_scale_forward(x, gate):
     """x [B, H, W, C] * gate [B, C]."""
+    _need_f32("se_scale_forward", x=x)
     _need_gpu(x, gate)
     x, gate = x.contiguous(), gate.float().contiguous()
     B, H, W, C = x.shape
@@ -536,6 +541,7 @@ def se_scale_forward(x, gate):
 
 def se_scale_backward(g, x, gate):
     """-> (g_x = g * gate, g_gate [B, C] = sum_hw g * x)."""
+    _need_f32("se_scale_backward", g=g, x=x)
     _need_gpu(g, x, gate)
     g, x, gate = g.contiguous(), x.contiguous(), gate.float().contiguous()
     B, H, W, C = x.shape
@@ -544,6 +550,123 @@ def se_scale_backward(g, x, gate):
     g_gate = torch.empty((B, C), dtype=torch.float32, device=x.device)
     ws = _ws(L.lib().vqae_se_scale_workspace_bytes(B, H * W, C), x.device)
     L.check(L.lib().vqae_se_scale_backward_f32(_p(g), _p(x), _p(gate), B, H * W, C, _p(g_x), _p(g_gate), _p(ws), _stream()))
+    return g_x, g_gate
+
+
+# ---- the same six ops with 16-bit I/O (csrc/mbconv_train_io.hip): the [B, H, W, C] tensors of a call share one dtype (fp32,
+# bf16 or f16), the small tensors stay fp32 / fp64, the gate fp32 or the tensors' dtype.  Each is bit for bit the fp32 op on the
+# up-cast inputs followed by torch's cast, without the casts.
+def _same_io(who, **tensors):
+    """The one dtype of the [B, H, W, C] tensors of a call -> (torch dtype, VQAE_DT_* code)."""
+    dts = {t.dtype for t in tensors.values() if t is not None}
+    assert len(dts) == 1, f"{who}: {', '.join(f'{k} {t.dtype}' for k, t in tensors.items() if t is not None)}: one dtype per call"
+    dt = dts.pop()
+    return dt, _io_code(who, "/".join(tensors), dt)
+
+
+def bn_act_train_forward_io(x, gamma, beta, running_mean, running_var, training, momentum, eps, silu=False, want_pool=False):
+    """bn_act_train_forward on x fp32, bf16 or f16 -> (y in x's dtype, mean, invstd (fp64), pool (fp32) | None): y rounded once,
+    every statistic and pool from the unrounded fp32 values."""
+    _, dt = _same_io("bn_act_train_forward_io", x=x)
+    _need_gpu(x, gamma, beta)
+    x = x.contiguous()
+    B, H, W, C = x.shape
+    dev = x.device
+    for t in (running_mean, running_var):
+        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()), "running statistics: dense fp32 in HBM"
+    y = torch.empty_like(x)
+    stat = torch.empty((2, C), dtype=torch.float64, device=dev)
+    pool = torch.empty((B, C), dtype=torch.float32, device=dev) if want_pool else None
+    ws = _ws(L.lib().vqae_bn_act_train_workspace_bytes(B, H * W, C), dev)
+    L.check(L.lib().vqae_bn_act_train_forward_io(_p(x), _p(_vec(gamma)), _p(_vec(beta)), _p(running_mean), _p(running_var),
+                                                 int(training), float(momentum), float(eps), int(silu), B, H * W, C, _p(y),
+                                                 _p(stat[0]), _p(stat[1]), _p(pool), _p(ws), dt, _stream()))
+    return y, stat[0], stat[1], pool
+
+
+def bn_act_train_backward_io(g, x, mean, invstd, gamma, beta, training, silu=False, g_pool=None):
+    """bn_act_train_backward on g and x of one dtype -> (g_x in that dtype, g_gamma [C], g_beta [C] fp32)."""
+    _, dt = _same_io("bn_act_train_backward_io", g=g, x=x)
+    _need_gpu(g, x, mean, invstd, gamma, beta, g_pool)
+    g, x = g.contiguous(), x.contiguous()
+    B, H, W, C = x.shape
+    assert g.shape == x.shape, (g.shape, x.shape)
+    dev = x.device
+    g_x = torch.empty_like(x)
+    sums = torch.empty((2, C), dtype=torch.float32, device=dev)
+    ws = _ws(L.lib().vqae_bn_act_train_workspace_bytes(B, H * W, C), dev)
+    gp = None if g_pool is None else g_pool.float().contiguous()
+    L.check(L.lib().vqae_bn_act_train_backward_io(_p(g), _p(x), _p(mean.contiguous()), _p(invstd.contiguous()), _p(_vec(gamma)),
+                                                  _p(_vec(beta)), _p(gp), int(training), int(silu), B, H * W, C, _p(g_x),
+                                                  _p(sums), _p(ws), dt, _stream()))
+    return g_x, sums[1], sums[0]
+
+
+def dwconv_train_forward_io(x, w, mode):
+    """dwconv_train_forward on x fp32, bf16 or f16 -> y in x's dtype; w the module's fp32 weight, each tap rounded to x's dtype
+    in registers."""
+    _, dt = _same_io("dwconv_train_forward_io", x=x)
+    _need_gpu(x, w)
+    x = x.contiguous()
+    B, H, W, C = x.shape
+    k = 3 if mode == L.DW_SAME else 2
+    assert tuple(w.shape) == (C, 1, k, k), (w.shape, C, mode)
+    Ho, Wo = _dw_out_shape(mode, H, W)
+    y = torch.empty((B, Ho, Wo, C), dtype=x.dtype, device=x.device)
+    L.check(L.lib().vqae_dwconv_train_forward_io(_p(x), _p(_vec(w)), mode, B, H, W, C, _p(y), dt, _stream()))
+    return y
+
+
+def dwconv_train_backward_io(g, x, w, mode, need_x=True, need_w=True):
+    """dwconv_train_backward on g and x of one dtype -> (g_x in that dtype | None, g_w fp32 in w's shape | None)."""
+    _, dt = _same_io("dwconv_train_backward_io", g=g, x=x)
+    _need_gpu(g, x, w)
+    g, x = g.contiguous(), x.contiguous()
+    B, H, W, C = x.shape
+    assert tuple(g.shape) == (B, *_dw_out_shape(mode, H, W), C), (g.shape, x.shape, mode)
+    dev = x.device
+    g_x = torch.empty_like(x) if need_x else None
+    g_w = torch.empty(tuple(w.shape), dtype=torch.float32, device=dev) if need_w else None
+    ws = _ws(L.lib().vqae_dwconv_train_workspace_bytes(B, H, W, C, mode), dev) if need_w else None
+    L.check(L.lib().vqae_dwconv_train_backward_io(_p(g), _p(x), _p(_vec(w)), mode, B, H, W, C, _p(g_x), _p(g_w), _p(ws), dt,
+                                                  _stream()))
+    return g_x, g_w
+
+
+def _gate_io(who, gate, x_dtype):
+    """The gate as the kernels read it: in x's dtype or in fp32 (any other dtype is up-cast) -> (gate, its code)."""
+    if gate.dtype != x_dtype and gate.dtype != torch.float32:
+        gate = gate.float()
+    return gate.contiguous(), _io_code(who, "gate", gate.dtype)
+
+
+def se_scale_forward_io(x, gate):
+    """se_scale_forward on x fp32, bf16 or f16 and gate [B, C] in fp32 or x's dtype -> y in x's dtype."""
+    xd, dt = _same_io("se_scale_forward_io", x=x)
+    _need_gpu(x, gate)
+    x = x.contiguous()
+    gate, dg = _gate_io("se_scale_forward_io", gate, xd)
+    B, H, W, C = x.shape
+    assert tuple(gate.shape) == (B, C), (gate.shape, x.shape)
+    y = torch.empty_like(x)
+    L.check(L.lib().vqae_se_scale_forward_io(_p(x), _p(gate), B, H * W, C, _p(y), dt, dg, _stream()))
+    return y
+
+
+def se_scale_backward_io(g, x, gate):
+    """se_scale_backward on g and x of one dtype -> (g_x in that dtype, g_gate [B, C] in the gate's dtype: the fp32 sum, rounded
+    once more for a 16-bit gate)."""
+    xd, dt = _same_io("se_scale_backward_io", g=g, x=x)
+    _need_gpu(g, x, gate)
+    g, x = g.contiguous(), x.contiguous()
+    gate, dg = _gate_io("se_scale_backward_io", gate, xd)
+    B, H, W, C = x.shape
+    assert g.shape == x.shape, (g.shape, x.shape)
+    g_x = torch.empty_like(x)
+    g_gate = torch.empty((B, C), dtype=gate.dtype, device=x.device)
+    ws = _ws(L.lib().vqae_se_scale_workspace_bytes(B, H * W, C), x.device)
+    L.check(L.lib().vqae_se_scale_backward_io(_p(g), _p(x), _p(gate), B, H * W, C, _p(g_x), _p(g_gate), _p(ws), dt, dg,
+                                              _stream()))
     return g_x, g_gate
 
 

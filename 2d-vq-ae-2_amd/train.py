@@ -96,7 +96,7 @@ between the casts torch would have made.  With every tensor fp32 the Functions c
 stats["io16_hip"] counts the nodes that ran a 16-bit form; stats["io16_fallbacks"] counts, under autocast, the nodes that have
 none and run their fp32 kernels on explicitly cast operands, correct but not 16-bit-native: the resize nodes (bicubic_up2,
 up2_act, fixup_out_up) and the fused conv nodes of the "hip" routes, which get fp32 operands.  The quantiser runs fp32, as in
-the reference (cdist is an fp32 op under autocast); MBConv training (train_mbconv.py) is fp32.
+the reference (cdist is an fp32 op under autocast); MBConv training under autocast is train_mbconv.py's.
 """
 import functools
 

@@ -27,10 +27,33 @@ Every sum of the three nodes (the batch statistics, g_gamma / g_beta, pool, the 
 fixed-order fp64 sum without atomics: two runs give the same bits.  The dense convs' gradients are torch's.
 
 Each Function has a restatement in plain torch ops, taken when its tensors are on the CPU: the same forward and the SAME
-hand-derived backward, which is what torch.autograd.gradcheck checks in tests/test_mbconv_train_cpu.py.  fp32 only on the
-device; the Functions are once-differentiable.  train.py and the inference mirrors are untouched: `train.forward_train` still
-refuses an MBConv model and `layers.conv_block.MBConv` still refuses `.train()`; the trainable module is
-layers.mbconv_train.MBConv.
+hand-derived backward, which is what torch.autograd.gradcheck checks in tests/test_mbconv_train_cpu.py.  The Functions are
+once-differentiable.  train.py and the inference mirrors are untouched: `train.forward_train` still refuses an MBConv model
+and `layers.conv_block.MBConv` still refuses `.train()`; the trainable module is layers.mbconv_train.MBConv.
+
+16-bit autocast (`torch.autocast("cuda", dtype=torch.bfloat16 | torch.float16)` around the step; no keyword -- autocast is the
+switch, because the convs produce the 16-bit tensors; f16 with torch.amp.GradScaler, inf / NaN pass through the nodes as
+through torch's ops).  The reference's rounding points: under autocast EVERY activation tensor of an MBConv block is 16-bit --
+the conv outputs, the BatchNorm output, SiLU, the depthwise conv, the SE mean, the gate, the SE product, the last BatchNorm and
+the residual sum -- while the running statistics and every parameter gradient stay fp32.  So, unlike the Fixup stacks, the
+residual stream is 16-bit, and each of the three nodes reads and writes 16 bits (csrc/mbconv_train_io.hip, ops.*_io):
+
+    reads     a 16-bit x as it is -- no `.float()` copy -- and saves it as it is: half the saved activation memory of the node
+    writes    y, and in the backward g_x, in x's dtype, rounded ONCE on store from the fp32 arithmetic of the fp32 kernels
+    small     mean, invstd fp64; pool, g_gamma, g_beta, g_w, the running statistics fp32, all sums of the UNROUNDED fp32 terms;
+              the gate (and g_gate) in fp32 or x's dtype, as the gate MLP hands it over; the depthwise taps are the module's
+              fp32 weight rounded to x's dtype in registers (autocast casts a conv weight)
+
+One rounding per node, on purpose: stock torch rounds z to 16 bits between BatchNorm and SiLU and again behind SiLU; the fused
+node rounds y only, and its backward recomputes z from the saved 16-bit x in fp32.  A node is therefore bit for bit its fp32 form
+between the casts torch would have made, not bit for bit the reference's 16-bit run; the tests hold it to the distance to fp64.
+With every tensor fp32 the Functions call what they always called.  The fall-backs (a BatchNorm or depthwise conv outside the
+route rule) and the CPU restatements follow the same rule in plain torch ops: a 16-bit input is up-cast, the arithmetic is fp32
+with autocast off, the result is rounded once to the input's dtype.  io16_stats["io16_hip"] counts the nodes that ran a 16-bit
+kernel, io16_stats["io16_fallbacks"] the 16-bit tensors that took a torch restatement on the device (a dict beside `stats`,
+whose four route counters keep counting every node).  forward_train up-casts the pre-VQ
+features to fp32 in front of the quantiser (cdist is an fp32 op under autocast); `t + skip`, the SE gate MLP and
+num_batches_tracked stay torch ops.
 """
 import torch
 import torch.nn.functional as F
@@ -39,9 +62,11 @@ from torch.autograd.function import once_differentiable
 from . import _lib as L
 from . import ops, train
 from .layers.conv_block import MBConv as _MBConvMirror
-from .train import _compute_dtype, _dense, pad_circular_nhwc, to_nchw, to_nhwc
+from .train import _IO16, _compute_dtype, _dense, autocast16, pad_circular_nhwc, to_nchw, to_nhwc
 
 stats = {"bn_hip": 0, "bn_fallbacks": 0, "dwconv_hip": 0, "dwconv_fallbacks": 0}
+# beside `stats` and not in it: tests/test_mbconv_train_gpu.py pins the key set of `stats` to the four route counters
+io16_stats = {"io16_hip": 0, "io16_fallbacks": 0}
 DW_MODES = {"same": L.DW_SAME, "out": L.DW_SAME, "down": L.DW_DOWN, "up": L.DW_UP}
 
 
@@ -59,10 +84,54 @@ def _bump(t):
         t.add_(0)
 
 
+def _fp32_math(t):
+    """The context of a torch restatement on a 16-bit tensor: autocast off for t's device, so that the up-cast operands stay
+    fp32 through F.conv2d and the einsums."""
+    return torch.autocast(t.device.type, enabled=False)
+
+
+def _count16(x, fused):
+    """A node on a 16-bit device tensor: a 16-bit kernel (fused) or a torch restatement."""
+    if x.is_cuda and x.dtype in _IO16:
+        io16_stats["io16_hip" if fused else "io16_fallbacks"] += 1
+
+
 # ---- autograd Functions --------------------------------------------------------------------------------------------------
+def _bn_forward_torch(x, gamma, beta, running_mean, running_var, training, momentum, eps, silu, want_pool):
+    """The restatement of bn_act's forward on an up-cast x (the 16-bit rule) -> (y, mean, invstd, pool | None), all fp32."""
+    B, H, W, C = x.shape
+    M = B * H * W
+    if training:
+        mean = x.mean((0, 1, 2))
+        var = ((x - mean) ** 2).mean((0, 1, 2))
+        if running_mean is not None:
+            running_mean.mul_(1 - momentum).add_(mean.to(running_mean.dtype), alpha=momentum)
+        if running_var is not None:
+            running_var.mul_(1 - momentum).add_((var * (M / (M - 1))).to(running_var.dtype), alpha=momentum)
+    else:
+        mean, var = running_mean.to(x.dtype), running_var.to(x.dtype)
+    invstd = torch.rsqrt(var + eps)
+    z = (x - mean) * invstd * gamma + beta
+    y = F.silu(z) if silu else z
+    return y, mean, invstd, (y.sum((1, 2)) if want_pool else None)
+
+
+def _bn_backward_torch(g, g_pool, x, mean, invstd, gamma, beta, training, silu):
+    """The hand-derived backward of bn_act on up-cast g and x -> (g_x, g_gamma, g_beta), all fp32."""
+    B, H, W, C = x.shape
+    if g_pool is not None:
+        g = g + g_pool.reshape(B, 1, 1, C)
+    xhat = (x - mean) * invstd
+    d = g * silu_grad(xhat * gamma + beta) if silu else g
+    g_beta, g_gamma = d.sum((0, 1, 2)), (d * xhat).sum((0, 1, 2))
+    M = B * H * W
+    g_x = gamma * invstd * (d - g_beta / M - xhat * (g_gamma / M) if training else d)
+    return g_x, g_gamma, g_beta
+
+
 class _BnActFn(torch.autograd.Function):
     """(y, pool) = BatchNorm2d (+ SiLU) of x [B, H, W, C]; pool [B, C] = sum_hw y where want_pool, else an empty tensor.  Saves x,
-    mean, invstd -- not z."""
+    mean, invstd -- not z.  A 16-bit x is read and saved as it is; y and g_x have its dtype, pool and the statistics do not."""
 
     @staticmethod
     def forward(ctx, x, gamma, beta, running_mean, running_var, training, momentum, eps, silu, want_pool):
@@ -72,12 +141,18 @@ class _BnActFn(torch.autograd.Function):
             raise ValueError(f"Expected more than 1 value per channel when training, got input size {[B, C, H, W]}")
         hip = x.is_cuda and ops.bn_act_train_supported(C)
         if hip:
-            y, mean, invstd, pool = ops.bn_act_train_forward(x.float(), gamma, beta, running_mean, running_var, training,
-                                                             momentum, eps, silu, want_pool)
+            fwd = ops.bn_act_train_forward_io if x.dtype in _IO16 else ops.bn_act_train_forward
+            y, mean, invstd, pool = fwd(x if x.dtype in _IO16 else x.float(), gamma, beta, running_mean, running_var, training,
+                                        momentum, eps, silu, want_pool)
             if training:
                 for t in (running_mean, running_var):
                     if t is not None:
                         _bump(t)
+        elif x.dtype in _IO16:
+            with _fp32_math(x):
+                y, mean, invstd, pool = _bn_forward_torch(x.float(), gamma.float(), beta.float(), running_mean, running_var,
+                                                          training, momentum, eps, silu, want_pool)
+            y = y.to(x.dtype)
         else:
             if training:
                 mean = x.mean((0, 1, 2))
@@ -110,9 +185,17 @@ class _BnActFn(torch.autograd.Function):
         if g is None:
             g = torch.zeros_like(x)
         B, H, W, C = x.shape
-        if hip:
+        if hip and x.dtype in _IO16:
+            g_x, g_gamma, g_beta = ops.bn_act_train_backward_io(_dense(g.to(x.dtype)), x, mean, invstd, gamma, beta, training,
+                                                                silu, g_pool)
+        elif hip:
             g_x, g_gamma, g_beta = ops.bn_act_train_backward(_dense(g.float()), x.float(), mean, invstd, gamma, beta, training,
                                                              silu, g_pool)
+        elif x.dtype in _IO16:
+            with _fp32_math(x):
+                g_x, g_gamma, g_beta = _bn_backward_torch(g.float(), None if g_pool is None else g_pool.float(), x.float(), mean,
+                                                          invstd, gamma.float(), beta.float(), training, silu)
+            g_x = g_x.to(x.dtype)
         else:
             if g_pool is not None:
                 g = g + g_pool.reshape(B, 1, 1, C)
@@ -169,6 +252,11 @@ class _DwConvFn(torch.autograd.Function):
     def forward(ctx, x, w, mode):
         ctx.save_for_backward(x, w)
         ctx.mode = mode
+        if x.dtype in _IO16:
+            if x.is_cuda:
+                return ops.dwconv_train_forward_io(x, w, mode)
+            with _fp32_math(x):                                # the taps rounded to x's dtype: autocast casts a conv weight
+                return _dw_forward_torch(x.float(), w.to(x.dtype).float(), mode).to(x.dtype)
         if x.is_cuda:
             return ops.dwconv_train_forward(x.float(), w, mode)
         return _dw_forward_torch(x, w, mode)
@@ -178,7 +266,14 @@ class _DwConvFn(torch.autograd.Function):
     def backward(ctx, g):
         x, w = ctx.saved_tensors
         need_x, need_w = ctx.needs_input_grad[:2]
-        if g.is_cuda:
+        if x.dtype in _IO16:
+            if g.is_cuda:
+                g_x, g_w = ops.dwconv_train_backward_io(_dense(g.to(x.dtype)), x, w, ctx.mode, need_x, need_w)
+            else:
+                with _fp32_math(x):
+                    g_x, g_w = _dw_backward_torch(g.float(), x.float(), w.to(x.dtype).float(), ctx.mode, need_x, need_w)
+                g_x = g_x.to(x.dtype) if need_x else None
+        elif g.is_cuda:
             g_x, g_w = ops.dwconv_train_backward(_dense(g.float()), x.float(), w, ctx.mode, need_x, need_w)
         else:
             g_x, g_w = _dw_backward_torch(g, x, w, ctx.mode, need_x, need_w)
@@ -192,6 +287,11 @@ class _SeScaleFn(torch.autograd.Function):
     def forward(ctx, x, gate):
         ctx.save_for_backward(x, gate)
         ctx.hip = x.is_cuda and ops.bn_act_train_supported(x.shape[-1])
+        if x.dtype in _IO16:
+            if ctx.hip:
+                return ops.se_scale_forward_io(x, gate)
+            with _fp32_math(x):
+                return (x.float() * gate.float().reshape(gate.shape[0], 1, 1, -1)).to(x.dtype)
         if ctx.hip:
             return ops.se_scale_forward(x.float(), gate)
         return x * gate.reshape(gate.shape[0], 1, 1, -1)
@@ -200,7 +300,15 @@ class _SeScaleFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g):
         x, gate = ctx.saved_tensors
-        if ctx.hip:
+        if x.dtype in _IO16:
+            if ctx.hip:
+                g_x, g_gate = ops.se_scale_backward_io(_dense(g.to(x.dtype)), x, gate)
+            else:
+                with _fp32_math(x):
+                    gf = g.float()
+                    g_x = (gf * gate.float().reshape(gate.shape[0], 1, 1, -1)).to(x.dtype)
+                    g_gate = (gf * x.float()).sum((1, 2))
+        elif ctx.hip:
             g_x, g_gate = ops.se_scale_backward(_dense(g.float()), x.float(), gate)
         else:
             g_x, g_gate = g * gate.reshape(gate.shape[0], 1, 1, -1), (g * x).sum((1, 2))
@@ -219,7 +327,9 @@ def bn_act(x, bn, silu=False, want_pool=False):
     y, pool = _BnActFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.training, float(bn.momentum),
                              float(bn.eps), bool(silu), bool(want_pool))
     if x.is_cuda:
-        stats["bn_hip" if ops.bn_act_train_supported(x.shape[-1]) else "bn_fallbacks"] += 1
+        fused = ops.bn_act_train_supported(x.shape[-1])
+        stats["bn_hip" if fused else "bn_fallbacks"] += 1
+        _count16(x, fused)
     if bn.training and bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
     return (y, pool) if want_pool else y
@@ -234,13 +344,20 @@ def dwconv(x, w, mode):
     if x.is_cuda:
         fused = ops.dwconv_train_supported(C, H, W, m)
         stats["dwconv_hip" if fused else "dwconv_fallbacks"] += 1
+        _count16(x, fused)
     else:
         fused = m != L.DW_DOWN or (H % 2 == 0 and W % 2 == 0)
-    return _DwConvFn.apply(x, w, m) if fused else _dw_forward_torch(x, w, m)
+    if fused:
+        return _DwConvFn.apply(x, w, m)
+    if x.dtype in _IO16:
+        with _fp32_math(x):
+            return _dw_forward_torch(x.float(), w.to(x.dtype).float(), m).to(x.dtype)
+    return _dw_forward_torch(x, w, m)
 
 
 def se_scale(x, gate):
-    """x [B, H, W, C] * gate [B, C] as ONE node."""
+    """x [B, H, W, C] * gate [B, C] as ONE node; a 16-bit x takes the gate in fp32 or in its own dtype."""
+    _count16(x, ops.bn_act_train_supported(x.shape[-1]) if x.is_cuda else False)
     return _SeScaleFn.apply(x, gate)
 
 
@@ -277,8 +394,11 @@ def block_forward_nhwc(block, x):
 
 
 def block_forward(block, x):
-    """One MBConv mirror on an NCHW-shaped tensor (channels_last preferred: no copy) -> NCHW-shaped, with a graph."""
-    return to_nchw(block_forward_nhwc(block, to_nhwc(_compute_dtype(x))))
+    """One MBConv mirror on an NCHW-shaped tensor (channels_last preferred: no copy) -> NCHW-shaped, with a graph.  Under 16-bit
+    autocast an x of the autocast dtype (the residual stream of the stack) is taken as it is."""
+    if x.dtype not in _IO16 or autocast16(x) != x.dtype:
+        x = _compute_dtype(x)
+    return to_nchw(block_forward_nhwc(block, to_nhwc(x)))
 
 
 def block_forward_torch(block, x):
@@ -335,6 +455,7 @@ def forward_train(model, x, return_indices=False, conv3x3z="torch"):
     for blk in pre:
         h = block_forward_nhwc(blk, h)
     vq = enc.vq_layers[0]
+    h = h.float()                           # the quantiser is fp32 under autocast too (cdist); a no-op on an fp32 tensor
     q, idx, vq_loss = vq(to_nchw(h)) if h.is_cuda else train._quantize_torch(vq, to_nchw(h))
     h = to_nhwc(q)
     for blk in post:

@@ -1046,6 +1046,38 @@ size_t vqae_se_scale_workspace_bytes(int batch, int64_t hw, int c);
 int vqae_se_scale_forward_f32(const float* x_dev, const float* gate_dev, int batch, int64_t hw, int c, float* y_dev, void* stream);
 int vqae_se_scale_backward_f32(const float* g_dev, const float* x_dev, const float* gate_dev, int batch, int64_t hw, int c,
                                float* g_x_dev, float* g_gate_dev, void* workspace_dev, void* stream);
+/* Mixed-precision forms of the six entries above, for training under 16-bit autocast (csrc/mbconv_train_io.hip): the _f32
+ * signatures with void* tensors plus dtype codes.  The [batch][h][w][c] tensors of a call (x, y, g, g_x) share ONE type,
+ * io_dtype (VQAE_DT_*); gamma, beta, the running statistics, pool, g_pool, g_beta_gamma and g_w stay fp32, mean and invstd
+ * fp64, the weight of the depthwise conv the module's own fp32 one.  gate and g_gate share a code of their own, gate_dtype:
+ * VQAE_DT_F32 or io_dtype.  The vqae_*_supported and vqae_*_workspace_bytes functions above hold unchanged (the partial rows
+ * are fp64 either way).
+ * The values are up-cast on load (exact), the arithmetic and the element-to-thread order are the fp32 entries', and a 16-bit
+ * result is rounded once on store (RNE, torch's cast): every tensor output is bit for bit the _f32 entry on the up-cast
+ * inputs followed by the cast, and every sum (mean, invstd, the running statistics, pool, g_beta_gamma, g_w, an fp32 g_gate)
+ * is the _f32 entry's bit for bit, taken from the UNROUNDED fp32 terms.  A BatchNorm + SiLU node therefore rounds ONCE (y), where
+ * stock torch under autocast rounds z and SiLU(z); its backward recomputes z from the saved 16-bit x in fp32.  The depthwise taps
+ * are rounded to io_dtype in registers (autocast casts the conv weight), in the forward and in the data gradient.  A 16-bit
+ * g_gate is the fp32 sum rounded once more.  inf / NaN pass through.  io_dtype VQAE_DT_F32: the _f32 entry.
+ * Errors as above, and: a dtype code outside VQAE_DT_* -> VQAE_ERR_INVALID; a 16-bit tensor (or gate) not on 8 bytes, an fp32
+ * one not on 16 -> VQAE_ERR_INVALID; two different 16-bit types in one call, a 16-bit gate beside fp32 tensors ->
+ * VQAE_ERR_UNSUPPORTED. */
+int vqae_bn_act_train_forward_io(const void* x_dev, const float* gamma_dev, const float* beta_dev, float* running_mean_dev,
+                                 float* running_var_dev, int training, double momentum, double eps, int act, int batch,
+                                 int64_t hw, int c, void* y_dev, double* mean_dev, double* invstd_dev, float* pool_dev,
+                                 void* workspace_dev, int io_dtype, void* stream);
+int vqae_bn_act_train_backward_io(const void* g_dev, const void* x_dev, const double* mean_dev, const double* invstd_dev,
+                                  const float* gamma_dev, const float* beta_dev, const float* g_pool_dev, int training, int act,
+                                  int batch, int64_t hw, int c, void* g_x_dev, float* g_beta_gamma_dev, void* workspace_dev,
+                                  int io_dtype, void* stream);
+int vqae_dwconv_train_forward_io(const void* x_dev, const float* w_dev, int mode, int batch, int h, int w, int c, void* y_dev,
+                                 int io_dtype, void* stream);
+int vqae_dwconv_train_backward_io(const void* g_dev, const void* x_dev, const float* w_dev, int mode, int batch, int h, int w,
+                                  int c, void* g_x_dev, float* g_w_dev, void* workspace_dev, int io_dtype, void* stream);
+int vqae_se_scale_forward_io(const void* x_dev, const void* gate_dev, int batch, int64_t hw, int c, void* y_dev, int io_dtype,
+                             int gate_dtype, void* stream);
+int vqae_se_scale_backward_io(const void* g_dev, const void* x_dev, const void* gate_dev, int batch, int64_t hw, int c,
+                              void* g_x_dev, void* g_gate_dev, void* workspace_dev, int io_dtype, int gate_dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * 7. Counts of stored code grids -- produces what the reference commits as data under scripts/create_wsi_histograms/
